@@ -15,15 +15,18 @@ transitions of all 65 536 envs of a GPU = 4 000 episodes per env (about a third 
 timed after W warm-up steps; `ms_per_step` is per bench step, `ms_per_batched_transition` per batched env transition
 (the figure earlier rounds called ms_per_step), and `ms_per_step_each` lists the K steps one by one.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see DESIGN.md §6 for every field).  After the timed region every rank replays one launch
-of the timed shape from reset and compares it with the C oracle (`parity_check`); at N = 1 rank 0 also collects the
-kernel's HBM traffic with two rocprofv3 --pmc child passes of the same launch shape (`roofline.traffic`, provenance in
-`roofline.traffic_source`) and times the oracle on the host cores (`cpu_baseline`).  Fields replayed from files under
-profiles/ instead of being measured in the run say so in a `source` / `how` key next to them.
+Prints ONE JSON line on rank 0 (see DESIGN.md §6 for every field).  A plain run sets up, warms up, times the K steps and
+prints the line, nothing else.  With --full, after the timed region every rank replays one launch of the timed shape from
+reset and compares it with the C oracle (`parity_check`); at N = 1 rank 0 also collects the kernel's HBM traffic with two
+rocprofv3 --pmc child passes of the same launch shape (`roofline.traffic`, provenance in `roofline.traffic_source`),
+measures the store-only ceiling and the side legs, and times the oracle on the host cores (`cpu_baseline`).  Fields
+replayed from files under profiles/ instead of being measured in the run say so in a `source` / `how` key next to them.
+--dump-outputs DIR writes what the last timed launch computed (benchlib.common.dump_rollout_outputs) as DIR/<name>.npy;
+the inputs depend on the command line alone, so two builds can be compared array for array.
 """
 import argparse
 import json
@@ -170,6 +173,10 @@ def run_single_process(args):
     wall = time.perf_counter() - t0
     transitions = args.steps * lps * fuse
     agg = env.aggregate(rews, fls)
+    if args.dump_outputs:
+        env.synchronize()
+        dump_rollout_outputs(args.dump_outputs, [(sh.start, r, f, sh.env.get_packed_state(), sh.env.ep_returns)
+                                                 for sh, r, f in zip(env.shards, rews, fls)], N * n, tiled8)
     parity = None
     if not args.no_parity_check:
         from oracle import oracle as O
@@ -244,6 +251,9 @@ def run_rollout_config(args, torch, VecOvercookedEnv, sharding, dev, rank, world
     metrics = torch.stack([rew[..., 0:2].sum().to(torch.float64), rew[..., 2:4].sum().to(torch.float64),
                            ((fl_t[-1, :, 7] if tiled8 else fl[-1]) & 1).sum().to(torch.float64)])
     sharding.allreduce_metrics(metrics)
+    if args.dump_outputs:  # (before the parity check, which reuses the output buffers)
+        dump_rollout_outputs(args.dump_outputs, [(0, rew, fl_t if tiled8 else fl, env.get_packed_state(), env.ep_returns)],
+                             n, tiled8, rank, world)
 
     value = float(world) * n * transitions / wall_max
 
@@ -257,6 +267,8 @@ def run_rollout_config(args, torch, VecOvercookedEnv, sharding, dev, rank, world
     if rank == 0 and world == 1 and not args.stub:
         if not args.no_traffic:
             traffic, traffic_src = measure_traffic(args, kernel, tiled8)
+        else:
+            traffic_src = {"how": "not collected", "why": "--no-traffic" if args.full else "plain run (--full measures it)"}
         if traffic is None:
             why = traffic_src.get("why")
             traffic, traffic_src = traffic_from_file(kernel, n, fuse, args.layout if args.config == 2 else "", bytes_per_launch)
@@ -282,7 +294,7 @@ def run_rollout_config(args, torch, VecOvercookedEnv, sharding, dev, rank, world
     # what the output format itself admits on this device at this batch size: the rollout's output stores and nothing else
     # (oc_output_stores_only, include/oc_amd.h), same arrays, after everything that reads them
     store_only = None
-    if rank == 0 and not args.stub:
+    if rank == 0 and not args.stub and args.full:
         try:
             store_only = measure_store_only(torch, dev, env, n, fuse, rew, fl, value / world, launch_med, tiled8=tiled8)
         except Exception as exc:  # an aid, never a reason to lose the line

@@ -83,8 +83,18 @@ def parse():
                     help="rehearsal on a box with fewer GPUs than ranks: rank r runs on GPU r %% device_count (with --backend gloo: RCCL "
                          "refuses two ranks on one device).  Exercises the per-rank path — process group, env_offset, NUMA pinning, "
                          "per-rank parity, the metric reductions — with real kernels; it says NOTHING about scaling or xGMI")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the oracle parity check, the PMC traffic passes, the "
+                         "store-only ceiling, the flags-layout and side legs (other configs, general path, step / encode / "
+                         "training APIs) and the CPU baselines.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed launch computed as DIR/<name>.npy (float32 / "
+                         "float64, a fixed seeded sample of the envs plus per-step sums over all of them, <= 64 MB in all)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # internal: the process rocprofv3 wraps
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run measures the headline and nothing else
+        args.no_parity_check = args.no_extras = args.no_cpu_baseline = args.no_traffic = True
+    return args
 
 def usable_cores():
     """Host cores this process may actually use: the affinity mask, capped by the cgroup CPU quota (the GPU boxes show
@@ -336,6 +346,73 @@ def parity_check(torch, wl, make_env, n, rank, steps, rew, fl, threads, tiled8=F
             "what": "one %d-step oc_rollout_random launch from reset (seed 0, global env offset %d): every reward quad and "
                     "flag byte of every env-step, the final packed states and the episode returns, bit for bit against "
                     "oracle/overcooked_oracle.c" % (steps, rank * n)}
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: everything one run writes
+DUMP_MAX_ENVS = 512        # ... of which the per-env arrays cover at most this many envs
+
+
+def dump_env_sample(n, per_env_bytes, budget):
+    """The envs --dump-outputs writes in full: a fixed, seeded sample (sorted), as many as `budget` bytes allow."""
+    import numpy as np
+
+    k = int(min(n, DUMP_MAX_ENVS, budget // max(1, per_env_bytes)))
+    if k < 1:
+        raise SystemExit("--dump-outputs: the per-step sums alone exceed %d bytes at this launch length" % DUMP_MAX_BYTES)
+    return np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+
+def write_outputs(dirname, arrays, rank=0, world=1):
+    """DIR/<name>.npy (DIR/<name>_rank<r>.npy with several ranks) for every float32 / float64 array of `arrays`."""
+    import numpy as np
+
+    total = sum(a.nbytes for a in arrays.values())
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert total * world <= DUMP_MAX_BYTES, total
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), np.ascontiguousarray(a))
+
+def dump_rollout_outputs(dirname, parts, n, tiled8, rank=0, world=1, obs=None):
+    """--dump-outputs of a rollout run: what the caller of the last timed launch receives.  `parts` = [(first env, rewards
+    [T][m][4], flags [T][m] or [T/8][m][8], packed state [P][m][16], episode returns [m][4] or None)], one per shard of the
+    `n` envs; `obs`: the observations [T][n][...] of a one-part rollout_encode run.  Written: rewards / flags (untiled) /
+    observations of every step, final_state and episode_returns of the sampled envs (env_index), and for all envs the
+    per-step reward_sums, flag_bit_counts (envs with flag bit b set) and observation_sums."""
+    import numpy as np
+    import torch
+
+    T = parts[0][1].shape[0]
+    P = np.asarray(parts[0][3]).shape[0]
+    o = 0 if obs is None else obs[0, 0].numel()
+    fixed = T * (4 + 8 + o) * 8
+    budget = (DUMP_MAX_BYTES - (1 << 20)) // world - fixed  # (1 MiB left for the .npy headers)
+    idx = dump_env_sample(n, T * (4 + 1 + o) * 4 + P * 16 * 4 + 4 * 4 + 8, budget)
+    sums, counts = np.zeros((T, 4)), np.zeros((T, 8))
+    rew_s, fl_s, st_s, ep_s = [], [], [], []
+    extra = {}
+    if obs is not None:
+        sel_t = torch.from_numpy(idx).to(obs.device)
+        extra["observations"] = obs.index_select(1, sel_t).cpu().numpy().astype(np.float32)
+        extra["observation_sums"] = np.stack([obs[t].to(torch.int32).sum(dim=0).cpu().numpy() for t in range(T)]).astype(np.float64)
+    for start, rew, fl, st, ep in parts:
+        m = rew.shape[1]
+        sel = idx[(idx >= start) & (idx < start + m)] - start
+        sel_t = torch.from_numpy(sel).to(rew.device)
+        sums += rew.sum(dim=1, dtype=torch.float64).cpu().numpy()
+        bits = torch.stack([(fl & (1 << b)).ne(0).sum(dim=1) for b in range(8)], dim=-1)
+        counts += bits.reshape(T, 8).cpu().numpy()  # (tiled: [T/8][8 steps][8 bits] -> [T][8 bits])
+        f = fl.index_select(1, sel_t)
+        fl_s.append((f.permute(0, 2, 1).reshape(T, len(sel)) if tiled8 else f).cpu().numpy())
+        rew_s.append(rew.index_select(1, sel_t).cpu().numpy())
+        st_s.append(np.asarray(st)[:, sel, :])
+        if ep is not None:
+            ep_s.append(ep.index_select(0, sel_t.to(ep.device)).cpu().numpy())
+    out = {"rewards": np.concatenate(rew_s, axis=1).astype(np.float32),
+           "flags": np.concatenate(fl_s, axis=1).astype(np.float32),
+           "final_state": np.concatenate(st_s, axis=1).astype(np.float32),
+           "env_index": idx.astype(np.float64), "reward_sums": sums, "flag_bit_counts": counts}
+    if ep_s:
+        out["episode_returns"] = np.concatenate(ep_s, axis=0).astype(np.float32)
+    write_outputs(dirname, dict(out, **extra), rank, world)
 
 def flags_tiled8_ok(args, env, fuse, rew, fl):
     """Does this batch / launch shape take the tiled flags layout (OC_OPT_FLAGS_TILED8: the pipelined joint-table kernel,

@@ -161,7 +161,7 @@ def general_legs(args, torch, VecOvercookedEnv, sharding, dev):
     return legs
 
 def encode_measure(torch, VecOvercookedEnv, sharding, dev, rank, world, n, launches=0, warm_launches=2, seconds=0.0,
-                   parity=True, extras=True):
+                   parity=True, extras=True, dump=""):
     """BASELINE configs[2] (the rollout of configs[1] plus oc_encode_lossless every step) on this rank's
     shard: ENC_FUSE transitions per oc_rollout_encode launch, the observation of every step kept ([ENC_FUSE][n] u8
     trajectory buffer: 7.7 GB at 65 536 9x5 envs).  `launches` fixed (the --config 3 line) or as many as fill `seconds`
@@ -191,6 +191,8 @@ def encode_measure(torch, VecOvercookedEnv, sharding, dev, rank, world, n, launc
     sharding.allreduce_max(tmax)
     wall = float(tmax.item())
     unit_bytes = n * (2 * sbytes + OUT_BYTES * fuse) + fuse * n * 2 * env.width * env.height * 26
+    if dump:  # --dump-outputs: the last timed launch's arrays (before the parity check reuses the buffers)
+        dump_rollout_outputs(dump, [(0, rew, fl, env.get_packed_state(), env.ep_returns)], n, False, rank, world, obs=obs)
     # parity of this launch shape: one ENC_FUSE-step launch from reset — every reward quad and flag byte, the final states,
     # and the u8 observation of EVERY step of every env (the oracle's encoder threaded over the host cores; compared on
     # the GPU) against the C oracle
@@ -271,7 +273,8 @@ def run_encode_config(args, torch, VecOvercookedEnv, sharding, dev, rank, world)
     transitions + observations each; same timing protocol as the headline, not the headline line."""
     lps = args.launches_per_step or ENC_LAUNCHES_PER_STEP
     m = encode_measure(torch, VecOvercookedEnv, sharding, dev, rank, world, args.envs, launches=args.steps * lps,
-                       warm_launches=args.warmup * lps, parity=not args.no_parity_check, extras=True)
+                       warm_launches=args.warmup * lps, parity=not args.no_parity_check, extras=not args.no_extras,
+                       dump=args.dump_outputs)
     out = {"metric": "env steps/sec (whole node)", "value": m["value"], "unit": "env steps/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": m["timed_region_s"] * 1e3 / args.steps,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",

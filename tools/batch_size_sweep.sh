@@ -5,7 +5,7 @@ cd ${GRAFT_REPO_ROOT:-.}
 for cfg in 2 4; do
 for n in 65536 131072 262144 524288 1048576; do
   l=$(( n > 262144 ? 20 : 60 ))
-  timeout 300 python3 bench.py --config $cfg --envs $n --steps 1 --warmup 1 --launches-per-step $l --no-extras --no-cpu-baseline --no-traffic 2>/dev/null > /tmp/sweep.json
+  timeout 300 python3 bench.py --config $cfg --envs $n --steps 1 --warmup 1 --launches-per-step $l --full --no-extras --no-cpu-baseline --no-traffic 2>/dev/null > /tmp/sweep.json
   python3 - <<PY
 import json
 d=json.load(open("/tmp/sweep.json"))

@@ -11,7 +11,7 @@ if [ -n "${TESTK:-}" ]; then
   timeout 900 python3 -m pytest tests -x -q -m gpu -k "$TESTK" > $O/pytest.log 2>&1
   tail -3 $O/pytest.log
 fi
-run() { tag=$1; shift; timeout 300 python3 bench.py --steps ${STEPS:-3} --warmup 1 --no-extras --no-cpu-baseline --no-traffic ${PARITY:-} "$@" > $O/$tag.json 2>> $O/err.log; }
+run() { tag=$1; shift; timeout 300 python3 bench.py --steps ${STEPS:-3} --warmup 1 --full --no-extras --no-cpu-baseline --no-traffic ${PARITY:-} "$@" > $O/$tag.json 2>> $O/err.log; }
 for rep in $(seq 1 ${REPS:-1}); do
 for lib in ${LIBS}; do
   t=$(basename $lib .so)
