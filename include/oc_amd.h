@@ -301,6 +301,27 @@ int oc_rollout_random(const OcBatch* batch, void* d_state, float* d_rewards, uin
                       const OcEventSink* events, void* stream);
 
 /*
+ * oc_rollout_record — oc_rollout_random (same arguments, same Philox stream, same results in d_state, d_rewards, d_flags,
+ * d_ep_returns and the start-state epochs) that also records what each step acted on: the trajectory of
+ * OvercookedEnv.get_rollouts / AgentEvaluator.evaluate_random_pair (env.py:485-580), its ep_states and ep_actions.
+ *   d_actions_out  [n_steps][n_envs][2] u8: the action indices (Action.INDEX_TO_ACTION) drawn at step k of the call — the
+ *                  d_actions layout of oc_step_many / oc_rollout_encode, so a recording replays through them; 2-byte aligned, or NULL
+ *   d_states_out   [n_steps][n_planes][n_envs][16] (oc_state_planes): slice k is the packed state step k ACTS ON — the pre-step
+ *                  state, after the previous step's restart (slice 0 = d_state on entry; the state after the last step is d_state
+ *                  on return); each slice is a packed-state array of its own (oc_encode_lossless, oc_featurize, ...); 16-byte
+ *                  aligned, or NULL.  Not both NULL.
+ *   d_rewards, d_flags: optional, as in oc_rollout_random.  recorded bytes per env-step: 16 per plane + 2 + 16 + 1 — 67 on grids of
+ *                  17..32 cells (cramped_room: 48 state, 2 actions, 16 rewards, 1 flags), 83 on 33..48 (asymmetric_advantages).
+ * Runs the one-wavefront arithmetic-movement kernel (k_rollout4, MODE 0) with recording stores.  options: OC_OPT_AUTO_RESET;
+ * OC_OPT_ONE_WAVEFRONT is accepted and has no effect; any other bit (OC_OPT_FLAGS_TILED8, OC_OPT_LANE_PAIR,
+ * OC_OPT_PREDICATE_INTERACT, ...) is OC_EINVAL, as are a start spec with regen_count > 0 (a re-drawn layout would have to be
+ * recorded per step too) and a table without OC_BATCH_TWO_PLAYERS.  All checks run before any device call.
+ */
+int oc_rollout_record(const OcBatch* batch, void* d_state, uint8_t* d_actions_out, void* d_states_out, float* d_rewards,
+                      uint8_t* d_flags, float* d_ep_returns, int horizon, uint32_t options, uint64_t seed,
+                      int64_t env_offset, int64_t t0, int n_steps, const OcStartSpec* start, void* stream);
+
+/*
  * oc_encode_lossless — the 26-layer observation of both players.
  * Replaces OvercookedGridworld.lossless_state_encoding (mdp.py:2385-2561) as called through
  * OvercookedEnv.lossless_state_encoding_mdp (env.py:276-280).

@@ -48,6 +48,7 @@ using oc_detail::g_err;
 using oc_detail::g_lds_refused;
 using oc_detail::StartArgs;
 using oc_detail::EvArgs;
+using oc_detail::RecArgs;
 
 // ------------------------------------------------------------------------------------------
 // Layout accessors.  `base` points at one 256-byte OcLayout, either in LDS or in global memory;

@@ -526,6 +526,38 @@ int oc_rollout_random(const OcBatch* b, void* d_state, float* d_rewards, uint8_t
     return check_launch("oc_rollout_random");
 }
 
+int oc_rollout_record(const OcBatch* b, void* d_state, uint8_t* d_actions_out, void* d_states_out, float* d_rewards,
+                      uint8_t* d_flags, float* d_ep_returns, int horizon, uint32_t options, uint64_t seed, int64_t env_offset,
+                      int64_t t0, int n_steps, const OcStartSpec* start, void* stream) {
+    // (every check comes before the first device call)
+    int n_obj = 0;
+    if (int rc = check_batch(b, &n_obj)) return rc;
+    if (!d_actions_out && !d_states_out) return fail(OC_EINVAL, "oc_rollout_record: d_actions_out and d_states_out are both NULL");
+    if (((uintptr_t)d_states_out & 15u) != 0) return fail(OC_EINVAL, "oc_rollout_record: d_states_out must be 16-byte aligned");
+    if (((uintptr_t)d_actions_out & 1u) != 0) return fail(OC_EINVAL, "oc_rollout_record: d_actions_out must be 2-byte aligned");
+    if (options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_WAVEFRONT))
+        return fail(OC_EINVAL, "oc_rollout_record: options other than OC_OPT_AUTO_RESET / OC_OPT_ONE_WAVEFRONT");
+    if (start && start->regen_count) return fail(OC_EINVAL, "oc_rollout_record: per-episode layout re-draws (start.regen_count > 0) are not recorded");
+    if ((b->batch_flags & OC_BATCH_TWO_PLAYERS) == 0) return fail(OC_EINVAL, "oc_rollout_record: needs a two-player table (OC_BATCH_TWO_PLAYERS)");
+    StartArgs sa;
+    if (!start_args(start, &sa, b)) return fail(OC_EINVAL, "oc_rollout_record: start.rnd_obj_prob_thresh must be in [0, 1]");
+    if (start && start->env_offset != env_offset) return fail(OC_EINVAL, "oc_rollout_record: start.env_offset differs from env_offset");
+    if (!d_state) return fail(OC_EINVAL, "oc_rollout_record: NULL state pointer");
+    if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_rollout_record: horizon must be in 1..65535");
+    if (n_steps < 0 || n_steps > (1 << 30)) return fail(OC_EINVAL, "oc_rollout_record: n_steps must be in 0..2^30");
+    if (b->n_envs == 0 || n_steps == 0) return OC_OK;
+    // the general one-wavefront instances of k_rollout4 (arithmetic movement, either dynamics, optional reward / flag rows) with REC
+    oc_detail::Rollout4Call c;
+    c.b = b; c.n_obj = n_obj; c.d_state = d_state; c.d_rewards = d_rewards; c.d_flags = d_flags; c.d_ep_returns = d_ep_returns;
+    c.horizon = horizon; c.options = options & OC_OPT_AUTO_RESET; c.seed = seed; c.env_offset = env_offset; c.t0 = t0;
+    c.n_steps = n_steps; c.sa = sa; c.ea = ev_args(nullptr, nullptr); c.stream = (hipStream_t)stream;
+    c.uniform = b->n_layouts == 1; c.lds = b->n_layouts <= LDS_LAYOUT_MAX; c.small = b->max_pots >= 1 && b->max_pots <= 2;
+    c.joint = false; c.old_dyn = true; c.out = false; c.pipe = true; c.events = false; c.tiled8 = false; c.noout = false; c.duo = false;
+    c.ra = oc_detail::RecArgs{d_actions_out, d_states_out};
+    oc_detail::launch_rollout4_record(c);
+    return check_launch("oc_rollout_record");
+}
+
 int oc_rollout_plan(const OcBatch* b, int horizon, uint32_t options, int64_t t0, int n_steps, int with_outputs, int event_sink,
                     const OcStartSpec* start, char* out, size_t out_size) {
     if (!out || out_size == 0) return fail(OC_EINVAL, "oc_rollout_plan: no output buffer");

@@ -26,10 +26,12 @@ namespace {
 
 // dynamic LDS of a k_rollout4 instance: its tables + the cell words of a workgroup's 256 envs
 template <bool U, int MP, bool LL, int MODE, bool OUT, bool OLD, int NF = JOINT_MAX_FLOOR, bool EV = false, bool PIPE = true,
-          bool RU = false, int CW = 2, bool NOCONF = false, bool FT8 = false>
+          bool RU = false, int CW = 2, bool NOCONF = false, bool FT8 = false, bool REC = false>
 constexpr size_t lds4_bytes(size_t cell_rows) {
-    // (EV: + the per-episode event counters, [N_EVENT_TYPES][BLOCK] u32 behind the cell words)
-    return (size_t)Lds4<U, LL, MODE, NF, U || RU, CW>::CELLS + cell_rows * BLOCK * CW + (EV ? (size_t)N_EVENT_TYPES * BLOCK * 4 : 0);
+    // (EV: + the per-episode event counters, [N_EVENT_TYPES][BLOCK] u32 behind the cell words; REC: + the packed object planes,
+    //  [n_obj][BLOCK] x 16 bytes)
+    return (size_t)Lds4<U, LL, MODE, NF, U || RU, CW>::CELLS + cell_rows * BLOCK * CW + (EV ? (size_t)N_EVENT_TYPES * BLOCK * 4 : 0) +
+           (REC ? (cell_rows - 2) * BLOCK : 0);
 }
 
 // (oc_rollout_plan: the instance is named instead of launched)
@@ -45,7 +47,7 @@ constexpr size_t lds4_bytes(size_t cell_rows) {
         hipLaunchKernelGGL((k_rollout4<U, MP, LL, MODE, OUT, OLD, NF, ##__VA_ARGS__>), grid4, block4, smem4, c.stream, b->d_layouts, \
                            b->n_layouts, b->d_layout_id, (uint4*)c.d_state, (float4*)c.d_rewards, c.d_flags,        \
                            (float4*)c.d_ep_returns, b->n_envs, b->width, c.n_obj, c.horizon, c.options,             \
-                           (uint32_t)c.seed, (uint32_t)(c.seed >> 32), c.env_offset, c.t0, c.n_steps, c.sa, c.ea);  \
+                           (uint32_t)c.seed, (uint32_t)(c.seed >> 32), c.env_offset, c.t0, c.n_steps, c.sa, c.ea, c.ra); \
     } while (0)
 
 // k_rollout5 (step_duo5.hpp): the per-env-terrain mover / interact kernel of round 6; two spare cell rows per lane
@@ -152,6 +154,14 @@ void launch_rollout4_mode0(const Rollout4Call& c) {
     }
     else if (c.small) GO4(false, 2, false, 0, false, true, 0);  // (old dynamics / no output arrays: the records through L2)
     else GO4(false, 8, false, 0, false, true, 0);               // more than two pots: one general instance
+}
+
+// oc_rollout_record: the three general instances above with REC — every step's pre-step state and actions stored as well
+void launch_rollout4_record(const Rollout4Call& c) {
+    OC_R4_PROLOGUE;
+    if (c.uniform && c.small) GO4(true, 2, true, 0, false, true, 0, false, true, false, 2, false, false, true);
+    else if (c.small) GO4(false, 2, false, 0, false, true, 0, false, true, false, 2, false, false, true);
+    else GO4(false, 8, false, 0, false, true, 0, false, true, false, 2, false, false, true);
 }
 #endif
 

@@ -41,6 +41,13 @@ struct EvArgs {
     uint32_t clear_on_done; // the caller restarts finished envs itself right after this launch (oc_multi_agent_step)
 };
 
+// Where a recorded launch (oc_rollout_record) writes each step's pre-step state and actions, by value in kernel arguments;
+// both NULL in every other launch.
+struct RecArgs {
+    uint8_t* actions;  // [n_steps][n_envs][2] u8, or NULL
+    void* states;      // [n_steps][n_planes][n_envs][16] wire-format states, 16-byte aligned, or NULL
+};
+
 // One oc_rollout_random call through k_rollout4, as oc_amd.hip hands it to the unit that holds the instance.
 struct Rollout4Call {
     const OcBatch* b;
@@ -62,10 +69,12 @@ struct Rollout4Call {
     bool tiled8;  // OC_OPT_FLAGS_TILED8: d_flags is [n_steps / 8][n_envs][8]
     bool noout;   // neither d_rewards nor d_flags: k_rollout5 runs its store-free instances
     bool duo;     // MODE 3: the per-env-terrain step split between mover and interact wavefronts (step_lut4.hpp)
+    RecArgs ra = {nullptr, nullptr};  // oc_rollout_record: the recording outputs (launch_rollout4_record)
 };
 OC_HIDDEN void launch_rollout4_joint_events(const Rollout4Call& c);  // rollout4.hip, OC_R4_PART 0
 OC_HIDDEN void launch_rollout4_mode2(const Rollout4Call& c);         // rollout4.hip, OC_R4_PART 1
 OC_HIDDEN void launch_rollout4_mode0(const Rollout4Call& c);         // rollout4.hip, OC_R4_PART 2
+OC_HIDDEN void launch_rollout4_record(const Rollout4Call& c);        // rollout4.hip, OC_R4_PART 2 (oc_rollout_record)
 OC_HIDDEN size_t rollout5_lds_bytes(bool lay_lds, bool big, bool ev, int n_obj);  // rollout4.hip, OC_R4_PART 1
 
 }  // namespace oc_detail

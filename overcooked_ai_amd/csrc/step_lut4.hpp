@@ -148,6 +148,10 @@ __device__ __forceinline__ void lds_wr64(uint32_t a, uint32_t x, uint32_t y) {
     const oc_u32x2 v = {x, y};
     *(OC_LDS oc_u32x2*)(uintptr_t)a = v;
 }
+__device__ __forceinline__ void lds_wr128(uint32_t a, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
+    const oc_u32x4 v = {x, y, z, w};
+    *(OC_LDS oc_u32x4*)(uintptr_t)a = v;
+}
 // Progress counters between the two wavefronts of a MODE 3 pair.  poll: a fresh wave-uniform read (never a value the
 // compiler has kept in a register); post: lane 0 writes — the LDS executes a wavefront's instructions in order, so whatever
 // the wavefront wrote (or read) before is done when the other side sees the new count.
@@ -241,15 +245,17 @@ __device__ __forceinline__ void load_env4(const LayC& C, const Lay L, const uint
     }
 }
 
+// The wire-format header of the env (players, timestep, pot ticks) from the registers and the pots' cell words; pot_fix_*: the
+// object a pot cell holds in the wire format where the cell word says otherwise (a pot that arrived holding an ingredient-less
+// soup object and kept it), cell 0xFFFFFFFF where there is none
 template <int MAXP, int CW>
-__device__ __forceinline__ void store_env4(const LayC& C, const Lay L, uint4* __restrict__ st, int64_t n, int64_t e,
-                                           int n_obj, int horizon, const Env4<MAXP>& s, uint32_t col) {
+__device__ __forceinline__ uint4 header_env4(const LayC& C, const Lay L, int horizon, const Env4<MAXP>& s, uint32_t col,
+                                             uint32_t (&pot_fix_cell)[MAXP], uint32_t (&pot_fix_obj)[MAXP]) {
     uint4 h;
     const uint32_t t = min((uint32_t)horizon - 1u - s.tleft + s.over, 0xFFFFu);  // the wire format's u16: saturates
     h.x = s.pos0 | (s.or0 << 8) | ((s.h0 & 0xFF00u) << 8) | (s.pos1 << 24);
     h.y = s.or1 | (s.h1 & 0xFF00u) | (t << 16);
     h.z = 0; h.w = 0;
-    uint32_t pot_fix_cell[MAXP], pot_fix_obj[MAXP];
 #pragma unroll
     for (int k = 0; k < MAXP; ++k) {
         pot_fix_cell[k] = 0xFFFFFFFFu; pot_fix_obj[k] = 0;
@@ -267,7 +273,14 @@ __device__ __forceinline__ void store_env4(const LayC& C, const Lay L, uint4* __
             if (o == 0u && ((s.exotic >> k) & 1u) && !live) { pot_fix_cell[k] = L.pot_cell(k); pot_fix_obj[k] = OC_O_SOUP; }
         }
     }
-    st[e] = h;
+    return h;
+}
+
+template <int MAXP, int CW>
+__device__ __forceinline__ void store_env4(const LayC& C, const Lay L, uint4* __restrict__ st, int64_t n, int64_t e,
+                                           int n_obj, int horizon, const Env4<MAXP>& s, uint32_t col) {
+    uint32_t pot_fix_cell[MAXP], pot_fix_obj[MAXP];
+    st[e] = header_env4<MAXP, CW>(C, L, horizon, s, col, pot_fix_cell, pot_fix_obj);
     for (int p = 0; p < n_obj; ++p) {
         uint32_t ow[4];
 #pragma unroll
@@ -483,11 +496,17 @@ __device__ __forceinline__ void env_reset4_draw(const LayC& C, const Lay L, int 
 //   wavefront stores the flag bytes of a whole unrolled block as ONE 512-byte piece of full lines instead of eight 64-byte
 //   pieces in eight far-apart rows (which cost the rollout ~6 % and its run-to-run spread: NOTEBOOK, round 4).  The launch
 //   must start on a block boundary and run whole blocks (t0 and n_steps multiples of 8): no rolled steps
+// REC (MODE 0, 16-bit cell words; oc_rollout_record): every step also stores the state it acts on — the pre-step state, after
+//   the previous step's restart — to ra.states + k * n_planes * n (wire format, [n_planes][n] x 16 bytes: each step's slice is a
+//   packed-state array of its own) and its two action indices to ra.actions + k * n * 2.  The object planes are not packed from
+//   the cell words every step (16 x n_obj LDS reads per lane): a packed copy, [n_obj][BLOCK] x 16 bytes behind the cell words, is
+//   kept current with one byte write per interacting player (the object byte of the cell word it writes) and re-packed after a
+//   restart; a step then reads it with one ds_read_b128 per plane.  The header comes from the registers as in store_env4.
 // PIPE (MODE 1, 2): the next step's faced cells are read one step ahead.  That hides the read behind the tail of the step
 //   when a SIMD holds one wavefront (65 536 envs); with two or more wavefronts per SIMD the extra LDS traffic costs
 //   more than the latency it hides (131 072 cramped_room envs: 0.48 vs 0.65 us per batched step), so big batches turn it off
 template <bool UNIFORM, int MAXP, bool LAY_LDS, int MODE, bool OUT, bool OLD, int NF = JOINT_MAX_FLOOR, bool EV = false,
-          bool PIPE = true, bool RU = false, int CW = 2, bool NOCONF = false, bool FT8 = false>
+          bool PIPE = true, bool RU = false, int CW = 2, bool NOCONF = false, bool FT8 = false, bool REC = false>
 #ifndef OC_R4_WAVES_MAX
 #define OC_R4_WAVES_MAX 4
 #endif
@@ -496,11 +515,13 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
                                                     float4* __restrict__ rewards, uint8_t* __restrict__ flags,
                                                     float4* __restrict__ ep_returns, int64_t n, int W, int n_obj,
                                                     int horizon, uint32_t options, uint32_t seed_lo, uint32_t seed_hi,
-                                                    int64_t env_offset, int64_t t0, int n_steps, StartArgs sa, EvArgs ea) {
+                                                    int64_t env_offset, int64_t t0, int n_steps, StartArgs sa, EvArgs ea,
+                                                    RecArgs ra) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn4[];
     constexpr bool RUX = UNIFORM || RU;  // one LUT variant, patched with the reward floats
     using M = Lds4<UNIFORM, LAY_LDS, MODE, NF, RUX, CW>;
     static_assert(CW == 2 || CW == 4, "cell words are u16 or u32");
+    static_assert(!REC || (MODE == 0 && CW == 2 && !EV && !FT8), "recording is served by the arithmetic-movement instances");
     if ((uint32_t)(uintptr_t)(OC_LDS uint8_t*)s_dyn4 != 0u) __builtin_trap();  // folds away: the region starts at address 0
     uint4* const s_lay = reinterpret_cast<uint4*>(s_dyn4 + M::LAY);
     uint4* const s_lut = reinterpret_cast<uint4*>(s_dyn4 + M::LUT);
@@ -554,6 +575,23 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
     const uint32_t delta4 = make_delta4(W);
     Env4<MAXP> s;
     load_env4<MAXP, CW>(C, L, st, n, e, n_obj, horizon, s, col);
+    // REC: this lane's packed object planes (16 bytes per plane, [plane][lane]) behind the cell words, and the bytes of the two
+    // cells the players face in the step being run
+    const uint32_t pk = (uint32_t)M::CELLS + ((uint32_t)n_obj * 16u + 2u) * (uint32_t)(BLOCK * CW) + tid * 16u;
+    uint32_t pk_f0 = 0, pk_f1 = 0;
+    auto pack_planes = [&]() __attribute__((always_inline)) {  // the packed copy from the cell words (launch start, restarts)
+        for (int p = 0; p < n_obj; ++p) {
+            uint32_t ow[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                ow[q] = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) ow[q] |= cw_obj<CW>(cw_rd<CW>(col + (uint32_t)(16 * p + 4 * q + b) * (BLOCK * CW))) << (8 * b);
+            }
+            lds_wr128(pk + (uint32_t)p * (BLOCK * 16u), ow[0], ow[1], ow[2], ow[3]);
+        }
+    };
+    if constexpr (REC) pack_planes();
     bool two = MODE == 1 || MODE == 2 || s.pos1 != 0xFFu;
     uint64_t fm = 0;  // MODE 2: bit c = cell c is floor (static per layout)
     auto floor_mask_of = [&](const Lay Lx) __attribute__((always_inline)) {
@@ -695,6 +733,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
         const uint32_t cw0 = cw_of_result<CW>(r0);  // player 0's faced cell afterwards
         cw_wr<CW>(fo0, cw0);
         cw_wr<CW>(fo1, cw_of_result<CW>(r1));
+        if constexpr (REC) {  // the object bytes of the two words just written, into the packed copy (same order)
+            lds_wr8(pk_f0, r0 >> 16);
+            lds_wr8(pk_f1, r1 >> 16);
+        }
         const uint32_t h0_before = s.h0, h1_before = s.h1, dc_before = s.dcount;
         const uint32_t dc_mid = dc_before + (uint32_t)((int32_t)e0.y >> 24);  // loose dishes after player 0's interact
         uint32_t dcount = dc_mid + (uint32_t)((int32_t)e1.y >> 24);
@@ -781,6 +823,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
                 r1 = interact4<CW>(e1, h1_before, cw0);
                 nh1 = r1;
                 cw_wr<CW>(fo1, cw_of_result<CW>(r1));
+                if constexpr (REC) lds_wr8(pk_f1, r1 >> 16);
                 dcount = dc_mid + (uint32_t)((int32_t)e1.y >> 24);
                 sh1 = shaped_of(e1.w);
                 grid_changed = true;
@@ -881,6 +924,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
                         env_reset4<MAXP, CW>(C, L, n_obj, horizon, s, col);
                         nh0 = nh1 = 0;
                     }
+                    if constexpr (REC) pack_planes();
                     dcount = DC0;
                     ep = zero4;        // the episode ends with this step: its returns restart from zero,
                     epsh.x = -rw.z; epsh.y = -rw.w;
@@ -998,6 +1042,39 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
         if (OUT) { rew_k += 8 * n; flg_k += 8 * n; }
     };
 
+    // REC: at the top of a step, its actions and the state it acts on — row pointers (wave-uniform) + lane offsets, the states
+    // with the streaming policy of the reward quads (written once, read by nobody in this launch)
+    uint8_t* rec_act = REC && ra.actions ? ra.actions + (int64_t)blk * BLOCK * 2 : nullptr;
+    uint4* rec_st = REC && ra.states ? reinterpret_cast<uint4*>(ra.states) + (int64_t)blk * BLOCK : nullptr;
+    auto record = [&](uint32_t a0, uint32_t a1) __attribute__((always_inline)) {
+        if (rec_act) {
+            asm volatile("global_store_short %0, %1, %2" : : "v"(tid * 2u), "v"(a0 | (a1 << 8)), "s"(rec_act) : "memory");
+            rec_act += 2 * n;
+        }
+        if (rec_st) {
+            auto put = [&](const uint4* row, uint4 v) __attribute__((always_inline)) {
+                const oc_u32x4 q = {v.x, v.y, v.z, v.w};
+                asm volatile("global_store_dwordx4 %0, %1, %2" OC_R4_QUAD_POLICY : : "v"(tid * 16u), "v"(q), "s"(row) : "memory");
+            };
+            uint32_t fix_cell[MAXP], fix_obj[MAXP];
+            put(rec_st, header_env4<MAXP, CW>(C, L, horizon, s, col, fix_cell, fix_obj));
+            for (int p = 0; p < n_obj; ++p) {
+                uint4 v = lds_rd128(pk + (uint32_t)p * (BLOCK * 16u));
+                if (s.exotic != 0u) {  // (rare) the wire format's object where a pot's cell word holds another: see header_env4
+#pragma unroll
+                    for (int k = 0; k < MAXP; ++k) {
+                        const uint32_t j = fix_cell[k] - 16u * (uint32_t)p, o = fix_obj[k] << (8u * (j & 3u));
+                        if (j < 16u) {
+                            v.x |= (j >> 2) == 0u ? o : 0u; v.y |= (j >> 2) == 1u ? o : 0u;
+                            v.z |= (j >> 2) == 2u ? o : 0u; v.w |= (j >> 2) == 3u ? o : 0u;
+                        }
+                    }
+                }
+                put(rec_st + (int64_t)(1 + p) * n, v);
+            }
+            rec_st += (int64_t)(1 + n_obj) * n;
+        }
+    };
 
     Phx4 w = {0, 0, 0, 0};  // the Philox block of the step being looked at
 #define OC_JA_AT(T, FIRST)                                                                                   \
@@ -1179,6 +1256,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
             const uint32_t fo0 = col + f0 * (BLOCK * CW), fo1 = col + f1 * (BLOCK * CW);
             const uint32_t off0 = lut_var + (a0 == OC_A_INTERACT ? 0u : (uint32_t)(LUT4_KEYS * 16));
             const uint32_t off1 = lut_var + ((two & (a1 == OC_A_INTERACT)) ? 0u : (uint32_t)(LUT4_KEYS * 16));
+            if constexpr (REC) {
+                record(a0, a1);
+                pk_f0 = pk + (f0 >> 4) * (BLOCK * 16u) + (f0 & 15u);
+                pk_f1 = pk + (f1 >> 4) * (BLOCK * 16u) + (f1 & 15u);
+            }
             const uint32_t c0 = cw_rd<CW>(fo0), c1 = cw_rd<CW>(fo1);
             const uint32_t cm0 = cw_rd<CW>(col + m0 * (BLOCK * CW)), cm1 = cw_rd<CW>(col + m1 * (BLOCK * CW));
             uint32_t pw[MAXP];

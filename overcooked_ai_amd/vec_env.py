@@ -305,7 +305,8 @@ class VecOvercookedEnv:
             raise ValueError("step_server: event tracking (track_events) is not served by the resident kernel")
         return StepServer(self, idle_ms, life_s)
 
-    def rollout_random(self, n_steps, rewards_out=None, flags_out=None, events_out=None, flags_tiled8=False):
+    def rollout_random(self, n_steps, rewards_out=None, flags_out=None, events_out=None, flags_tiled8=False,
+                       actions_out=None, states_out=None):
         """n_steps fused random-policy transitions in one launch (Philox actions, see include/oc_amd.h).  A launch
         costs ~16 us outside its step loop (tables, state load / store, dispatch): 12 % of a 400-step launch at 65 536
         envs, 3 % of a 2 000-step one — prefer few long launches.
@@ -314,7 +315,14 @@ class VecOvercookedEnv:
         flags_tiled8 (OC_OPT_FLAGS_TILED8): flags_out is [n_steps // 8, n_envs, 8] — byte [k // 8, e, k % 8] = step k of env e
         (`untile_flags` gives the [n_steps, n_envs] view's copy) —, which the kernel writes as full lines: worth ~6 % on the
         joint-table kernel (one cramped_room-like layout; whole 256-env workgroups up to 524 288 envs, else up to ~98 000; n_steps and the step counter multiples of 8;
-        ValueError via OC_EINVAL otherwise)."""
+        ValueError via OC_EINVAL otherwise).
+        Recording (oc_rollout_record): actions_out uint8 [n_steps, n_envs, 2] receives the actions drawn at every step and
+        states_out uint8 [n_steps, n_planes, n_envs, 16] the packed state each step acts on (slice k: before step k, after step
+        k - 1's restart; slice 0 is the state before the call, self.state the state after the last step).  Same stream, same
+        results as without them; `trajectories.recorded_trajectories` turns them into get_rollouts' dict.  Not combined with
+        events_out, flags_tiled8, event counters (track_events), lane_pair / predicate_interact or regen_layout (ValueError)."""
+        if actions_out is not None or states_out is not None:
+            return self._rollout_record(int(n_steps), rewards_out, flags_out, events_out, flags_tiled8, actions_out, states_out)
         if events_out is not None:
             self._check(events_out, torch.int64, int(n_steps) * self.n_envs, "events_out")
         if rewards_out is not None:
@@ -333,6 +341,33 @@ class VecOvercookedEnv:
         _lib.check(rc, "oc_rollout_random")
         self.t_global += int(n_steps)
         self._advance(int(n_steps))
+        return rewards_out, flags_out
+
+    def _rollout_record(self, K, rewards_out, flags_out, events_out, flags_tiled8, actions_out, states_out):
+        if events_out is not None or flags_tiled8 or self.event_counts is not None:
+            raise ValueError("recording (actions_out / states_out) does not log events and takes the plain flags layout")
+        if self.lane_pair or self.predicate_interact:
+            raise ValueError("recording (actions_out / states_out) runs the default kernel: lane_pair / predicate_interact are off")
+        if self.regen is not None:
+            raise ValueError("recording (actions_out / states_out) does not follow per-episode layout re-draws (regen_layout)")
+        if actions_out is not None:
+            self._check(actions_out, torch.uint8, K * self.n_envs * 2, "actions_out")
+        if states_out is not None:
+            self._check(states_out, torch.uint8, K * self.n_planes * self.n_envs * 16, "states_out")
+        if rewards_out is not None:
+            self._check(rewards_out, torch.float32, K * self.n_envs * 4, "rewards_out")
+        if flags_out is not None:
+            self._check(flags_out, torch.uint8, K * self.n_envs, "flags_out")
+        rc = self._launch(self.lib.oc_rollout_record, self._bref, self._state_ptr,
+                          actions_out.data_ptr() if actions_out is not None else None,
+                          states_out.data_ptr() if states_out is not None else None,
+                          rewards_out.data_ptr() if rewards_out is not None else None,
+                          flags_out.data_ptr() if flags_out is not None else None, self._ep_ptr, self.horizon,
+                          self.options, self.seed, self.env_offset, self.t_global, K,
+                          self._start_spec() if self.auto_reset else None)
+        _lib.check(rc, "oc_rollout_record")
+        self.t_global += K
+        self._advance(K)
         return rewards_out, flags_out
 
     @staticmethod
