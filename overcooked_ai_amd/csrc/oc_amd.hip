@@ -8,7 +8,7 @@
 //   step_table.hpp      the same transition with the table-driven interact: k_step3 (oc_step_many, grids above 64 cells)
 //   step_one.hpp        one transition per launch on the wire format itself: k_step1 (oc_step)
 //   step_lut4.hpp       the rollout path: key-byte cell words, 16-byte interact LUT, joint move table: k_rollout4 — compiled in
-//                       rollout4.hip (three units, see shared.hpp), launched from here through oc_detail::launch_rollout4_*
+//                       rollout4.hip (three units, see shared.hpp), chosen here (choose_rollout), launched through oc_detail::launch_rollout
 //   rollout_pair.hpp    two lanes per env: k_rollout_pair
 //   reset.hpp           get_standard_start_state mdp.py:1297, get_random_start_state_fn 1307: k_reset, k_reset_random
 //   encode.hpp          lossless_state_encoding mdp.py:2385-2561: k_encode, k_encode_uniform
@@ -243,6 +243,116 @@ __global__ __launch_bounds__(BLOCK) void k_output_stores_only_tiled8(float4* __r
     }
 }
 
+// Which kernel serves a call of oc_rollout_random (without OC_OPT_LANE_PAIR / OC_OPT_PREDICATE_INTERACT) or of oc_rollout_record
+// (record): the one place that reads the batch and the call for it.  rollout4.hip's units launch what it returns.
+struct RolloutChoice {
+    int r4 = -1;                    // a k_rollout4 instance: its index in R4Instances (shared.hpp); -1: k_rollout5, r5
+    oc_detail::R5Sel r5 = {};
+    int head = 0, bulk = 0;         // bulk > 0: the call runs as three calls of head, bulk (whole 8-step blocks) and the other steps
+    const char* refusal = nullptr;  // the call is refused (OC_EINVAL) with this message
+};
+
+template <class P>
+RolloutChoice pick() {
+    static_assert(oc_detail::R4Instances::id<P>() >= 0, "not in R4Instances");
+    return RolloutChoice{oc_detail::R4Instances::id<P>()};
+}
+
+RolloutChoice choose_rollout(const OcBatch* b, int n_obj, uint32_t options, int64_t t0, int n_steps, bool rewards, bool flags,
+                             const EvArgs& ea, bool record) {
+    using namespace oc_detail;
+    const bool uniform = b->n_layouts == 1, lds = b->n_layouts <= LDS_LAYOUT_MAX, small = b->max_pots >= 1 && b->max_pots <= 2;
+    if (record) return uniform && small ? pick<R4RecUniform>() : small ? pick<R4RecSmall>() : pick<R4RecGeneral>();
+    // Which family runs:
+    //   joint   one two-player, one-pot, new-dynamics layout with at most 6 free cells (cramped_room): the JOINT move table.
+    //           Launches of a few steps cannot amortise the ~10 us the workgroups spend building it: they move arithmetically
+    //   mode2   two players everywhere, at most two pots and 64 cells, one set of shaping rewards: per-env terrain with
+    //           the pose one step ahead on a floor mask (BASELINE configs[3] / [4], single layouts with more free cells)
+    //   else    arithmetic movement (MODE 0): any table, either dynamics, event logging
+    const bool two = (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0, events = ev_on(ea), tiled8 = (options & OC_OPT_FLAGS_TILED8) != 0;
+    const bool old_dyn = (b->batch_flags & OC_BATCH_NEW_DYNAMICS) == 0;  // some layout may use old dynamics
+    const bool out = rewards && flags, noout = !rewards && !flags;  // (noout: a rollout run for its final states / returns / event counters)
+#ifdef OC_AMD_TUNING
+    static const int forced_pipe = []() { const char* e = getenv("OC_ROLLOUT_PIPE"); return e ? atoi(e) : -1; }();  // tuning builds
+    static const bool no_mode2 = getenv("OC_ROLLOUT_NO_MODE2") != nullptr;
+    static const int forced_rounds = []() { const char* e = getenv("OC_DUO_ROUNDS"); return e ? atoi(e) : 0; }();
+#else
+    constexpr int forced_pipe = -1;
+    constexpr bool no_mode2 = false;
+    constexpr int forced_rounds = 0;
+#endif
+    // big batches (more than ~1.5 wavefronts per SIMD) hide latency with the other wavefronts: no one-step-ahead reads
+    const bool pipe = forced_pipe >= 0 ? forced_pipe != 0 : b->n_envs <= simd_count() * 64 * 3 / 2;
+    const bool joint = uniform && two && b->max_pots == 1 && b->max_free_cells >= 2 && b->max_free_cells <= 6u && out && !old_dyn &&
+                       n_steps >= 8 && !events;
+    const bool shaping_uniform = uniform || (b->batch_flags & OC_BATCH_UNIFORM_SHAPING) != 0;
+    // what the per-env-terrain kernels serve: two players everywhere, at most two pots, 64 cells (k_rollout5: 128 with the table
+    // in LDS), one set of shaping rewards, both output arrays (a one-pot joint-table layout is such a batch too)
+    // (one dynamics flag for the whole table — OC_BATCH_UNIFORM_SHAPING —: old dynamics is served by k_rollout5, not by MODE 2)
+    const int n_cells = b->width * b->height;
+    // (an event log: per-episode counters only — no per-step masks —, table in LDS, <= 64 cells, and the counters must fit the
+    //  CU's LDS beside the cell words: grids of up to 48 cells)
+    const bool ev_ok = !events || (ea.events == nullptr && lds && n_cells <= 64 && rollout5_lds_bytes(true, false, true, n_obj) <= (size_t)160 * 1024);
+    const bool terrain_shape = two && small && shaping_uniform && (n_cells <= 64 || (n_cells <= 128 && lds)) && ev_ok && !no_mode2;
+    const bool terrain_ok = terrain_shape && out;
+    const bool mode2 = !joint && terrain_ok && !old_dyn && n_cells <= 64 && !events;
+    // k_rollout5 (step_duo5.hpp): the step split between mover and interact wavefronts — whole workgroups of envs (every
+    // wavefront meets every barrier) and whole 8-step blocks; a workgroup's 127-154 KB of LDS leave room for one per CU.
+    // Bigger batches run these workgroups in ROUNDS, one per CU at a time — the next round's workgroups start as the first ones
+    // finish their launch's steps — which keeps the one-workgroup-per-CU rate where the one-wavefront instances fall behind
+    // (round 6, same box: the 5-layout mix at 65 536 / 131 072 / 262 144 envs 343 / 344 / 343 G env-steps/s; generated
+    // terrains, table read through L2, 131 072 envs: 332 G in two rounds against 315 G with one wavefront per env group).
+    // Beyond 8 rounds the one-wavefront instances win (round 5: 1 M cramped_room envs 356 G in 16 rounds against 384 G).
+    const int64_t per_round = (simd_count() / 4) * BLOCK;
+    const int64_t max_rounds = forced_rounds > 0 ? forced_rounds : 8;
+    const bool duo_batch = (terrain_ok || (terrain_shape && noout)) && !(options & OC_OPT_ONE_WAVEFRONT) && b->n_envs % BLOCK == 0 &&
+                           b->n_envs <= per_round * max_rounds;
+    // A long launch that is not made of whole 8-step blocks (t0 or n_steps not a multiple of 8 — e.g. every call after one
+    // rollout of 150 steps): the steps up to the next block boundary and the last < 8 steps go through the one-wavefront
+    // instances, the whole blocks between them through the mover / interact kernel — three launches on the stream, the same
+    // results (the state lives in d_state between them, every random draw is keyed by the global step)
+    if (duo_batch && !tiled8 && (((t0 & 7) != 0) || ((n_steps & 7) != 0))) {
+        const int head = (int)((8 - (t0 & 7)) & 7), bulk = head < n_steps ? ((n_steps - head) & ~7) : 0;
+        if (bulk >= 256) return RolloutChoice{-1, {}, head, bulk};
+    }
+    RolloutChoice ch;
+    if (duo_batch && n_steps >= 8 && (t0 & 7) == 0 && (n_steps & 7) == 0) {
+        // (event counters: tables in LDS, at most 64 cells; 65..128 cells: tables in LDS only)
+        const bool big = !events && n_cells > 64;
+        ch.r5 = R5Sel{events || big || lds, tiled8, old_dyn, big, events, noout};
+    } else if (events) {  // the general instances (arithmetic movement, either dynamics; mixed tables: the records are read through L2)
+        ch = uniform && small ? pick<R4EvUniform>() : small ? pick<R4EvSmall>() : pick<R4EvGeneral>();
+    } else if (joint) {  // (32-bit cell words and the faced cells read a step ahead where no two players can face the same cell)
+        const bool noconf = (b->batch_flags & OC_BATCH_NO_SHARED_FACES) != 0;
+        ch = !(pipe && n_cells <= 64 && noconf) ? pick<R4JointLean>() : tiled8 ? pick<R4JointTiled>() : pick<R4JointPipe>();
+    } else if (mode2) {
+        if (uniform) ch = b->max_pots == 1 && pipe ? pick<R4TerrainUniform1>() : pipe ? pick<R4TerrainUniform>() : pick<R4TerrainUniformLean>();
+        else if (lds) ch = !pipe ? pick<R4TerrainLdsLean>() : tiled8 ? pick<R4TerrainLdsTiled>() : pick<R4TerrainLds>();
+        else if (b->max_pots == 1)
+            ch = pipe ? (tiled8 ? pick<R4TerrainL2OnePotTiled>() : pick<R4TerrainL2OnePot>())
+                      : (tiled8 ? pick<R4TerrainL2OnePotLeanTiled>() : pick<R4TerrainL2OnePotLean>());
+        else ch = pipe ? pick<R4TerrainL2>() : pick<R4TerrainL2Lean>();
+    } else if (small && !old_dyn && out) {  // new dynamics, both output arrays: no per-step NULL / old-dynamics tests
+        ch = uniform ? pick<R4ArithUniformOut>() : lds ? pick<R4ArithLdsOut>() : pick<R4ArithL2Out>();
+    } else {  // (old dynamics / no output arrays: the records through L2 unless one layout; more than two pots: one general instance)
+        ch = uniform && small ? pick<R4ArithUniform>() : small ? pick<R4ArithSmall>() : pick<R4ArithGeneral>();
+    }
+    const bool ft8 = ch.r4 < 0 ? ch.r5.ft8 : R4Instances::FT8[ch.r4];  // (OC_OPT_FLAGS_TILED8: served where the choice writes tiled flags)
+    if (tiled8 && (!ft8 || b->n_envs >= ((int64_t)1 << 24)))
+        ch.refusal = "oc_rollout_random: OC_OPT_FLAGS_TILED8 is served by the pipelined joint-table kernel (one two-player, "
+                     "one-pot layout with <= 6 free cells and no shared faced cells, <= ~98 000 envs) and by the per-env-"
+                     "terrain kernels of mixed tables (<= 32 layouts: <= ~98 000 envs; one-pot tables beyond that), or by the mover / interact kernel "
+                     "(whole 256-env workgroups, <= 524 288 envs)";
+    return ch;
+}
+
+// launches c's instance through the rollout4.hip unit that compiles it
+void launch_rollout(const oc_detail::Rollout4Call& c) {
+    static void (*const unit[3])(const oc_detail::Rollout4Call&) = {oc_detail::launch_rollout<0>, oc_detail::launch_rollout<1>,
+                                                                     oc_detail::launch_rollout<2>};
+    unit[c.r4 < 0 ? 1 : oc_detail::R4Instances::PART[c.r4]](c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -363,7 +473,7 @@ int oc_rollout_random(const OcBatch* b, void* d_state, float* d_rewards, uint8_t
     if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_rollout_random: horizon must be in 1..65535");
     if (n_steps < 0 || n_steps > (1 << 30)) return fail(OC_EINVAL, "oc_rollout_random: n_steps must be in 0..2^30");
     const bool tiled8 = (options & OC_OPT_FLAGS_TILED8) != 0;
-    if (tiled8) {  // the launch-shape half of the option's conditions (the batch half follows the kernel choice below)
+    if (tiled8) {  // the launch-shape half of the option's conditions (the batch half: choose_rollout)
         if (!d_rewards || !d_flags || ((uintptr_t)d_flags & 7u) != 0)
             return fail(OC_EINVAL, "oc_rollout_random: OC_OPT_FLAGS_TILED8 needs d_rewards and an 8-byte aligned d_flags");
         if ((t0 & 7) != 0 || (n_steps & 7) != 0)
@@ -405,107 +515,36 @@ int oc_rollout_random(const OcBatch* b, void* d_state, float* d_rewards, uint8_t
                                env_offset, t0, n_steps);
         return check_launch("oc_rollout_random");
     }
-    if ((options & OC_OPT_PREDICATE_INTERACT) == 0) {
-        // k_rollout4 (step_lut4.hpp; its instances are compiled in rollout4.hip, three units).  Which family runs:
-        //   joint   one two-player, one-pot, new-dynamics layout with at most 6 free cells (cramped_room): the JOINT move table.
-        //           Launches of a few steps cannot amortise the ~10 us the workgroups spend building it: they move arithmetically
-        //   mode2   two players everywhere, at most two pots and 64 cells, one set of shaping rewards: per-env terrain with
-        //           the pose one step ahead on a floor mask (BASELINE configs[3] / [4], single layouts with more free cells)
-        //   else    arithmetic movement (MODE 0): any table, either dynamics, event logging
+    if ((options & OC_OPT_PREDICATE_INTERACT) == 0) {  // k_rollout4 / k_rollout5 (their instances are compiled in rollout4.hip)
+        const RolloutChoice ch = choose_rollout(b, n_obj, options, t0, n_steps, d_rewards != nullptr, d_flags != nullptr, ea, false);
+        if (ch.refusal) return fail(OC_EINVAL, ch.refusal);
+        if (ch.bulk > 0) {  // (see choose_rollout)
+            const int lens[3] = {ch.head, ch.bulk, n_steps - ch.head - ch.bulk};
+            int off = 0;
+            for (int part = 0; part < 3; ++part) {
+                const int len = lens[part];
+                if (len > 0 && !(oc_detail::g_describe && part != 1)) {
+                    OcStartSpec sk;
+                    if (start) { sk = *start; sk.epoch = start->epoch + (uint32_t)off; }  // a restart at step k draws from epoch + k
+                    const int rc = oc_rollout_random(b, d_state, d_rewards ? d_rewards + (int64_t)off * b->n_envs * 4 : nullptr,
+                                                     d_flags ? d_flags + (int64_t)off * b->n_envs : nullptr, d_ep_returns, horizon,
+                                                     options | (part == 1 ? 0u : (uint32_t)OC_OPT_ONE_WAVEFRONT), seed, env_offset, t0 + off, len,
+                                                     start ? &sk : nullptr, events, stream);
+                    if (rc) return rc;
+                }
+                off += len;
+            }
+            if (oc_detail::g_describe) {
+                const size_t used = strlen(oc_detail::g_describe);
+                snprintf(oc_detail::g_describe + used, 256 - used, "; %d + %d steps around the whole blocks: one-wavefront launches", lens[0], lens[2]);
+            }
+            return OC_OK;
+        }
         oc_detail::Rollout4Call c;
         c.b = b; c.n_obj = n_obj; c.d_state = d_state; c.d_rewards = d_rewards; c.d_flags = d_flags; c.d_ep_returns = d_ep_returns;
         c.horizon = horizon; c.options = options; c.seed = seed; c.env_offset = env_offset; c.t0 = t0; c.n_steps = n_steps;
-        c.sa = sa; c.ea = ea; c.stream = s;
-        const bool two = (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0;
-        c.uniform = uniform; c.lds = lds; c.small = small; c.events = ev_on(ea);
-        c.old_dyn = (b->batch_flags & OC_BATCH_NEW_DYNAMICS) == 0;  // some layout may use old dynamics
-        c.out = d_rewards != nullptr && d_flags != nullptr;
-        c.noout = d_rewards == nullptr && d_flags == nullptr;  // (a rollout run for its final states / returns / event counters)
-        // big batches (more than ~1.5 wavefronts per SIMD) hide latency with the other wavefronts: no one-step-ahead reads
-#ifdef OC_AMD_TUNING
-        static const int forced_pipe = []() { const char* e = getenv("OC_ROLLOUT_PIPE"); return e ? atoi(e) : -1; }();  // tuning builds
-        static const bool no_mode2 = getenv("OC_ROLLOUT_NO_MODE2") != nullptr;
-#else
-        constexpr int forced_pipe = -1;
-        constexpr bool no_mode2 = false;
-#endif
-        c.pipe = forced_pipe >= 0 ? forced_pipe != 0 : b->n_envs <= simd_count() * 64 * 3 / 2;
-        c.joint = uniform && two && b->max_pots == 1 && b->max_free_cells >= 2 && b->max_free_cells <= 6u && c.out &&
-                  !c.old_dyn && n_steps >= 8 && !c.events;
-        const bool shaping_uniform = uniform || (b->batch_flags & OC_BATCH_UNIFORM_SHAPING) != 0;
-        // what the per-env-terrain kernels serve: two players everywhere, at most two pots, 64 cells (k_rollout5: 128 with the table
-        // in LDS), one set of shaping rewards, both output arrays (a one-pot joint-table layout is such a batch too)
-        // (one dynamics flag for the whole table — OC_BATCH_UNIFORM_SHAPING —: old dynamics is served by k_rollout5, not by MODE 2)
-        const int n_cells = b->width * b->height;
-        // (an event log: per-episode counters only — no per-step masks —, table in LDS, <= 64 cells, and the counters must fit the
-        //  CU's LDS beside the cell words: grids of up to 48 cells)
-        const bool ev_ok = !c.events || (ea.events == nullptr && lds && n_cells <= 64 &&
-                                         oc_detail::rollout5_lds_bytes(true, false, true, n_obj) <= (size_t)160 * 1024);
-        const bool terrain_shape = two && small && shaping_uniform && (n_cells <= 64 || (n_cells <= 128 && lds)) && ev_ok && !no_mode2;
-        const bool terrain_ok = terrain_shape && c.out;
-        const bool mode2 = !c.joint && terrain_ok && !c.old_dyn && n_cells <= 64 && !c.events;
-        // k_rollout5 (step_duo5.hpp): the step split between mover and interact wavefronts — whole workgroups of envs (every
-        // wavefront meets every barrier) and whole 8-step blocks; a workgroup's 127-154 KB of LDS leave room for one per CU.
-        // Bigger batches run these workgroups in ROUNDS, one per CU at a time — the next round's workgroups start as the first ones
-        // finish their launch's steps — which keeps the one-workgroup-per-CU rate where the one-wavefront instances fall behind
-        // (round 6, same box: the 5-layout mix at 65 536 / 131 072 / 262 144 envs 343 / 344 / 343 G env-steps/s; generated
-        // terrains, table read through L2, 131 072 envs: 332 G in two rounds against 315 G with one wavefront per env group).
-        // Beyond 8 rounds the one-wavefront instances win (round 5: 1 M cramped_room envs 356 G in 16 rounds against 384 G).
-#ifdef OC_AMD_TUNING
-        static const int forced_rounds = []() { const char* e = getenv("OC_DUO_ROUNDS"); return e ? atoi(e) : 0; }();  // tuning builds
-#else
-        constexpr int forced_rounds = 0;
-#endif
-        const int64_t per_round = (simd_count() / 4) * BLOCK;
-        const int64_t max_rounds = forced_rounds > 0 ? forced_rounds : 8;
-        const bool duo_batch = (terrain_ok || (terrain_shape && c.noout)) && !(options & OC_OPT_ONE_WAVEFRONT) && b->n_envs % BLOCK == 0 &&
-                               b->n_envs <= per_round * max_rounds;
-        // A long launch that is not made of whole 8-step blocks (t0 or n_steps not a multiple of 8 — e.g. every call after one
-        // rollout of 150 steps): the steps up to the next block boundary and the last < 8 steps go through the one-wavefront
-        // instances, the whole blocks between them through the mover / interact kernel — three launches on the stream, the same
-        // results (the state lives in d_state between them, every random draw is keyed by the global step)
-        if (duo_batch && !tiled8 && (((t0 & 7) != 0) || ((n_steps & 7) != 0))) {
-            const int head = (int)((8 - (t0 & 7)) & 7);
-            const int bulk = head < n_steps ? ((n_steps - head) & ~7) : 0;
-            if (bulk >= 256) {
-                const int lens[3] = {head, bulk, n_steps - head - bulk};
-                int off = 0;
-                for (int part = 0; part < 3; ++part) {
-                    const int len = lens[part];
-                    if (len > 0 && !(oc_detail::g_describe && part != 1)) {
-                        OcStartSpec sk;
-                        if (start) { sk = *start; sk.epoch = start->epoch + (uint32_t)off; }  // a restart at step k draws from epoch + k
-                        const int rc = oc_rollout_random(b, d_state, d_rewards ? d_rewards + (int64_t)off * b->n_envs * 4 : nullptr,
-                                                         d_flags ? d_flags + (int64_t)off * b->n_envs : nullptr, d_ep_returns, horizon,
-                                                         options | (part == 1 ? 0u : (uint32_t)OC_OPT_ONE_WAVEFRONT), seed, env_offset, t0 + off, len,
-                                                         start ? &sk : nullptr, events, stream);
-                        if (rc) return rc;
-                    }
-                    off += len;
-                }
-                if (oc_detail::g_describe) {
-                    const size_t used = strlen(oc_detail::g_describe);
-                    snprintf(oc_detail::g_describe + used, 256 - used, "; %d + %d steps around the whole blocks: one-wavefront launches", lens[0], lens[2]);
-                }
-                return OC_OK;
-            }
-        }
-        c.duo = duo_batch && n_steps >= 8 && (t0 & 7) == 0 && (n_steps & 7) == 0;
-        c.tiled8 = tiled8;
-        if (tiled8) {  // which instances write the tiled flags array: the pipelined joint-table one, the per-env-terrain ones of
-                       // mixed tables in LDS (pipelined) and of one-pot tables in HBM
-            const bool by_joint = c.joint && c.pipe && b->width * b->height <= 64 && (b->batch_flags & OC_BATCH_NO_SHARED_FACES) != 0;
-            const bool by_mode2 = mode2 && !uniform && ((lds && c.pipe) || (!lds && b->max_pots == 1));
-            if (!(c.duo || by_joint || by_mode2) || b->n_envs >= ((int64_t)1 << 24))
-                return fail(OC_EINVAL, "oc_rollout_random: OC_OPT_FLAGS_TILED8 is served by the pipelined joint-table kernel (one two-player, "
-                                       "one-pot layout with <= 6 free cells and no shared faced cells, <= ~98 000 envs) and by the per-env-"
-                                       "terrain kernels of mixed tables (<= 32 layouts: <= ~98 000 envs; one-pot tables beyond that), or by the mover / interact kernel "
-                                       "(whole 256-env workgroups, <= 524 288 envs)");
-        }
-        if (c.duo) oc_detail::launch_rollout4_mode2(c);
-        else if (c.joint || c.events) oc_detail::launch_rollout4_joint_events(c);
-        else if (mode2) oc_detail::launch_rollout4_mode2(c);
-        else oc_detail::launch_rollout4_mode0(c);
+        c.sa = sa; c.ea = ea; c.stream = s; c.r4 = ch.r4; c.r5 = ch.r5;
+        launch_rollout(c);
         if (oc_detail::g_describe) return OC_OK;  // (oc_rollout_plan: nothing was launched)
         return check_launch("oc_rollout_random");
     }
@@ -546,15 +585,14 @@ int oc_rollout_record(const OcBatch* b, void* d_state, uint8_t* d_actions_out, v
     if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_rollout_record: horizon must be in 1..65535");
     if (n_steps < 0 || n_steps > (1 << 30)) return fail(OC_EINVAL, "oc_rollout_record: n_steps must be in 0..2^30");
     if (b->n_envs == 0 || n_steps == 0) return OC_OK;
-    // the general one-wavefront instances of k_rollout4 (arithmetic movement, either dynamics, optional reward / flag rows) with REC
+    const EvArgs ea = ev_args(nullptr, nullptr);
+    const RolloutChoice ch = choose_rollout(b, n_obj, options, t0, n_steps, d_rewards != nullptr, d_flags != nullptr, ea, true);
     oc_detail::Rollout4Call c;
     c.b = b; c.n_obj = n_obj; c.d_state = d_state; c.d_rewards = d_rewards; c.d_flags = d_flags; c.d_ep_returns = d_ep_returns;
     c.horizon = horizon; c.options = options & OC_OPT_AUTO_RESET; c.seed = seed; c.env_offset = env_offset; c.t0 = t0;
-    c.n_steps = n_steps; c.sa = sa; c.ea = ev_args(nullptr, nullptr); c.stream = (hipStream_t)stream;
-    c.uniform = b->n_layouts == 1; c.lds = b->n_layouts <= LDS_LAYOUT_MAX; c.small = b->max_pots >= 1 && b->max_pots <= 2;
-    c.joint = false; c.old_dyn = true; c.out = false; c.pipe = true; c.events = false; c.tiled8 = false; c.noout = false; c.duo = false;
+    c.n_steps = n_steps; c.sa = sa; c.ea = ea; c.stream = (hipStream_t)stream; c.r4 = ch.r4; c.r5 = ch.r5;
     c.ra = oc_detail::RecArgs{d_actions_out, d_states_out};
-    oc_detail::launch_rollout4_record(c);
+    launch_rollout(c);
     return check_launch("oc_rollout_record");
 }
 

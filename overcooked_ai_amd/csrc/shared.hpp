@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/oc_amd.h"
 
 #define OC_HIDDEN __attribute__((visibility("hidden")))
@@ -48,7 +50,141 @@ struct RecArgs {
     void* states;      // [n_steps][n_planes][n_envs][16] wire-format states, 16-byte aligned, or NULL
 };
 
-// One oc_rollout_random call through k_rollout4, as oc_amd.hip hands it to the unit that holds the instance.
+// ---- The instances of k_rollout4 (step_lut4.hpp).  Each is a traits struct: R4Base's members, overridden by name.  The base
+//      is the instance that serves any table (arithmetic movement, up to 8 pot slots, records read through L2, either dynamics).
+template <class D>  // D: the instance (its choices are read by the derived values below)
+struct R4Base {
+    static constexpr bool UNIFORM = false;  // one layout: its tables and cook times are staged once per workgroup
+    static constexpr int MAXP = 8;          // pot slots per env
+    static constexpr bool LAY_LDS = false;  // the layout records are staged in LDS (<= LDS_LAYOUT_MAX layouts)
+    static constexpr int MODE = 0;          // 0 arithmetic movement, 1 JOINT move table, 2 per-env terrain, pose one step ahead
+    static constexpr bool OUT = false;      // both output arrays are present: no per-step NULL tests
+    static constexpr bool OLD = true;       // some layout may use old dynamics
+    static constexpr bool EV = false;       // event_infos are logged (EvArgs)
+    static constexpr bool PIPE = true;      // MODE 1 / 2: the next step's faced cells are read one step ahead
+    static constexpr bool RU = false;       // one set of shaping rewards and one dynamics flag for the whole table
+    static constexpr int CW = 2;            // bytes of a cell word
+    static constexpr bool NOCONF = false;   // the two players can never face the same cell (OC_BATCH_NO_SHARED_FACES)
+    static constexpr bool FT8 = false;      // the flags array is tiled by 8 steps (OC_OPT_FLAGS_TILED8)
+    static constexpr bool REC = false;      // every step's pre-step state and actions are stored too (oc_rollout_record)
+    // derived
+    static constexpr bool RUX = D::UNIFORM || D::RU;  // one LUT variant, patched with the reward floats
+    static constexpr int NF = D::MODE == 1 ? 6 : 0;   // free cells the move table has room for
+    static constexpr int PART = D::EV || D::MODE == 1 ? 0 : D::MODE == 2 ? 1 : 2;  // the rollout4.hip unit (OC_R4_PART) that compiles it
+    static constexpr bool legal() {
+        static_assert(D::CW == 2 || D::CW == 4, "cell words are u16 or u32");
+        static_assert(!D::REC || (D::MODE == 0 && D::CW == 2 && !D::EV && !D::FT8), "recording is served by the arithmetic-movement instances");
+        static_assert(!D::FT8 || ((D::MODE == 1 || D::MODE == 2) && D::OUT && !D::EV),
+                      "the tiled flags array is served by joint-table and per-env-terrain instances");
+        return true;
+    }
+};
+
+// Every instance, with the batches choose_rollout (oc_amd.hip) gives it.  "Pipelined": <= ~1.5 wavefronts per SIMD (PIPE with
+// 32-bit cell words); "lean": bigger batches.
+// -- event logging (arithmetic movement, either dynamics)
+struct R4EvUniform : R4Base<R4EvUniform> {  // one layout, <= 2 pots
+    static constexpr bool UNIFORM = true, LAY_LDS = true, EV = true; static constexpr int MAXP = 2;
+};
+struct R4EvSmall : R4Base<R4EvSmall> { static constexpr bool EV = true; static constexpr int MAXP = 2; };  // mixed tables, <= 2 pots
+struct R4EvGeneral : R4Base<R4EvGeneral> { static constexpr bool EV = true; };  // more than 2 pots
+// -- JOINT move table: one two-player, one-pot, new-dynamics layout with 2..6 free cells, launches of >= 8 steps ("pipelined": also
+//    <= 64 cells and no shared faced cells)
+struct R4JointTiled : R4Base<R4JointTiled> {  // pipelined, tiled flags
+    static constexpr bool UNIFORM = true, LAY_LDS = true, OUT = true, OLD = false, NOCONF = true, FT8 = true;
+    static constexpr int MAXP = 1, MODE = 1, CW = 4;
+};
+struct R4JointPipe : R4Base<R4JointPipe> {  // pipelined
+    static constexpr bool UNIFORM = true, LAY_LDS = true, OUT = true, OLD = false, NOCONF = true;
+    static constexpr int MAXP = 1, MODE = 1, CW = 4;
+};
+struct R4JointLean : R4Base<R4JointLean> {  // big batches, shared faced cells or more than 64 cells
+    static constexpr bool UNIFORM = true, LAY_LDS = true, OUT = true, OLD = false, PIPE = false; static constexpr int MAXP = 1, MODE = 1;
+};
+// -- MODE 2, per-env terrain: two players everywhere, <= 2 pots, <= 64 cells, one set of shaping rewards, new dynamics, both output
+//    arrays, no event log (what k_rollout5 does not take of these: ragged batches, above 8 rounds, < 8 steps, ONE_WAVEFRONT)
+struct R4TerrainUniform1 : R4Base<R4TerrainUniform1> {  // one one-pot layout, pipelined
+    static constexpr bool UNIFORM = true, LAY_LDS = true, OUT = true, OLD = false; static constexpr int MAXP = 1, MODE = 2, CW = 4;
+};
+struct R4TerrainUniform : R4Base<R4TerrainUniform> {  // one layout, pipelined
+    static constexpr bool UNIFORM = true, LAY_LDS = true, OUT = true, OLD = false; static constexpr int MAXP = 2, MODE = 2, CW = 4;
+};
+struct R4TerrainUniformLean : R4Base<R4TerrainUniformLean> {  // one layout, lean
+    static constexpr bool UNIFORM = true, LAY_LDS = true, OUT = true, OLD = false, PIPE = false; static constexpr int MAXP = 2, MODE = 2;
+};
+struct R4TerrainLdsTiled : R4Base<R4TerrainLdsTiled> {  // table in LDS, pipelined, tiled flags
+    static constexpr bool LAY_LDS = true, OUT = true, OLD = false, RU = true, FT8 = true; static constexpr int MAXP = 2, MODE = 2, CW = 4;
+};
+struct R4TerrainLds : R4Base<R4TerrainLds> {  // table in LDS, pipelined
+    static constexpr bool LAY_LDS = true, OUT = true, OLD = false, RU = true; static constexpr int MAXP = 2, MODE = 2, CW = 4;
+};
+struct R4TerrainLdsLean : R4Base<R4TerrainLdsLean> {  // table in LDS, lean
+    static constexpr bool LAY_LDS = true, OUT = true, OLD = false, RU = true, PIPE = false; static constexpr int MAXP = 2, MODE = 2;
+};
+struct R4TerrainL2OnePotTiled : R4Base<R4TerrainL2OnePotTiled> {  // one-pot table through L2, pipelined, tiled flags
+    static constexpr bool OUT = true, OLD = false, RU = true, FT8 = true; static constexpr int MAXP = 1, MODE = 2, CW = 4;
+};
+struct R4TerrainL2OnePotLeanTiled : R4Base<R4TerrainL2OnePotLeanTiled> {  // one-pot table through L2, lean, tiled flags
+    static constexpr bool OUT = true, OLD = false, RU = true, PIPE = false, FT8 = true; static constexpr int MAXP = 1, MODE = 2;
+};
+struct R4TerrainL2OnePot : R4Base<R4TerrainL2OnePot> {  // one-pot table through L2, pipelined
+    static constexpr bool OUT = true, OLD = false, RU = true; static constexpr int MAXP = 1, MODE = 2, CW = 4;
+};
+struct R4TerrainL2OnePotLean : R4Base<R4TerrainL2OnePotLean> {  // one-pot table through L2, lean
+    static constexpr bool OUT = true, OLD = false, RU = true, PIPE = false; static constexpr int MAXP = 1, MODE = 2;
+};
+struct R4TerrainL2 : R4Base<R4TerrainL2> {  // two-pot table through L2, pipelined
+    static constexpr bool OUT = true, OLD = false, RU = true; static constexpr int MAXP = 2, MODE = 2, CW = 4;
+};
+struct R4TerrainL2Lean : R4Base<R4TerrainL2Lean> {  // two-pot table through L2, lean
+    static constexpr bool OUT = true, OLD = false, RU = true, PIPE = false; static constexpr int MAXP = 2, MODE = 2;
+};
+// -- arithmetic movement (MODE 0): every other batch
+struct R4ArithUniformOut : R4Base<R4ArithUniformOut> {  // one new-dynamics layout, <= 2 pots, both output arrays
+    static constexpr bool UNIFORM = true, LAY_LDS = true, OUT = true, OLD = false; static constexpr int MAXP = 2;
+};
+struct R4ArithLdsOut : R4Base<R4ArithLdsOut> {  // new-dynamics table in LDS, <= 2 pots, both output arrays
+    static constexpr bool LAY_LDS = true, OUT = true, OLD = false; static constexpr int MAXP = 2;
+};
+struct R4ArithL2Out : R4Base<R4ArithL2Out> {  // new-dynamics table through L2, <= 2 pots, both output arrays
+    static constexpr bool OUT = true, OLD = false; static constexpr int MAXP = 2;
+};
+struct R4ArithUniform : R4Base<R4ArithUniform> {  // other single layouts with <= 2 pots
+    static constexpr bool UNIFORM = true, LAY_LDS = true; static constexpr int MAXP = 2;
+};
+struct R4ArithSmall : R4Base<R4ArithSmall> { static constexpr int MAXP = 2; };  // other tables with <= 2 pots (records through L2)
+struct R4ArithGeneral : R4Base<R4ArithGeneral> {};  // more than 2 pots
+// -- oc_rollout_record: the three general arithmetic-movement instances with REC
+struct R4RecUniform : R4Base<R4RecUniform> {  // one layout, <= 2 pots
+    static constexpr bool UNIFORM = true, LAY_LDS = true, REC = true; static constexpr int MAXP = 2;
+};
+struct R4RecSmall : R4Base<R4RecSmall> { static constexpr bool REC = true; static constexpr int MAXP = 2; };  // mixed tables, <= 2 pots
+struct R4RecGeneral : R4Base<R4RecGeneral> { static constexpr bool REC = true; };  // more than 2 pots
+
+template <class... P>
+struct R4List {
+    static_assert((P::legal() && ...), "");
+    static constexpr int PART[] = {P::PART...};
+    static constexpr bool FT8[] = {P::FT8...};
+    template <class Q> static constexpr int id() {  // index of instance Q, -1 when it is not listed
+        constexpr bool same[] = {std::is_same<Q, P>::value...};
+        for (int i = 0; i < (int)sizeof...(P); ++i)
+            if (same[i]) return i;
+        return -1;
+    }
+};
+using R4Instances = R4List<R4EvUniform, R4EvSmall, R4EvGeneral, R4JointTiled, R4JointPipe, R4JointLean, R4TerrainUniform1,
+                           R4TerrainUniform, R4TerrainUniformLean, R4TerrainLdsTiled, R4TerrainLds, R4TerrainLdsLean,
+                           R4TerrainL2OnePotTiled, R4TerrainL2OnePotLeanTiled, R4TerrainL2OnePot, R4TerrainL2OnePotLean, R4TerrainL2,
+                           R4TerrainL2Lean, R4ArithUniformOut, R4ArithUniform, R4ArithLdsOut, R4ArithL2Out, R4ArithSmall, R4ArithGeneral,
+                           R4RecUniform, R4RecSmall, R4RecGeneral>;
+
+// k_rollout5<LAY_LDS, FT8, OLD, BIG, EV, NOOUT> (step_duo5.hpp): the mover / interact kernel, chosen by its own six flags
+struct R5Sel {
+    bool lay_lds, ft8, old, big, ev, noout;
+};
+
+// One oc_rollout_random / oc_rollout_record launch, as oc_amd.hip hands it to the unit that compiles the chosen instance.
 struct Rollout4Call {
     const OcBatch* b;
     int n_obj;
@@ -64,17 +200,12 @@ struct Rollout4Call {
     StartArgs sa;
     EvArgs ea;
     hipStream_t stream;
-    // what oc_rollout_random derived from the batch and the call
-    bool uniform, lds, small, joint, old_dyn, out, pipe, events;
-    bool tiled8;  // OC_OPT_FLAGS_TILED8: d_flags is [n_steps / 8][n_envs][8]
-    bool noout;   // neither d_rewards nor d_flags: k_rollout5 runs its store-free instances
-    bool duo;     // MODE 3: the per-env-terrain step split between mover and interact wavefronts (step_lut4.hpp)
-    RecArgs ra = {nullptr, nullptr};  // oc_rollout_record: the recording outputs (launch_rollout4_record)
+    int r4;     // the chosen k_rollout4 instance: its index in R4Instances; -1: k_rollout5, r5
+    R5Sel r5;
+    RecArgs ra = {nullptr, nullptr};  // oc_rollout_record: the recording outputs
 };
-OC_HIDDEN void launch_rollout4_joint_events(const Rollout4Call& c);  // rollout4.hip, OC_R4_PART 0
-OC_HIDDEN void launch_rollout4_mode2(const Rollout4Call& c);         // rollout4.hip, OC_R4_PART 1
-OC_HIDDEN void launch_rollout4_mode0(const Rollout4Call& c);         // rollout4.hip, OC_R4_PART 2
-OC_HIDDEN void launch_rollout4_record(const Rollout4Call& c);        // rollout4.hip, OC_R4_PART 2 (oc_rollout_record)
+// rollout4.hip, compiled with -DOC_R4_PART=UNIT (one explicit instantiation per unit): launches c's instance, which that unit compiles
+template <int UNIT> OC_HIDDEN void launch_rollout(const Rollout4Call& c);
 OC_HIDDEN size_t rollout5_lds_bytes(bool lay_lds, bool big, bool ev, int n_obj);  // rollout4.hip, OC_R4_PART 1
 
 }  // namespace oc_detail

@@ -436,19 +436,19 @@ __device__ __forceinline__ uint32_t joint_action_of(uint32_t w0, uint32_t w1, ui
 // With u16 table entries (CW = 2) the move table comes first, so that row addresses and the LUT addresses in ACT fit 16 bits;
 // with u32 entries (CW = 4, an 85 KB move table) the small tables come first instead, so that THEIR addresses stay below
 // 64 KiB and fold into the 16-bit offset field of the DS instructions.
-template <bool UNIFORM, bool LAY_LDS, int MODE, int NF, bool ONE_LUT = UNIFORM, int CW = 2>
+template <class P>  // a k_rollout4 instance (R4Base, shared.hpp)
 struct Lds4 {
-    static constexpr int MVJ_CAP = MODE == 1 ? ((16 * NF * NF * Mvj<CW>::ROW_BYTES + 15) & ~15) : 0;
-    static constexpr bool TABLE_FIRST = CW == 2;
+    static constexpr int MVJ_CAP = P::MODE == 1 ? ((16 * P::NF * P::NF * Mvj<P::CW>::ROW_BYTES + 15) & ~15) : 0;
+    static constexpr bool TABLE_FIRST = P::CW == 2;
     // MODE 1: [player][40] u16 / u32 LUT addresses
-    static constexpr int ACT = TABLE_FIRST ? MVJ_CAP : 0, ACT_P1 = 40 * CW, ACT_BYTES = MODE == 1 ? 2 * ACT_P1 : 0;
-    static constexpr int LUT = ACT + ACT_BYTES, LUT_BYTES = ONE_LUT ? LUT4_BYTES : 2 * LUT4_BYTES;
-    static constexpr int LAY = LUT + LUT_BYTES, LAY_BYTES = LAY_LDS ? (UNIFORM ? 256 : LDS_LAYOUT_MAX * 256) : 16;
-    static constexpr int FL = LAY + LAY_BYTES, FI = FL + 16, CT = FI + (MODE == 1 ? OC_MAX_CELLS : 0);
+    static constexpr int ACT = TABLE_FIRST ? MVJ_CAP : 0, ACT_P1 = 40 * P::CW, ACT_BYTES = P::MODE == 1 ? 2 * ACT_P1 : 0;
+    static constexpr int LUT = ACT + ACT_BYTES, LUT_BYTES = P::RUX ? LUT4_BYTES : 2 * LUT4_BYTES;
+    static constexpr int LAY = LUT + LUT_BYTES, LAY_BYTES = P::LAY_LDS ? (P::UNIFORM ? 256 : LDS_LAYOUT_MAX * 256) : 16;
+    static constexpr int FL = LAY + LAY_BYTES, FI = FL + 16, CT = FI + (P::MODE == 1 ? OC_MAX_CELLS : 0);
     static constexpr int MVJ = TABLE_FIRST ? 0 : CT + 32;  // LDS address of the move table
     static constexpr int CELLS = TABLE_FIRST ? CT + 32 : MVJ + MVJ_CAP;
-    static_assert(CW == 4 || MVJ_CAP + ACT_BYTES + LUT4_KEYS * 16 < 65536, "row / LUT addresses are u16 in the tables");
-    static_assert(CW == 2 || CT + 32 < 65536, "the small tables' addresses must fit the DS offset field");
+    static_assert(P::CW == 4 || MVJ_CAP + ACT_BYTES + LUT4_KEYS * 16 < 65536, "row / LUT addresses are u16 in the tables");
+    static_assert(P::CW == 2 || CT + 32 < 65536, "the small tables' addresses must fit the DS offset field");
 };
 
 // flags[k][e] for the 64 envs of this wavefront: SGPR row pointer + lane offset, no 64-bit address arithmetic
@@ -505,8 +505,7 @@ __device__ __forceinline__ void env_reset4_draw(const LayC& C, const Lay L, int 
 // PIPE (MODE 1, 2): the next step's faced cells are read one step ahead.  That hides the read behind the tail of the step
 //   when a SIMD holds one wavefront (65 536 envs); with two or more wavefronts per SIMD the extra LDS traffic costs
 //   more than the latency it hides (131 072 cramped_room envs: 0.48 vs 0.65 us per batched step), so big batches turn it off
-template <bool UNIFORM, int MAXP, bool LAY_LDS, int MODE, bool OUT, bool OLD, int NF = JOINT_MAX_FLOOR, bool EV = false,
-          bool PIPE = true, bool RU = false, int CW = 2, bool NOCONF = false, bool FT8 = false, bool REC = false>
+template <class P>  // the instance: a traits struct of shared.hpp (R4Base: what each member means, R4Instances: the list)
 #ifndef OC_R4_WAVES_MAX
 #define OC_R4_WAVES_MAX 4
 #endif
@@ -518,10 +517,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
                                                     int64_t env_offset, int64_t t0, int n_steps, StartArgs sa, EvArgs ea,
                                                     RecArgs ra) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn4[];
-    constexpr bool RUX = UNIFORM || RU;  // one LUT variant, patched with the reward floats
-    using M = Lds4<UNIFORM, LAY_LDS, MODE, NF, RUX, CW>;
-    static_assert(CW == 2 || CW == 4, "cell words are u16 or u32");
-    static_assert(!REC || (MODE == 0 && CW == 2 && !EV && !FT8), "recording is served by the arithmetic-movement instances");
+    constexpr bool UNIFORM = P::UNIFORM, LAY_LDS = P::LAY_LDS, OUT = P::OUT, OLD = P::OLD, EV = P::EV, PIPE = P::PIPE, NOCONF = P::NOCONF;
+    constexpr bool FT8 = P::FT8, REC = P::REC, RUX = P::RUX;
+    constexpr int MAXP = P::MAXP, MODE = P::MODE, CW = P::CW;
+    using M = Lds4<P>;
     if ((uint32_t)(uintptr_t)(OC_LDS uint8_t*)s_dyn4 != 0u) __builtin_trap();  // folds away: the region starts at address 0
     uint4* const s_lay = reinterpret_cast<uint4*>(s_dyn4 + M::LAY);
     uint4* const s_lut = reinterpret_cast<uint4*>(s_dyn4 + M::LUT);
@@ -621,7 +620,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
     const uint32_t g_lo = (uint32_t)g, g_hi = (uint32_t)(g >> 32);
     float4* rew_k = rewards ? rewards + (int64_t)blk * BLOCK : nullptr;  // wave-uniform row pointers
     const uint32_t wave_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid & ~63u));  // first lane of this wavefront
-    static_assert(!FT8 || ((MODE == 1 || MODE == 2) && OUT && !EV), "the tiled flags array is served by joint-table and per-env-terrain instances");
     uint8_t* flg_k = flags ? flags + ((int64_t)blk * BLOCK + wave_base) * (FT8 ? 8 : 1) : nullptr;  // (FT8: the tile row of 8 steps)
     uint32_t flt_lo = 0, flt_hi = 0;  // FT8: the flag bytes of the block's steps 0..3 / 4..7
     const uint32_t lane = tid & 63u;

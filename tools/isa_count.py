@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Static instruction counts of a kernel's hot loop in a built library (no GPU needed).
 
-    python tools/isa_count.py [path/to/liboc_amd.so] 'k_rollout4<true, 1, true, 1, true, false, 6, false, true, false, 4, true>'
+    python tools/isa_count.py [path/to/liboc_amd.so] 'k_rollout4<oc_detail::R4JointPipe>'
+
+(k_rollout4's instances are the traits structs of overcooked_ai_amd/csrc/shared.hpp, R4Instances.)
 
 Extracts the gfx950 code object (llvm-objcopy + clang-offload-bundler), disassembles it, finds the kernel whose demangled
 name contains the given text, and prints — for every loop (backward branch) of at least 300 instructions — the number of
