@@ -322,6 +322,37 @@ int oc_rollout_record(const OcBatch* batch, void* d_state, uint8_t* d_actions_ou
                       int64_t env_offset, int64_t t0, int n_steps, const OcStartSpec* start, void* stream);
 
 /*
+ * Where oc_rollout_record_ex records each step k of the call.
+ *   d_actions     [n_steps][n_envs][2] u8, as d_actions_out of oc_rollout_record; 2-byte aligned, or NULL
+ *   d_states      [n_steps][n_planes][n_envs][16], as d_states_out of oc_rollout_record; 16-byte aligned, or NULL
+ *   d_layout_ids  [n_steps][n_envs] u16: the layout id of the state in d_states slice k — the env's id after step k - 1's restart
+ *                 and layout re-draw (slice 0: OcBatch.d_layout_id on entry; 0 for a one-layout table); 2-byte aligned, or NULL
+ */
+typedef struct OcRecordSink {
+    uint8_t* d_actions;
+    void* d_states;
+    uint16_t* d_layout_ids;
+} OcRecordSink;
+
+/*
+ * oc_rollout_record_ex — oc_rollout_record with the event log and per-episode layout re-draws: the complete trajectory of
+ * OvercookedEnv.get_rollouts (env.py:485-580) with each episode's game_stats (env.py:382-401: the event lists of ep_game_stats
+ * come from the per-step masks or the counters of `events`), on layouts re-drawn at every restart (start->regen_count > 0:
+ * OvercookedEnv.reset(regen_mdp=True), env.py:288-302), each step labelled with its layout in rec->d_layout_ids.
+ * With the same arguments, start spec and event sink it gives the results of oc_rollout_random: d_state, d_rewards, d_flags,
+ * d_ep_returns, OcBatch.d_layout_id after re-draws, the event masks and counters, the Philox stream and the start-state epochs.
+ * recorded bytes per env-step with every array: 16 per plane + 2 (actions) + 2 (layout ids) + 8 (event mask) + 17 (rewards,
+ * flags) — 77 on grids of 17..32 cells (cramped_room), 93 on 33..48 (asymmetric_advantages, 9 x 5 tables).
+ * Runs the one-wavefront arithmetic-movement kernel (k_rollout4, MODE 0) with recording stores, and with the event log when
+ * `events` names masks or counters.  options: OC_OPT_AUTO_RESET; OC_OPT_ONE_WAVEFRONT is accepted and has no effect.  OC_EINVAL,
+ * before any device call: any other option bit, a table without OC_BATCH_TWO_PLAYERS, rec NULL or all three of its arrays NULL,
+ * a misaligned array, and the start-spec errors of oc_rollout_record (but for regen_count, which is accepted).
+ */
+int oc_rollout_record_ex(const OcBatch* batch, void* d_state, const OcRecordSink* rec, float* d_rewards, uint8_t* d_flags,
+                         float* d_ep_returns, int horizon, uint32_t options, uint64_t seed, int64_t env_offset, int64_t t0,
+                         int n_steps, const OcStartSpec* start, const OcEventSink* events, void* stream);
+
+/*
  * oc_encode_lossless — the 26-layer observation of both players.
  * Replaces OvercookedGridworld.lossless_state_encoding (mdp.py:2385-2561) as called through
  * OvercookedEnv.lossless_state_encoding_mdp (env.py:276-280).

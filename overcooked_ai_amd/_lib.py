@@ -21,7 +21,7 @@ BATCH_NO_SHARED_FACES = 0x8
 OBS_U8, OBS_F32 = 0, 1
 
 EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes", "oc_batch_hints", "oc_step", "oc_step_many",
-           "oc_rollout_random", "oc_rollout_record", "oc_encode_lossless", "oc_step_encode", "oc_rollout_encode", "oc_featurize", "oc_potential",
+           "oc_rollout_random", "oc_rollout_record", "oc_rollout_record_ex", "oc_encode_lossless", "oc_step_encode", "oc_rollout_encode", "oc_featurize", "oc_potential",
            "oc_phi_table_size", "oc_reset", "oc_reset_random", "oc_regen_layouts", "oc_shape_rewards", "oc_multi_agent_step",
            "oc_mailbox_open", "oc_mailbox_buffer", "oc_mailbox_step", "oc_mailbox_close", "oc_output_stores_only", "oc_rollout_plan",
            "oc_step_server_open", "oc_step_server_requests", "oc_step_server_responses", "oc_step_server_resume",
@@ -57,6 +57,10 @@ class OcStartSpec(ctypes.Structure):
 
 class OcEventSink(ctypes.Structure):
     _fields_ = [("d_events", ctypes.c_void_p), ("d_counts", ctypes.c_void_p), ("d_counts_done", ctypes.c_void_p)]
+
+
+class OcRecordSink(ctypes.Structure):
+    _fields_ = [("d_actions", ctypes.c_void_p), ("d_states", ctypes.c_void_p), ("d_layout_ids", ctypes.c_void_p)]
 
 
 class OcAmdError(RuntimeError):
@@ -106,6 +110,8 @@ def load():
     L.oc_rollout_random.argtypes = [bp, vp, vp, vp, vp, i32, u32, u64, i64, i64, i32, sp, ep, vp]
     L.oc_rollout_record.restype = i32
     L.oc_rollout_record.argtypes = [bp, vp, vp, vp, vp, vp, vp, i32, u32, u64, i64, i64, i32, sp, vp]
+    L.oc_rollout_record_ex.restype = i32
+    L.oc_rollout_record_ex.argtypes = [bp, vp, ctypes.POINTER(OcRecordSink), vp, vp, vp, i32, u32, u64, i64, i64, i32, sp, ep, vp]
     L.oc_encode_lossless.restype = i32
     L.oc_encode_lossless.argtypes = [bp, vp, vp, i32, i32, vp]
     L.oc_step_encode.restype = i32

@@ -243,8 +243,8 @@ __global__ __launch_bounds__(BLOCK) void k_output_stores_only_tiled8(float4* __r
     }
 }
 
-// Which kernel serves a call of oc_rollout_random (without OC_OPT_LANE_PAIR / OC_OPT_PREDICATE_INTERACT) or of oc_rollout_record
-// (record): the one place that reads the batch and the call for it.  rollout4.hip's units launch what it returns.
+// Which kernel serves a call of oc_rollout_random (without OC_OPT_LANE_PAIR / OC_OPT_PREDICATE_INTERACT) or of oc_rollout_record /
+// oc_rollout_record_ex (record): the one place that reads the batch and the call for it.  rollout4.hip's units launch what it returns.
 struct RolloutChoice {
     int r4 = -1;                    // a k_rollout4 instance: its index in R4Instances (shared.hpp); -1: k_rollout5, r5
     oc_detail::R5Sel r5 = {};
@@ -262,6 +262,7 @@ RolloutChoice choose_rollout(const OcBatch* b, int n_obj, uint32_t options, int6
                              const EvArgs& ea, bool record) {
     using namespace oc_detail;
     const bool uniform = b->n_layouts == 1, lds = b->n_layouts <= LDS_LAYOUT_MAX, small = b->max_pots >= 1 && b->max_pots <= 2;
+    if (record && ev_on(ea)) return uniform && small ? pick<R4RecEvUniform>() : small ? pick<R4RecEvSmall>() : pick<R4RecEvGeneral>();
     if (record) return uniform && small ? pick<R4RecUniform>() : small ? pick<R4RecSmall>() : pick<R4RecGeneral>();
     // Which family runs:
     //   joint   one two-player, one-pot, new-dynamics layout with at most 6 free cells (cramped_room): the JOINT move table.
@@ -351,6 +352,47 @@ void launch_rollout(const oc_detail::Rollout4Call& c) {
     static void (*const unit[3])(const oc_detail::Rollout4Call&) = {oc_detail::launch_rollout<0>, oc_detail::launch_rollout<1>,
                                                                      oc_detail::launch_rollout<2>};
     unit[c.r4 < 0 ? 1 : oc_detail::R4Instances::PART[c.r4]](c);
+}
+
+// oc_rollout_record and oc_rollout_record_ex: the checks both make (every one before the first device call) and the launch.
+// ex: re-draws and an event sink are accepted, the messages name oc_rollout_record_ex.
+int rollout_record(bool ex, const OcBatch* b, void* d_state, const oc_detail::RecArgs& ra, float* d_rewards, uint8_t* d_flags,
+                   float* d_ep_returns, int horizon, uint32_t options, uint64_t seed, int64_t env_offset, int64_t t0, int n_steps,
+                   const OcStartSpec* start, const OcEventSink* events, void* stream) {
+    const char* const who = ex ? "oc_rollout_record_ex" : "oc_rollout_record";
+    auto refuse = [&](const char* why) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "%s: %s", who, why);
+        return fail(OC_EINVAL, msg);
+    };
+    int n_obj = 0;
+    if (int rc = check_batch(b, &n_obj)) return rc;
+    if (!ra.actions && !ra.states && !ra.layout_ids)
+        return refuse(ex ? "the record sink is NULL or all its arrays are" : "d_actions_out and d_states_out are both NULL");
+    if (((uintptr_t)ra.states & 15u) != 0) return refuse(ex ? "d_states must be 16-byte aligned" : "d_states_out must be 16-byte aligned");
+    if (((uintptr_t)ra.actions & 1u) != 0) return refuse(ex ? "d_actions must be 2-byte aligned" : "d_actions_out must be 2-byte aligned");
+    if (((uintptr_t)ra.layout_ids & 1u) != 0) return refuse("d_layout_ids must be 2-byte aligned");
+    if (options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_WAVEFRONT)) return refuse("options other than OC_OPT_AUTO_RESET / OC_OPT_ONE_WAVEFRONT");
+    if (!ex && start && start->regen_count) return refuse("per-episode layout re-draws (start.regen_count > 0) are not recorded");
+    if ((b->batch_flags & OC_BATCH_TWO_PLAYERS) == 0) return refuse("needs a two-player table (OC_BATCH_TWO_PLAYERS)");
+    StartArgs sa;
+    if (!start_args(start, &sa, b))
+        return refuse(ex ? "start.rnd_obj_prob_thresh must be in [0, 1] and its regen range within the table"
+                         : "start.rnd_obj_prob_thresh must be in [0, 1]");
+    if (start && start->env_offset != env_offset) return refuse("start.env_offset differs from env_offset");
+    if (!d_state) return refuse("NULL state pointer");
+    if (horizon < 1 || horizon > 65535) return refuse("horizon must be in 1..65535");
+    if (n_steps < 0 || n_steps > (1 << 30)) return refuse("n_steps must be in 0..2^30");
+    if (b->n_envs == 0 || n_steps == 0) return OC_OK;
+    const EvArgs ea = ev_args(events, nullptr);
+    const RolloutChoice ch = choose_rollout(b, n_obj, options, t0, n_steps, d_rewards != nullptr, d_flags != nullptr, ea, true);
+    oc_detail::Rollout4Call c;
+    c.b = b; c.n_obj = n_obj; c.d_state = d_state; c.d_rewards = d_rewards; c.d_flags = d_flags; c.d_ep_returns = d_ep_returns;
+    c.horizon = horizon; c.options = options & OC_OPT_AUTO_RESET; c.seed = seed; c.env_offset = env_offset; c.t0 = t0;
+    c.n_steps = n_steps; c.sa = sa; c.ea = ea; c.stream = (hipStream_t)stream; c.r4 = ch.r4; c.r5 = ch.r5;
+    c.ra = ra;
+    launch_rollout(c);
+    return check_launch(who);
 }
 
 }  // namespace
@@ -568,32 +610,16 @@ int oc_rollout_random(const OcBatch* b, void* d_state, float* d_rewards, uint8_t
 int oc_rollout_record(const OcBatch* b, void* d_state, uint8_t* d_actions_out, void* d_states_out, float* d_rewards,
                       uint8_t* d_flags, float* d_ep_returns, int horizon, uint32_t options, uint64_t seed, int64_t env_offset,
                       int64_t t0, int n_steps, const OcStartSpec* start, void* stream) {
-    // (every check comes before the first device call)
-    int n_obj = 0;
-    if (int rc = check_batch(b, &n_obj)) return rc;
-    if (!d_actions_out && !d_states_out) return fail(OC_EINVAL, "oc_rollout_record: d_actions_out and d_states_out are both NULL");
-    if (((uintptr_t)d_states_out & 15u) != 0) return fail(OC_EINVAL, "oc_rollout_record: d_states_out must be 16-byte aligned");
-    if (((uintptr_t)d_actions_out & 1u) != 0) return fail(OC_EINVAL, "oc_rollout_record: d_actions_out must be 2-byte aligned");
-    if (options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_WAVEFRONT))
-        return fail(OC_EINVAL, "oc_rollout_record: options other than OC_OPT_AUTO_RESET / OC_OPT_ONE_WAVEFRONT");
-    if (start && start->regen_count) return fail(OC_EINVAL, "oc_rollout_record: per-episode layout re-draws (start.regen_count > 0) are not recorded");
-    if ((b->batch_flags & OC_BATCH_TWO_PLAYERS) == 0) return fail(OC_EINVAL, "oc_rollout_record: needs a two-player table (OC_BATCH_TWO_PLAYERS)");
-    StartArgs sa;
-    if (!start_args(start, &sa, b)) return fail(OC_EINVAL, "oc_rollout_record: start.rnd_obj_prob_thresh must be in [0, 1]");
-    if (start && start->env_offset != env_offset) return fail(OC_EINVAL, "oc_rollout_record: start.env_offset differs from env_offset");
-    if (!d_state) return fail(OC_EINVAL, "oc_rollout_record: NULL state pointer");
-    if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_rollout_record: horizon must be in 1..65535");
-    if (n_steps < 0 || n_steps > (1 << 30)) return fail(OC_EINVAL, "oc_rollout_record: n_steps must be in 0..2^30");
-    if (b->n_envs == 0 || n_steps == 0) return OC_OK;
-    const EvArgs ea = ev_args(nullptr, nullptr);
-    const RolloutChoice ch = choose_rollout(b, n_obj, options, t0, n_steps, d_rewards != nullptr, d_flags != nullptr, ea, true);
-    oc_detail::Rollout4Call c;
-    c.b = b; c.n_obj = n_obj; c.d_state = d_state; c.d_rewards = d_rewards; c.d_flags = d_flags; c.d_ep_returns = d_ep_returns;
-    c.horizon = horizon; c.options = options & OC_OPT_AUTO_RESET; c.seed = seed; c.env_offset = env_offset; c.t0 = t0;
-    c.n_steps = n_steps; c.sa = sa; c.ea = ea; c.stream = (hipStream_t)stream; c.r4 = ch.r4; c.r5 = ch.r5;
-    c.ra = oc_detail::RecArgs{d_actions_out, d_states_out};
-    launch_rollout(c);
-    return check_launch("oc_rollout_record");
+    return rollout_record(false, b, d_state, oc_detail::RecArgs{d_actions_out, d_states_out, nullptr}, d_rewards, d_flags,
+                          d_ep_returns, horizon, options, seed, env_offset, t0, n_steps, start, nullptr, stream);
+}
+
+int oc_rollout_record_ex(const OcBatch* b, void* d_state, const OcRecordSink* rec, float* d_rewards, uint8_t* d_flags,
+                         float* d_ep_returns, int horizon, uint32_t options, uint64_t seed, int64_t env_offset, int64_t t0,
+                         int n_steps, const OcStartSpec* start, const OcEventSink* events, void* stream) {
+    if (!rec) return fail(OC_EINVAL, "oc_rollout_record_ex: the record sink is NULL or all its arrays are");
+    return rollout_record(true, b, d_state, oc_detail::RecArgs{rec->d_actions, rec->d_states, rec->d_layout_ids}, d_rewards,
+                          d_flags, d_ep_returns, horizon, options, seed, env_offset, t0, n_steps, start, events, stream);
 }
 
 int oc_rollout_plan(const OcBatch* b, int horizon, uint32_t options, int64_t t0, int n_steps, int with_outputs, int event_sink,

@@ -26,7 +26,7 @@ namespace {
 
 // dynamic LDS of a k_rollout4 instance: its tables + the cell words of a workgroup's 256 envs
 // (EV: + the per-episode event counters, [N_EVENT_TYPES][BLOCK] u32 behind the cell words; REC: + the packed object planes,
-//  [n_obj][BLOCK] x 16 bytes)
+//  [n_obj][BLOCK] x 16 bytes, last: behind the counters when both are on)
 template <class P>
 constexpr size_t lds4_bytes(size_t cell_rows) {
     return (size_t)Lds4<P>::CELLS + cell_rows * BLOCK * P::CW + (P::EV ? (size_t)N_EVENT_TYPES * BLOCK * 4 : 0) +

@@ -43,11 +43,12 @@ struct EvArgs {
     uint32_t clear_on_done; // the caller restarts finished envs itself right after this launch (oc_multi_agent_step)
 };
 
-// Where a recorded launch (oc_rollout_record) writes each step's pre-step state and actions, by value in kernel arguments;
-// both NULL in every other launch.
+// Where a recorded launch (oc_rollout_record / oc_rollout_record_ex) writes each step's pre-step state, actions and layout id,
+// by value in kernel arguments; all NULL in every other launch.
 struct RecArgs {
-    uint8_t* actions;  // [n_steps][n_envs][2] u8, or NULL
-    void* states;      // [n_steps][n_planes][n_envs][16] wire-format states, 16-byte aligned, or NULL
+    uint8_t* actions;       // [n_steps][n_envs][2] u8, or NULL
+    void* states;           // [n_steps][n_planes][n_envs][16] wire-format states, 16-byte aligned, or NULL
+    uint16_t* layout_ids;   // [n_steps][n_envs]: the layout id of the state of slice k (after re-draws), or NULL
 };
 
 // ---- The instances of k_rollout4 (step_lut4.hpp).  Each is a traits struct: R4Base's members, overridden by name.  The base
@@ -66,14 +67,14 @@ struct R4Base {
     static constexpr int CW = 2;            // bytes of a cell word
     static constexpr bool NOCONF = false;   // the two players can never face the same cell (OC_BATCH_NO_SHARED_FACES)
     static constexpr bool FT8 = false;      // the flags array is tiled by 8 steps (OC_OPT_FLAGS_TILED8)
-    static constexpr bool REC = false;      // every step's pre-step state and actions are stored too (oc_rollout_record)
+    static constexpr bool REC = false;      // every step's pre-step state, actions and layout id are stored too (oc_rollout_record*)
     // derived
     static constexpr bool RUX = D::UNIFORM || D::RU;  // one LUT variant, patched with the reward floats
     static constexpr int NF = D::MODE == 1 ? 6 : 0;   // free cells the move table has room for
     static constexpr int PART = D::EV || D::MODE == 1 ? 0 : D::MODE == 2 ? 1 : 2;  // the rollout4.hip unit (OC_R4_PART) that compiles it
     static constexpr bool legal() {
         static_assert(D::CW == 2 || D::CW == 4, "cell words are u16 or u32");
-        static_assert(!D::REC || (D::MODE == 0 && D::CW == 2 && !D::EV && !D::FT8), "recording is served by the arithmetic-movement instances");
+        static_assert(!D::REC || (D::MODE == 0 && D::CW == 2 && !D::FT8), "recording is served by the arithmetic-movement instances");
         static_assert(!D::FT8 || ((D::MODE == 1 || D::MODE == 2) && D::OUT && !D::EV),
                       "the tiled flags array is served by joint-table and per-env-terrain instances");
         return true;
@@ -160,6 +161,14 @@ struct R4RecUniform : R4Base<R4RecUniform> {  // one layout, <= 2 pots
 };
 struct R4RecSmall : R4Base<R4RecSmall> { static constexpr bool REC = true; static constexpr int MAXP = 2; };  // mixed tables, <= 2 pots
 struct R4RecGeneral : R4Base<R4RecGeneral> { static constexpr bool REC = true; };  // more than 2 pots
+// -- oc_rollout_record_ex with an event sink: the same three with the event log as well (compiled beside the R4Ev* instances)
+struct R4RecEvUniform : R4Base<R4RecEvUniform> {  // one layout, <= 2 pots
+    static constexpr bool UNIFORM = true, LAY_LDS = true, EV = true, REC = true; static constexpr int MAXP = 2;
+};
+struct R4RecEvSmall : R4Base<R4RecEvSmall> {  // mixed tables, <= 2 pots
+    static constexpr bool EV = true, REC = true; static constexpr int MAXP = 2;
+};
+struct R4RecEvGeneral : R4Base<R4RecEvGeneral> { static constexpr bool EV = true, REC = true; };  // more than 2 pots
 
 template <class... P>
 struct R4List {
@@ -177,14 +186,14 @@ using R4Instances = R4List<R4EvUniform, R4EvSmall, R4EvGeneral, R4JointTiled, R4
                            R4TerrainUniform, R4TerrainUniformLean, R4TerrainLdsTiled, R4TerrainLds, R4TerrainLdsLean,
                            R4TerrainL2OnePotTiled, R4TerrainL2OnePotLeanTiled, R4TerrainL2OnePot, R4TerrainL2OnePotLean, R4TerrainL2,
                            R4TerrainL2Lean, R4ArithUniformOut, R4ArithUniform, R4ArithLdsOut, R4ArithL2Out, R4ArithSmall, R4ArithGeneral,
-                           R4RecUniform, R4RecSmall, R4RecGeneral>;
+                           R4RecUniform, R4RecSmall, R4RecGeneral, R4RecEvUniform, R4RecEvSmall, R4RecEvGeneral>;
 
 // k_rollout5<LAY_LDS, FT8, OLD, BIG, EV, NOOUT> (step_duo5.hpp): the mover / interact kernel, chosen by its own six flags
 struct R5Sel {
     bool lay_lds, ft8, old, big, ev, noout;
 };
 
-// One oc_rollout_random / oc_rollout_record launch, as oc_amd.hip hands it to the unit that compiles the chosen instance.
+// One oc_rollout_random / oc_rollout_record(_ex) launch, as oc_amd.hip hands it to the unit that compiles the chosen instance.
 struct Rollout4Call {
     const OcBatch* b;
     int n_obj;
@@ -202,7 +211,7 @@ struct Rollout4Call {
     hipStream_t stream;
     int r4;     // the chosen k_rollout4 instance: its index in R4Instances; -1: k_rollout5, r5
     R5Sel r5;
-    RecArgs ra = {nullptr, nullptr};  // oc_rollout_record: the recording outputs
+    RecArgs ra = {nullptr, nullptr, nullptr};  // oc_rollout_record / oc_rollout_record_ex: the recording outputs
 };
 // rollout4.hip, compiled with -DOC_R4_PART=UNIT (one explicit instantiation per unit): launches c's instance, which that unit compiles
 template <int UNIT> OC_HIDDEN void launch_rollout(const Rollout4Call& c);

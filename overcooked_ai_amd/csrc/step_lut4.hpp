@@ -502,6 +502,9 @@ __device__ __forceinline__ void env_reset4_draw(const LayC& C, const Lay L, int 
 //   the cell words every step (16 x n_obj LDS reads per lane): a packed copy, [n_obj][BLOCK] x 16 bytes behind the cell words, is
 //   kept current with one byte write per interacting player (the object byte of the cell word it writes) and re-packed after a
 //   restart; a step then reads it with one ds_read_b128 per plane.  The header comes from the registers as in store_env4.
+//   ra.layout_ids: each step's layout id (u16, [n_steps][n]) beside its actions — the id of the state it acts on, i.e. after
+//   the previous step's restart and re-draw (StartArgs.regen_count) —, kept in a register.  With EV too (oc_rollout_record_ex
+//   with an event sink) the packed copy lies behind the event counters: cell words, counters, planes
 // PIPE (MODE 1, 2): the next step's faced cells are read one step ahead.  That hides the read behind the tail of the step
 //   when a SIMD holds one wavefront (65 536 envs); with two or more wavefronts per SIMD the extra LDS traffic costs
 //   more than the latency it hides (131 072 cramped_room envs: 0.48 vs 0.65 us per batched step), so big batches turn it off
@@ -574,9 +577,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
     const uint32_t delta4 = make_delta4(W);
     Env4<MAXP> s;
     load_env4<MAXP, CW>(C, L, st, n, e, n_obj, horizon, s, col);
-    // REC: this lane's packed object planes (16 bytes per plane, [plane][lane]) behind the cell words, and the bytes of the two
-    // cells the players face in the step being run
-    const uint32_t pk = (uint32_t)M::CELLS + ((uint32_t)n_obj * 16u + 2u) * (uint32_t)(BLOCK * CW) + tid * 16u;
+    // REC: this lane's packed object planes (16 bytes per plane, [plane][lane]) behind the cell words (EV: behind the counters),
+    // and the bytes of the two cells the players face in the step being run
+    const uint32_t pk = (uint32_t)M::CELLS + ((uint32_t)n_obj * 16u + 2u) * (uint32_t)(BLOCK * CW) +
+                        (EV ? (uint32_t)(N_EVENT_TYPES * BLOCK * 4) : 0u) + tid * 16u;
     uint32_t pk_f0 = 0, pk_f1 = 0;
     auto pack_planes = [&]() __attribute__((always_inline)) {  // the packed copy from the cell words (launch start, restarts)
         for (int p = 0; p < n_obj; ++p) {
@@ -591,6 +595,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
         }
     };
     if constexpr (REC) pack_planes();
+    // REC with ra.layout_ids: the layout id of the state the next step acts on (a one-layout table: 0)
+    uint32_t lid_now = 0;
+    if constexpr (REC && !UNIFORM) lid_now = ra.layout_ids && layout_id ? (uint32_t)layout_id[e] : 0u;
     bool two = MODE == 1 || MODE == 2 || s.pos1 != 0xFFu;
     uint64_t fm = 0;  // MODE 2: bit c = cell c is floor (static per layout)
     auto floor_mask_of = [&](const Lay Lx) __attribute__((always_inline)) {
@@ -814,6 +821,47 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
             q_hi = ((uint64_t)__float_as_uint(sh1) << 32) | __float_as_uint(sh0);
         }
         uint32_t fl = 0;                              // (a second store to the same address would wait for the first)
+        // EV: event_infos of the step (mdp.py:2121-2308), from its outcomes — against the env as the step leaves it, before a
+        // restart: a restart rewrites the pot cells the mask reads (tables of more than two pots) and a re-draw the layout
+        // constants (C.n_pots, the potting classes)
+        auto step_events = [&]() __attribute__((always_inline)) {
+            uint64_t ev = 0;
+            const bool acted = (((r0 | r1) & 0xFFu) != 0u) | ((((r0 ^ h0_before) | (r1 ^ h1_before)) & 0xFF00u) != 0u);
+            if (acted) {
+                const uint32_t hb0 = (h0_before >> 8) & 0xFFu, hb1 = (h1_before >> 8) & 0xFFu, hn0 = (r0 >> 8) & 0xFFu;
+                const uint32_t hn1 = (r1 >> 8) & 0xFFu, cc1 = conflict ? cw0 : c1;
+                uint32_t useful_pots = 0, n_full = 0;
+#pragma unroll
+                for (int k = 0; k < MAXP; ++k) {
+                    if (MAXP > 1 && (uint32_t)k >= C.n_pots) break;
+                    uint32_t kb;
+                    if (PW) {
+                        kb = cw_kb<CW>(pw[k]);
+                    } else {
+                        const uint32_t pa = col + s.poff[k];
+                        kb = cw_kb<CW>(cw_rd<CW>(pa));
+                        kb = ((r1 & F4_POTBITS) && fo1 == pa) ? cw_kb<CW>(cc1) : kb;
+                        kb = ((r0 & F4_POTBITS) && fo0 == pa) ? cw_kb<CW>(c0) : kb;
+                    }
+                    useful_pots += (kb != KB_POT + PC_EMPTY && kb != KB_POT + PC_IDLE3) ? 1u : 0u;
+                    n_full += kb >= KB_POT + PC_IDLE3 ? 1u : 0u;
+                }
+                const bool du0 = two & (((hb1 == OC_O_DISH) ? 1u : 0u) < useful_pots) & (dc_before == DC0);
+                const bool du1 = two & (((hn0 == OC_O_DISH) ? 1u : 0u) < useful_pots) & (dc_mid == DC0);
+                const uint32_t t0_ = (cw_kb<CW>(c0) * 137u) >> 12, t1_ = (cw_kb<CW>(cc1) * 137u) >> 12;  // key byte / 30 = terrain type
+                const bool disp0 = (t0_ == OC_T_ONION_DISP) | (t0_ == OC_T_TOMATO_DISP) | (t0_ == OC_T_DISH_DISP);
+                const bool disp1 = (t1_ == OC_T_ONION_DISP) | (t1_ == OC_T_TOMATO_DISP) | (t1_ == OC_T_DISH_DISP);
+                ev = interact_events<0>(C, t0_, hb0, cw_obj<CW>(c0), ((r0 & F4_CHG) != 0u) & (t0_ == OC_T_COUNTER),
+                                        disp0 & (hb0 == 0u) & (hn0 != 0u), (r0 & F4_PLACE) != 0u, (r0 & F4_PLATE) != 0u,
+                                        (r0 & F4_SERVE) != 0u, hb1, du0, n_full, two) |
+                     interact_events<1>(C, t1_, hb1, cw_obj<CW>(cc1), ((r1 & F4_CHG) != 0u) & (t1_ == OC_T_COUNTER),
+                                        disp1 & (hb1 == 0u) & (hn1 != 0u), (r1 & F4_PLACE) != 0u, (r1 & F4_PLATE) != 0u,
+                                        (r1 & F4_SERVE) != 0u, hn0, du1, n_full, two);
+            }
+            return ev;
+        };
+        uint64_t ev_end = 0;  // EV: the mask of a step that restarts the env, taken before the restart
+        bool ev_ended = false;
         if (__builtin_expect(rare, 0)) {
             bool grid_changed = false;  // something below wrote to the grid after the prefetch
             if (conflict) {
@@ -902,10 +950,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
             if (done) {  // OvercookedEnv.step bookkeeping at the horizon (env.py:266-267, 321-325)
                 fl = OC_F_DONE;
                 if (options & OC_OPT_AUTO_RESET) {
+                    if constexpr (EV) {
+                        ev_end = step_events();
+                        ev_ended = true;
+                    }
                     if (sa.enabled) {  // the batch's start_state_fn: drawn from (seed, global env, epoch of this step)
                         if (!UNIFORM && sa.regen_count) {  // ... on a layout drawn for the new episode (regen_mdp, env.py:288-302)
                             const uint32_t lid = draw_layout(sa, g, sa.epoch + step_k);
                             sa.layout_ids[e] = (uint16_t)lid;
+                            if constexpr (REC) lid_now = lid;
                             L = LAY_LDS ? Lay{reinterpret_cast<const uint8_t*>(s_lay) + lid * 256u}
                                         : Lay{reinterpret_cast<const uint8_t*>(g_layouts) + (size_t)lid * 256u};
                             C = load_consts<UNIFORM>(L);
@@ -956,40 +1009,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
             q_lo = ((uint64_t)__float_as_uint(rw.y) << 32) | __float_as_uint(rw.x);
             q_hi = ((uint64_t)__float_as_uint(rw.w) << 32) | __float_as_uint(rw.z);
         }
-        if (EV) {  // event_infos of the step (mdp.py:2121-2308), from the outcomes above
-            uint64_t ev = 0;
-            const bool acted = (((r0 | r1) & 0xFFu) != 0u) | ((((r0 ^ h0_before) | (r1 ^ h1_before)) & 0xFF00u) != 0u);
-            if (acted) {
-                const uint32_t hb0 = (h0_before >> 8) & 0xFFu, hb1 = (h1_before >> 8) & 0xFFu, hn0 = (r0 >> 8) & 0xFFu;
-                const uint32_t hn1 = (r1 >> 8) & 0xFFu, cc1 = conflict ? cw0 : c1;
-                uint32_t useful_pots = 0, n_full = 0;
-#pragma unroll
-                for (int k = 0; k < MAXP; ++k) {
-                    if (MAXP > 1 && (uint32_t)k >= C.n_pots) break;
-                    uint32_t kb;
-                    if (PW) {
-                        kb = cw_kb<CW>(pw[k]);
-                    } else {
-                        const uint32_t pa = col + s.poff[k];
-                        kb = cw_kb<CW>(cw_rd<CW>(pa));
-                        kb = ((r1 & F4_POTBITS) && fo1 == pa) ? cw_kb<CW>(cc1) : kb;
-                        kb = ((r0 & F4_POTBITS) && fo0 == pa) ? cw_kb<CW>(c0) : kb;
-                    }
-                    useful_pots += (kb != KB_POT + PC_EMPTY && kb != KB_POT + PC_IDLE3) ? 1u : 0u;
-                    n_full += kb >= KB_POT + PC_IDLE3 ? 1u : 0u;
-                }
-                const bool du0 = two & (((hb1 == OC_O_DISH) ? 1u : 0u) < useful_pots) & (dc_before == DC0);
-                const bool du1 = two & (((hn0 == OC_O_DISH) ? 1u : 0u) < useful_pots) & (dc_mid == DC0);
-                const uint32_t t0_ = (cw_kb<CW>(c0) * 137u) >> 12, t1_ = (cw_kb<CW>(cc1) * 137u) >> 12;  // key byte / 30 = terrain type
-                const bool disp0 = (t0_ == OC_T_ONION_DISP) | (t0_ == OC_T_TOMATO_DISP) | (t0_ == OC_T_DISH_DISP);
-                const bool disp1 = (t1_ == OC_T_ONION_DISP) | (t1_ == OC_T_TOMATO_DISP) | (t1_ == OC_T_DISH_DISP);
-                ev = interact_events<0>(C, t0_, hb0, cw_obj<CW>(c0), ((r0 & F4_CHG) != 0u) & (t0_ == OC_T_COUNTER),
-                                        disp0 & (hb0 == 0u) & (hn0 != 0u), (r0 & F4_PLACE) != 0u, (r0 & F4_PLATE) != 0u,
-                                        (r0 & F4_SERVE) != 0u, hb1, du0, n_full, two) |
-                     interact_events<1>(C, t1_, hb1, cw_obj<CW>(cc1), ((r1 & F4_CHG) != 0u) & (t1_ == OC_T_COUNTER),
-                                        disp1 & (hb1 == 0u) & (hn1 != 0u), (r1 & F4_PLACE) != 0u, (r1 & F4_PLATE) != 0u,
-                                        (r1 & F4_SERVE) != 0u, hn0, du1, n_full, two);
-            }
+        if (EV) {  // event_infos of the step
+            uint64_t ev = ev_ended ? ev_end : step_events();
             if (ea.events) ea.events[(int64_t)step_k * n + e] = ev;
             if (ea.counts) {  // the episode's counters live in LDS for the launch ([event type][lane]; count_events' packing)
                 while (ev) {
@@ -1040,14 +1061,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, OC_R4_
         if (OUT) { rew_k += 8 * n; flg_k += 8 * n; }
     };
 
-    // REC: at the top of a step, its actions and the state it acts on — row pointers (wave-uniform) + lane offsets, the states
-    // with the streaming policy of the reward quads (written once, read by nobody in this launch)
+    // REC: at the top of a step, its actions, layout id and the state it acts on — row pointers (wave-uniform) + lane offsets,
+    // the states with the streaming policy of the reward quads (written once, read by nobody in this launch)
     uint8_t* rec_act = REC && ra.actions ? ra.actions + (int64_t)blk * BLOCK * 2 : nullptr;
+    uint16_t* rec_lid = REC && ra.layout_ids ? ra.layout_ids + (int64_t)blk * BLOCK : nullptr;
     uint4* rec_st = REC && ra.states ? reinterpret_cast<uint4*>(ra.states) + (int64_t)blk * BLOCK : nullptr;
     auto record = [&](uint32_t a0, uint32_t a1) __attribute__((always_inline)) {
         if (rec_act) {
             asm volatile("global_store_short %0, %1, %2" : : "v"(tid * 2u), "v"(a0 | (a1 << 8)), "s"(rec_act) : "memory");
             rec_act += 2 * n;
+        }
+        if (rec_lid) {
+            asm volatile("global_store_short %0, %1, %2" : : "v"(tid * 2u), "v"(lid_now), "s"(rec_lid) : "memory");
+            rec_lid += n;
         }
         if (rec_st) {
             auto put = [&](const uint4* row, uint4 v) __attribute__((always_inline)) {

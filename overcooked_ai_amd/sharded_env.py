@@ -153,14 +153,18 @@ class ShardedVecOvercookedEnv:
         masks = None if mask is None else self._split(mask)
         self._each(lambda s, i: s.env.reset(None if masks is None else masks[i], **kw))
 
-    def rollout_random(self, n_steps, rewards_out=None, flags_out=None, events_out=None, flags_tiled8=False):
+    def rollout_random(self, n_steps, rewards_out=None, flags_out=None, events_out=None, flags_tiled8=False, actions_out=None,
+                       states_out=None, layouts_out=None):
         """n_steps fused random-policy transitions on every shard (one oc_rollout_random launch per shard, all in flight
         together).  rewards_out / flags_out (/ events_out: int64 [n_steps, n] masks): per-shard lists (alloc_outputs), or
         None.  flags_tiled8: the OC_OPT_FLAGS_TILED8 flags layout on every shard (alloc_outputs(n_steps, flags_tiled8=True);
-        ValueError from the first shard whose batch / launch shape no tiled instance serves)."""
-        self._each(lambda s, i: s.env.rollout_random(n_steps, None if rewards_out is None else rewards_out[i],
-                                                     None if flags_out is None else flags_out[i],
-                                                     None if events_out is None else events_out[i], flags_tiled8=flags_tiled8))
+        ValueError from the first shard whose batch / launch shape no tiled instance serves).  actions_out / states_out /
+        layouts_out: per-shard lists of the recording arrays of VecOvercookedEnv.rollout_random (each shard records its own
+        envs), or None."""
+        pick = lambda lst, i: None if lst is None else lst[i]  # noqa: E731
+        self._each(lambda s, i: s.env.rollout_random(n_steps, pick(rewards_out, i), pick(flags_out, i), pick(events_out, i),
+                                                     flags_tiled8=flags_tiled8, actions_out=pick(actions_out, i),
+                                                     states_out=pick(states_out, i), layouts_out=pick(layouts_out, i)))
         return rewards_out, flags_out
 
     def rollout_encode(self, n_steps, obs_out, rewards_out=None, flags_out=None, actions=None, dtype=torch.uint8):

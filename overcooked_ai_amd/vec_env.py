@@ -306,7 +306,7 @@ class VecOvercookedEnv:
         return StepServer(self, idle_ms, life_s)
 
     def rollout_random(self, n_steps, rewards_out=None, flags_out=None, events_out=None, flags_tiled8=False,
-                       actions_out=None, states_out=None):
+                       actions_out=None, states_out=None, layouts_out=None):
         """n_steps fused random-policy transitions in one launch (Philox actions, see include/oc_amd.h).  A launch
         costs ~16 us outside its step loop (tables, state load / store, dispatch): 12 % of a 400-step launch at 65 536
         envs, 3 % of a 2 000-step one — prefer few long launches.
@@ -319,10 +319,14 @@ class VecOvercookedEnv:
         Recording (oc_rollout_record): actions_out uint8 [n_steps, n_envs, 2] receives the actions drawn at every step and
         states_out uint8 [n_steps, n_planes, n_envs, 16] the packed state each step acts on (slice k: before step k, after step
         k - 1's restart; slice 0 is the state before the call, self.state the state after the last step).  Same stream, same
-        results as without them; `trajectories.recorded_trajectories` turns them into get_rollouts' dict.  Not combined with
-        events_out, flags_tiled8, event counters (track_events), lane_pair / predicate_interact or regen_layout (ValueError)."""
-        if actions_out is not None or states_out is not None:
-            return self._rollout_record(int(n_steps), rewards_out, flags_out, events_out, flags_tiled8, actions_out, states_out)
+        results as without them; `trajectories.recorded_trajectories` turns them into get_rollouts' dict.  layouts_out int16 /
+        uint16 [n_steps, n_envs] receives the layout id of each states_out slice (after the previous step's re-draw, regen_layout).
+        A recording with events_out, event counters (track_events), regen_layout or layouts_out runs oc_rollout_record_ex (the
+        event log and the re-draws of the same launch without recording), any other oc_rollout_record.  Not combined with
+        flags_tiled8 or lane_pair / predicate_interact (ValueError)."""
+        if actions_out is not None or states_out is not None or layouts_out is not None:
+            return self._rollout_record(int(n_steps), rewards_out, flags_out, events_out, flags_tiled8, actions_out, states_out,
+                                        layouts_out)
         if events_out is not None:
             self._check(events_out, torch.int64, int(n_steps) * self.n_envs, "events_out")
         if rewards_out is not None:
@@ -343,13 +347,17 @@ class VecOvercookedEnv:
         self._advance(int(n_steps))
         return rewards_out, flags_out
 
-    def _rollout_record(self, K, rewards_out, flags_out, events_out, flags_tiled8, actions_out, states_out):
-        if events_out is not None or flags_tiled8 or self.event_counts is not None:
-            raise ValueError("recording (actions_out / states_out) does not log events and takes the plain flags layout")
+    def _rollout_record(self, K, rewards_out, flags_out, events_out, flags_tiled8, actions_out, states_out, layouts_out=None):
+        if flags_tiled8:
+            raise ValueError("recording (actions_out / states_out / layouts_out) takes the plain flags layout")
         if self.lane_pair or self.predicate_interact:
-            raise ValueError("recording (actions_out / states_out) runs the default kernel: lane_pair / predicate_interact are off")
-        if self.regen is not None:
-            raise ValueError("recording (actions_out / states_out) does not follow per-episode layout re-draws (regen_layout)")
+            raise ValueError("recording (actions_out / states_out / layouts_out) runs the default kernel: lane_pair / predicate_interact are off")
+        if layouts_out is not None and (layouts_out.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16))
+                                        or layouts_out.device != self.state.device or not layouts_out.is_contiguous()
+                                        or layouts_out.numel() != K * self.n_envs):
+            raise ValueError("layouts_out must be a contiguous int16 / uint16 tensor with %d elements on %s" % (K * self.n_envs, self.state.device))
+        if events_out is not None:
+            self._check(events_out, torch.int64, K * self.n_envs, "events_out")
         if actions_out is not None:
             self._check(actions_out, torch.uint8, K * self.n_envs * 2, "actions_out")
         if states_out is not None:
@@ -358,14 +366,19 @@ class VecOvercookedEnv:
             self._check(rewards_out, torch.float32, K * self.n_envs * 4, "rewards_out")
         if flags_out is not None:
             self._check(flags_out, torch.uint8, K * self.n_envs, "flags_out")
-        rc = self._launch(self.lib.oc_rollout_record, self._bref, self._state_ptr,
-                          actions_out.data_ptr() if actions_out is not None else None,
-                          states_out.data_ptr() if states_out is not None else None,
-                          rewards_out.data_ptr() if rewards_out is not None else None,
-                          flags_out.data_ptr() if flags_out is not None else None, self._ep_ptr, self.horizon,
-                          self.options, self.seed, self.env_offset, self.t_global, K,
-                          self._start_spec() if self.auto_reset else None)
-        _lib.check(rc, "oc_rollout_record")
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        start = self._start_spec() if self.auto_reset else None
+        if events_out is not None or self.event_counts is not None or self.regen is not None or layouts_out is not None:
+            sink = _lib.OcRecordSink(ptr(actions_out), ptr(states_out), ptr(layouts_out))
+            rc = self._launch(self.lib.oc_rollout_record_ex, self._bref, self._state_ptr, ctypes.byref(sink), ptr(rewards_out),
+                              ptr(flags_out), self._ep_ptr, self.horizon, self.options, self.seed, self.env_offset, self.t_global,
+                              K, start, self._event_sink(events_out))
+            _lib.check(rc, "oc_rollout_record_ex")
+        else:
+            rc = self._launch(self.lib.oc_rollout_record, self._bref, self._state_ptr, ptr(actions_out), ptr(states_out),
+                              ptr(rewards_out), ptr(flags_out), self._ep_ptr, self.horizon, self.options, self.seed,
+                              self.env_offset, self.t_global, K, start)
+            _lib.check(rc, "oc_rollout_record")
         self.t_global += K
         self._advance(K)
         return rewards_out, flags_out

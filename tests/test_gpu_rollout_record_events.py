@@ -1,0 +1,253 @@
+"""Recorded random rollouts with the event log and per-episode layout re-draws (oc_rollout_record_ex /
+rollout_random(actions_out=, states_out=, layouts_out=, events_out=) with track_events and regen_layout) on the GPU: every
+recorded step against the C oracle (state, layout id, rewards, flags, event mask), recording against the same launch without
+it, the converter's ep_game_stats against the drop-in get_rollouts on each episode's recorded layout, two shards against one
+batch, and a full-size launch."""
+import os
+
+import numpy as np
+import pytest
+
+from helpers import CANONICAL_5
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+SEVEN = {"grid": "XPPPPPX\nO 1 2 O\nX     X\nXDPSPTX", "onion_time": 3, "tomato_time": 5, "onion_value": 7, "tomato_value": 4}
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    if not torch.cuda.is_available():
+        pytest.fail("gpu-marked test run without a GPU")
+    from overcooked_ai_amd import _lib
+
+    _lib.load()
+    return torch.device("cuda:0")
+
+
+def _table(name):
+    from overcooked_ai_amd.layout_gen import reference_generated_layouts
+    from overcooked_ai_amd.layouts import LayoutSpec, LayoutTable, spec_from_name
+
+    if name == "mix5":
+        return LayoutTable([spec_from_name(nm) for nm in CANONICAL_5], pad_to=(9, 5))
+    if name == "generated":
+        return LayoutTable(reference_generated_layouts(512))
+    if name == "seven_pots":
+        return LayoutTable([LayoutSpec(SEVEN)])
+    if name.endswith("_old"):  # old dynamics: a full pot starts cooking by itself
+        return LayoutTable([spec_from_name(name[:-4], old_dynamics=True)])
+    return LayoutTable([spec_from_name(name)])
+
+
+def _oracle(specs):
+    from oracle import oracle as O
+
+    O.set_threads(min(16, len(os.sched_getaffinity(0))))
+    return O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in specs])
+
+
+def _env(gpu, name, n, horizon, seed=3, env_offset=0, t0=0, regen=False, **kw):
+    from overcooked_ai_amd.vec_env import VecOvercookedEnv
+
+    table = _table(name)
+    lid = ((np.arange(n) * 7 + 3) % len(table)).astype(np.uint16) if len(table) > 1 else None
+    env = VecOvercookedEnv(table, n, horizon=horizon, device=gpu, auto_reset=True, seed=seed, env_offset=env_offset,
+                           layout_id=lid, regen_layout=regen, track_events=True, **kw)
+    env.t_global = t0
+    return env
+
+
+def _buffers(env, K):
+    dev, n = env.state.device, env.n_envs
+    return dict(actions_out=torch.full((K, n, 2), 0xEE, dtype=torch.uint8, device=dev),
+                states_out=torch.full((K, env.n_planes, n, 16), 0xEE, dtype=torch.uint8, device=dev),
+                layouts_out=torch.full((K, n), -1, dtype=torch.int16, device=dev),
+                events_out=torch.full((K, n), -1, dtype=torch.int64, device=dev),
+                rewards_out=torch.zeros((K, n, 4), dtype=torch.float32, device=dev),
+                flags_out=torch.zeros((K, n), dtype=torch.uint8, device=dev))
+
+
+def _host(bufs):
+    out = {k: v.cpu().numpy() for k, v in bufs.items()}
+    out["layouts_out"] = out["layouts_out"].view(np.uint16)
+    out["events_out"] = out["events_out"].view(np.uint64)
+    return out
+
+
+def _record_and_check(gpu, name, n, K, horizon, t0=0, seed=3, env_offset=0, start=None, regen=False, check_envs=None):
+    """One recorded launch with everything on, then for every step k: oracle.step(states[k], actions[k], layout_id=layouts[k])
+    = (states[k + 1] or the final state, layouts[k + 1] or the final ids, rewards[k], flags[k]), and its event mask =
+    events_out[k].  Returns the host arrays, the number of restarts and how many envs changed layout."""
+    from oracle import oracle as O
+
+    start = start or {}
+    env = _env(gpu, name, n, horizon, seed=seed, env_offset=env_offset, t0=t0, regen=regen, **start)
+    before, lid0, epoch = env.get_packed_state().copy(), env.layout_ids(), env.reset_epoch
+    bufs = _buffers(env, K)
+    env.rollout_random(K, **bufs)
+    assert env.t_global == t0 + K
+    H = _host(bufs)
+    S, A, Lid, E, R, F = H["states_out"], H["actions_out"], H["layouts_out"], H["events_out"], H["rewards_out"], H["flags_out"]
+    final, lid_final = env.get_packed_state(), env.layout_ids()
+    assert np.array_equal(S[0], before) and np.array_equal(Lid[0], lid0)
+    for k in range(K):
+        assert np.array_equal(A[k], O.random_actions(seed, env_offset, t0 + k, n)), "actions of step %d" % k
+    sel = np.arange(n) if check_envs is None else np.asarray(check_envs)
+    if (start or regen) and check_envs is not None:
+        raise AssertionError("drawn starts and layouts are keyed by the global env: check all envs")
+    orc = _oracle(env.table.specs)
+    multi = len(env.table) > 1
+    resets = 0
+    for k in range(K):
+        sp = None
+        if start or regen:
+            sp = O.start_spec(seed=seed, env_offset=env_offset, epoch=epoch + k, regen=(0, len(env.table)) if regen else None, **start)
+        lid = np.ascontiguousarray(Lid[k][sel]) if multi else None
+        if not multi:
+            assert not Lid[k].any(), "a one-layout table records layout 0"
+        nxt, r, f = orc.step(np.ascontiguousarray(S[k][:, sel]), A[k][sel], horizon=horizon, options=1, layout_id=lid, start=sp)
+        after, lid_after = (S[k + 1][:, sel], Lid[k + 1][sel]) if k + 1 < K else (final[:, sel], lid_final[sel])
+        assert np.array_equal(nxt, after), "state after step %d" % k
+        if multi:
+            assert np.array_equal(lid, lid_after), "layout ids after step %d" % k
+        assert np.array_equal(r, R[k][sel]), "rewards of step %d" % k
+        assert np.array_equal(f, F[k][sel]), "flags of step %d" % k
+        assert np.array_equal(orc.last_events, E[k][sel]), "event masks of step %d" % k
+        resets += int(((f & 4) != 0).sum())
+    changed = int((lid_final != lid0).sum()) if multi else 0
+    return H, resets, changed
+
+
+@pytest.mark.parametrize("name,n", [("cramped_room", 4096), ("asymmetric_advantages", 4096), ("mix5", 5000),
+                                    ("seven_pots", 1000), ("cramped_room_old", 2048)])
+def test_every_step_follows_the_oracle(gpu, name, n):
+    H, resets, _ = _record_and_check(gpu, name, n, K=90, horizon=40)
+    assert resets == 2 * n  # two horizons inside the launch
+    assert H["events_out"].any() and H["rewards_out"][..., 2:].sum() > 0
+
+
+@pytest.mark.parametrize("name,n", [("mix5", 5000), ("generated", 6000)])
+def test_layout_redraws(gpu, name, n):
+    _, resets, changed = _record_and_check(gpu, name, n, K=75, horizon=30, seed=7, regen=True)
+    assert resets == 2 * n and changed > n // 2
+
+
+def test_redraws_with_drawn_starts_off_grid_t0(gpu):
+    _, resets, changed = _record_and_check(gpu, "mix5", 3000, K=61, horizon=25, t0=5, seed=11, env_offset=777, regen=True,
+                                           start={"random_start_pos": True, "rnd_obj_prob_thresh": 0.4})
+    assert resets == 2 * 3000 and changed > 0
+
+
+@pytest.mark.parametrize("name,regen", [("cramped_room", False), ("mix5", True), ("generated", True)])
+def test_recording_changes_nothing(gpu, name, regen):
+    start = {"random_start_pos": True, "rnd_obj_prob_thresh": 0.2} if name == "mix5" else {}
+    runs = []
+    for record in (False, True):
+        env = _env(gpu, name, 3000, 50, seed=17, t0=6, regen=regen, **start)
+        bufs = _buffers(env, 130)
+        if record:
+            env.rollout_random(130, **bufs)
+        else:
+            env.rollout_random(130, bufs["rewards_out"], bufs["flags_out"], bufs["events_out"])
+        stats = [{k: v.cpu().numpy() for k, v in env.event_stats(finished).items()} for finished in (False, True)]
+        runs.append([bufs["rewards_out"].cpu().numpy(), bufs["flags_out"].cpu().numpy(), bufs["events_out"].cpu().numpy(),
+                     env.ep_returns.cpu().numpy(), env.get_packed_state(), env.layout_ids(), env.t_global, env.reset_epoch,
+                     env.event_counts.cpu().numpy(), env.event_counts_done.cpu().numpy()] + [s[k] for s in stats for k in sorted(s)])
+    assert runs[1][9].any()  # some episode has finished with events
+    for a, b in zip(*runs):
+        assert np.array_equal(np.asarray(a), np.asarray(b))
+
+
+class _Replay:
+    """An agent pair that plays back one episode's recorded actions."""
+
+    def __init__(self, actions):
+        from overcooked_ai_amd.actions import Action
+
+        self.rows, self.i, self.A = actions, 0, Action.INDEX_TO_ACTION
+
+    def joint_action(self, state):
+        a = self.rows[self.i]
+        self.i += 1
+        return (self.A[int(a[0])], {}), (self.A[int(a[1])], {})
+
+
+def _same_game_stats(a, b):
+    assert set(a) == set(b)
+    for key in a:
+        if key.startswith("cumulative_"):
+            assert a[key].dtype == np.asarray(b[key]).dtype and list(a[key]) == list(b[key]), key
+        else:
+            assert a[key] == b[key], key
+
+
+def test_converter_matches_dropin_get_rollouts(gpu):
+    from overcooked_ai_amd.env import OvercookedEnv
+    from overcooked_ai_amd.mdp import OvercookedGridworld
+    from overcooked_ai_amd.state import canonical_state_dict
+    from overcooked_ai_amd.trajectories import recorded_trajectories
+
+    H, games, n = 30, 3, 64
+    env = _env(gpu, "mix5", n, H, seed=4, regen=True)
+    recs = []
+    for K in (37, H * games - 37 + 5):  # two recordings joined along the step axis
+        recs.append(_buffers(env, K))
+        env.rollout_random(K, **recs[-1])
+    joined = {k: torch.cat([r[k] for r in recs]) for k in recs[0]}
+    envs = [0, 7, 63]
+    traj = recorded_trajectories(env, joined["states_out"], joined["actions_out"], joined["rewards_out"], joined["flags_out"],
+                                 envs=envs, events_out=joined["events_out"], layouts_out=joined["layouts_out"])
+    assert len(traj["ep_lengths"]) == games * len(envs)
+    A, Lid = joined["actions_out"].cpu().numpy(), joined["layouts_out"].cpu().numpy().view(np.uint16)
+    layouts_seen = set()
+    for i, e in enumerate(envs):
+        for g in range(games):
+            j, k = i * games + g, g * H
+            lid = int(Lid[k, e])
+            layouts_seen.add(lid)
+            mdp = OvercookedGridworld.from_spec(env.table.specs[lid])
+            ref = OvercookedEnv.from_mdp(mdp, horizon=H).get_rollouts(_Replay(A[k:k + H, e]), 1)
+            assert [canonical_state_dict(s) for s in traj["ep_states"][j]] == [canonical_state_dict(s) for s in ref["ep_states"][0]]
+            assert list(traj["ep_actions"][j]) == [tuple(a) for a in ref["ep_actions"][0]]
+            assert list(traj["ep_rewards"][j]) == list(ref["ep_rewards"][0])
+            assert list(traj["ep_dones"][j]) == list(ref["ep_dones"][0])
+            assert traj["ep_returns"][j] == ref["ep_returns"][0] and traj["ep_lengths"][j] == ref["ep_lengths"][0] == H
+            for a, b in zip(traj["ep_infos"][j], ref["ep_infos"][0]):
+                assert list(a["sparse_r_by_agent"]) == list(b["sparse_r_by_agent"])
+                assert list(a["shaped_r_by_agent"]) == list(b["shaped_r_by_agent"])
+            last, ref_last = traj["ep_infos"][j][-1]["episode"], ref["ep_infos"][0][-1]["episode"]
+            assert last["ep_sparse_r"] == ref_last["ep_sparse_r"] and last["ep_shaped_r"] == ref_last["ep_shaped_r"]
+            assert last["ep_length"] == ref_last["ep_length"]
+            _same_game_stats(last["ep_game_stats"], ref_last["ep_game_stats"])
+            assert traj["mdp_params"][j]["layout_name"] == mdp.mdp_params["layout_name"] == CANONICAL_5[lid]
+    assert len(layouts_seen) > 1
+
+
+def test_two_shards_equal_one_batch(gpu):
+    from overcooked_ai_amd.sharded_env import ShardedVecOvercookedEnv
+
+    n, K, H = 3000, 70, 25
+    table = _table("mix5")
+    lid = ((np.arange(n) * 7 + 3) % 5).astype(np.uint16)
+    kw = dict(horizon=H, auto_reset=True, seed=21, regen_layout=True, track_events=True)
+    one = _env(gpu, "mix5", n, H, seed=21, regen=True)
+    ref = _buffers(one, K)
+    one.rollout_random(K, **ref)
+    sh = ShardedVecOvercookedEnv(table, n, devices=["cuda:0", "cuda:0"], layout_id=lid, **kw)
+    per = [_buffers(s.env, K) for s in sh.shards]
+    sh.rollout_random(K, **{k: [p[k] for p in per] for k in per[0]})
+    sh.synchronize()
+    for key, axis in (("actions_out", 1), ("states_out", 2), ("layouts_out", 1), ("events_out", 1), ("rewards_out", 1),
+                      ("flags_out", 1)):
+        assert torch.equal(torch.cat([p[key] for p in per], dim=axis), ref[key]), key
+    assert (one.layout_ids() != lid).any()
+
+
+def test_large_launch_65536_x_400(gpu):
+    check = np.arange(0, 65536, 16)  # 4 096 envs against the oracle
+    H, resets, _ = _record_and_check(gpu, "cramped_room", 65536, K=400, horizon=150, seed=8, check_envs=check)
+    assert resets == 2 * len(check)
+    assert H["events_out"].any()
