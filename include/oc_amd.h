@@ -606,8 +606,9 @@ int oc_output_stores_only(int64_t n_envs, int n_steps, float* d_rewards, uint8_t
 /*
  * oc_rollout_plan (ABI 6) — which kernel instance oc_rollout_random would launch for this batch and launch shape, as text
  * (e.g. "k_rollout5<LAY_LDS=true, FT8=true, OLD=false, BIG=false, EV=false> mover + interact wavefronts, 1 round(s), 130864 B LDS").
- * The answer comes from oc_rollout_random's own dispatch, walked with stand-in pointers: every argument check applies, every branch
- * is the one a real call takes, nothing is launched and no device memory is touched — so it also runs on a host without a GPU
+ * oc_rollout_random plans every call before it launches anything (its argument checks, then the choice of kernels); this is that
+ * plan, put into words instead of launched: every check applies, every choice is the one a real call gets, and the code that answers
+ * holds no launch and no device pointer — so it also runs on a host without a GPU
  * (the device's SIMD count then defaults to MI355X's 1 024).  docs/DISPATCH.md is generated from it (tools/gen_dispatch_table.py)
  * and tests/test_dispatch_table.py keeps that file equal to what the library answers.
  *   with_outputs  1: d_rewards and d_flags are given; 0: both NULL

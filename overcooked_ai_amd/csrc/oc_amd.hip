@@ -16,6 +16,8 @@
 //   featurize.hpp       featurize_state mdp.py:2579-2898: k_featurize
 //   potential.hpp       potential_function mdp.py:2920-3238: k_potential, k_potential2
 //   shaping.hpp         OvercookedMultiAgent.step reward, rllib.py:306-329: k_shape_rewards
+//   train_obs.hpp       the training step with its observation in one kernel: k_train_step_obs
+//   stores_only.hpp     the output stores of a rollout and nothing else: k_output_stores_only (oc_output_stores_only)
 //   this file           launch dispatch and the extern "C" entry points declared in include/oc_amd.h
 //
 // Execution model: one lane per env, 64-lane wavefronts, 256-lane workgroups.  This is integer /
@@ -34,7 +36,6 @@
 namespace oc_detail {
 __thread char g_err[256] = "";
 __thread bool g_lds_refused = false;
-__thread char* g_describe = nullptr;
 }  // namespace oc_detail
 
 namespace {
@@ -54,6 +55,7 @@ namespace {
 #include "potential.hpp"
 #include "shaping.hpp"
 #include "train_obs.hpp"
+#include "stores_only.hpp"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -70,36 +72,48 @@ int check_batch(const OcBatch* b, int* n_obj) {
     return OC_OK;
 }
 
-// LDS bytes one encode workgroup may fill with output (40 KiB = 3 workgroups per CU).  The library reads no environment
-// variable unless it is built with -DOC_AMD_TUNING (the knobs of the measurement scripts under tools/: OC_ENC_LDS,
-// OC_STEP_NO_LEAN, OC_ROLLOUT_PIPE, OC_ROLLOUT_NO_MODE2, OC_ROLLOUT_ENCODE_WAVES).
-inline int enc_lds_budget() {
+// The library reads no environment variable unless it is built with -DOC_AMD_TUNING (the knobs of the measurement scripts under
+// tools/: OC_ENC_LDS, OC_STEP_NO_LEAN, OC_ROLLOUT_PIPE, OC_ROLLOUT_NO_MODE2, OC_ROLLOUT_ENCODE_WAVES, ...): a knob's value, or
+// whether it is set at all.  Every other build: the default, a constant.
 #ifdef OC_AMD_TUNING
-    static int v = []() { const char* e = getenv("OC_ENC_LDS"); return e ? atoi(e) : 40 * 1024; }();
-    return v;
+inline int tuning_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline bool tuning_set(const char* name) { return getenv(name) != nullptr; }
 #else
-    return 40 * 1024;
+constexpr int tuning_int(const char*, int dflt) { return dflt; }
+constexpr bool tuning_set(const char*) { return false; }
 #endif
+
+// LDS bytes one encode workgroup may fill with output (40 KiB = 3 workgroups per CU)
+inline int enc_lds_budget() {
+    static const int v = tuning_int("OC_ENC_LDS", 40 * 1024);
+    return v;
 }
 // ... for the persistent single-layout kernel: ~19 envs per group is the measured sweet spot (65 536 cramped_room envs,
 // u8: 18.1 us with a 20 KB image, 20.6 us with 40 KB, 25.2 us with 12 KB; 9x5 grids: 40 KB = 17 envs is best)
 inline size_t enc_uniform_budget(size_t env_bytes) {
-#ifdef OC_AMD_TUNING
-    static const bool forced = getenv("OC_ENC_LDS") != nullptr;
-#else
-    constexpr bool forced = false;
-#endif
+    static const bool forced = tuning_set("OC_ENC_LDS");
     const size_t cap = (size_t)enc_lds_budget();
     if (forced) return cap;
     const size_t want = 19 * env_bytes;
     return want < cap ? want : cap;
 }
 
-// OcStartSpec -> kernel argument; false when the spec is malformed (a message is left in g_err)
+// the keys every draw of a start spec is made with (seed, epoch, env offset), as a kernel argument
+void start_keys(const OcStartSpec* sp, StartArgs* sa) {
+    memset(sa, 0, sizeof(*sa));
+    sa->enabled = 1;
+    sa->seed_lo = (uint32_t)sp->seed;
+    sa->seed_hi = (uint32_t)(sp->seed >> 32);
+    sa->epoch = sp->epoch;
+    sa->env_offset = sp->env_offset;
+}
+
+// OcStartSpec -> kernel argument; false when the spec is malformed
 bool start_args(const OcStartSpec* sp, StartArgs* sa, const OcBatch* b = nullptr) {
     memset(sa, 0, sizeof(*sa));
     if (!sp) return true;
     if (!(sp->rnd_obj_prob_thresh >= 0.0 && sp->rnd_obj_prob_thresh <= 1.0)) return false;
+    start_keys(sp, sa);
     if (sp->regen_count) {  // per-episode layout re-draw: the ids must exist, be writable and in range
         if (!b || (uint64_t)sp->regen_first + sp->regen_count > (uint64_t)(b ? b->n_layouts : 0)) return false;
         if (b->n_layouts > 1) {
@@ -109,14 +123,42 @@ bool start_args(const OcStartSpec* sp, StartArgs* sa, const OcBatch* b = nullptr
             sa->layout_ids = const_cast<uint16_t*>(b->d_layout_id);
         }  // (one layout: nothing to draw)
     }
-    sa->enabled = 1;
-    sa->seed_lo = (uint32_t)sp->seed;
-    sa->seed_hi = (uint32_t)(sp->seed >> 32);
-    sa->epoch = sp->epoch;
-    sa->env_offset = sp->env_offset;
     sa->thresh = (uint64_t)(sp->rnd_obj_prob_thresh * 4294967296.0);  // floor(thresh * 2^32); 1.0 -> 2^32: always
     sa->random_start_pos = sp->random_start_pos != 0;
     return true;
+}
+
+// ---- checks that many entry points make, each said once; who: the entry point's name, in front of the message
+int refuse(const char* who, const char* why) {
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
+    return fail(OC_EINVAL, msg);
+}
+int check_horizon(const char* who, int horizon) {
+    return horizon < 1 || horizon > 65535 ? refuse(who, "horizon must be in 1..65535") : OC_OK;
+}
+const char* const START_SPEC_RULE = "start.rnd_obj_prob_thresh must be in [0, 1] and its regen range within the table";
+int check_start(const char* who, const OcStartSpec* sp, StartArgs* sa, const OcBatch* b) {
+    return start_args(sp, sa, b) ? OC_OK : refuse(who, START_SPEC_RULE);
+}
+inline bool obs_dtype_ok(int obs_dtype) { return obs_dtype == OC_OBS_U8 || obs_dtype == OC_OBS_F32; }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+int check_obs(const char* who, int obs_dtype, const void* d_obs) {
+    if (!obs_dtype_ok(obs_dtype)) return refuse(who, "bad obs_dtype");
+    return aligned16(d_obs) ? OC_OK : refuse(who, "d_obs must be 16-byte aligned");
+}
+
+// envs per observation template: the fewest whose bytes are a multiple of 16 (1, 2 or 4)
+inline int envs_per_template(size_t env_bytes) {
+    int unit = 1;
+    while (((env_bytes * unit) & 15u) != 0) unit *= 2;
+    return unit;
+}
+
+// tuning builds: OC_STEP_NO_LEAN sends every single step to the general kernels (k_step3, k_train_step)
+inline bool step_no_lean() {
+    static const bool v = tuning_set("OC_STEP_NO_LEAN");
+    return v;
 }
 
 EvArgs ev_args(const OcEventSink* sink, uint64_t* d_events, uint32_t clear_on_done = 0) {
@@ -147,9 +189,9 @@ inline bool ev_on(const EvArgs& ea) { return ea.events || ea.counts; }
 // canonical layout, 8 is the format's maximum),
 // LAY_LDS (layout table staged in LDS vs read from HBM/L2 for tables of more than 32 layouts)
 template <bool EVENTS>
-void launch_step(const OcBatch* b, int n_obj, const void* d_state_in, void* d_state_out, const uint8_t* d_actions,
-                 float* d_rewards, uint8_t* d_flags, float* d_ep_returns, uint64_t* d_events, int horizon,
-                 uint32_t options, hipStream_t s, const StartArgs& sa, const EvArgs& ea, int n_steps = 1) {
+void launch_step_as(const OcBatch* b, int n_obj, const void* d_state_in, void* d_state_out, const uint8_t* d_actions,
+                    float* d_rewards, uint8_t* d_flags, float* d_ep_returns, int horizon, uint32_t options, hipStream_t s,
+                    const StartArgs& sa, const EvArgs& ea, int n_steps) {
     const bool uniform = b->n_layouts == 1;
     const bool lds = b->n_layouts <= LDS_LAYOUT_MAX;
     const bool small = b->max_pots >= 1 && b->max_pots <= 2;
@@ -159,12 +201,7 @@ void launch_step(const OcBatch* b, int n_obj, const void* d_state_in, void* d_st
     if (!(options & OC_OPT_PREDICATE_INTERACT)) {
         // one step on a grid of at most 64 cells: the transition on the wire format itself (step_one.hpp) — in place or out of
         // place, with or without event logging
-#ifdef OC_AMD_TUNING
-        static const bool no_lean = getenv("OC_STEP_NO_LEAN") != nullptr;  // tuning builds: k_step3 for every oc_step
-#else
-        constexpr bool no_lean = false;
-#endif
-        if (n_steps == 1 && n_obj <= STEP1_MAX_PLANES && !no_lean) {
+        if (n_steps == 1 && n_obj <= STEP1_MAX_PLANES && !step_no_lean()) {
             const size_t smem1 = (size_t)n_obj * BLOCK * sizeof(uint4);
 #define GO1(U, MP, LL)                                                                                                \
     hipLaunchKernelGGL((k_step1<U, MP, LL, EVENTS>), grid, block, smem1, s, b->d_layouts, b->n_layouts, b->d_layout_id, \
@@ -205,42 +242,12 @@ void launch_step(const OcBatch* b, int n_obj, const void* d_state_in, void* d_st
     else GO(false, 8, false);
 #undef GO
 }
-
-// oc_output_stores_only: the output stores of a rollout and nothing else (include/oc_amd.h) — one store of each kind per step,
-// in step order, through (row pointer of the step, lane offset) exactly as k_rollout4 addresses its rows
-__global__ __launch_bounds__(BLOCK) void k_output_stores_only(float4* __restrict__ rewards, uint8_t* __restrict__ flags, int64_t n,
-                                                              int n_steps) {
-    const uint32_t blk = xcd_block();  // (as k_rollout4: each XCD owns a contiguous eighth of the envs)
-    const int64_t e = (int64_t)blk * BLOCK + threadIdx.x;
-    if (e >= n) return;
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4* rew_k = rewards + (int64_t)blk * BLOCK;                      // wave-uniform row pointers
-    uint8_t* flg_k = flags ? flags + (int64_t)blk * BLOCK : nullptr;
-#pragma unroll 1
-    for (int k = 0; k < n_steps; ++k) {
-        stream_store16(reinterpret_cast<uint4*>(rew_k + threadIdx.x), make_uint4(0u, 0u, 0u, 0u));  // (as k_rollout4 stores them beside [step][env] flags)
-        if (flg_k) { flg_k[threadIdx.x] = 0; flg_k += n; }
-        rew_k += n;
-    }
-}
-// ... with the flags array tiled by 8 steps (OC_OPT_FLAGS_TILED8): per block of 8 steps eight reward rows and ONE 8-byte store
-// per lane into the block's tile row, as the kernels that serve that layout write it
-__global__ __launch_bounds__(BLOCK) void k_output_stores_only_tiled8(float4* __restrict__ rewards, uint2* __restrict__ flag_tiles,
-                                                                     int64_t n, int n_blocks) {
-    const uint32_t blk = xcd_block();
-    const int64_t e = (int64_t)blk * BLOCK + threadIdx.x;
-    if (e >= n) return;
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4* rew_k = rewards + (int64_t)blk * BLOCK;
-    uint2* flg_k = flag_tiles + (int64_t)blk * BLOCK;
-#pragma unroll 1
-    for (int b = 0; b < n_blocks; ++b) {
-#pragma unroll
-        for (int k8 = 0; k8 < 8; ++k8) rew_k[(int64_t)k8 * n + threadIdx.x] = zero4;
-        flg_k[threadIdx.x] = make_uint2(0u, 0u);
-        rew_k += 8 * n;
-        flg_k += n;
-    }
+// ... with the event-logging instances when ea names a sink
+void launch_step(const OcBatch* b, int n_obj, const void* d_state_in, void* d_state_out, const uint8_t* d_actions,
+                 float* d_rewards, uint8_t* d_flags, float* d_ep_returns, int horizon, uint32_t options, hipStream_t s,
+                 const StartArgs& sa, const EvArgs& ea, int n_steps = 1) {
+    const auto go = ev_on(ea) ? launch_step_as<true> : launch_step_as<false>;
+    go(b, n_obj, d_state_in, d_state_out, d_actions, d_rewards, d_flags, d_ep_returns, horizon, options, s, sa, ea, n_steps);
 }
 
 // Which kernel serves a call of oc_rollout_random (without OC_OPT_LANE_PAIR / OC_OPT_PREDICATE_INTERACT) or of oc_rollout_record /
@@ -248,9 +255,15 @@ __global__ __launch_bounds__(BLOCK) void k_output_stores_only_tiled8(float4* __r
 struct RolloutChoice {
     int r4 = -1;                    // a k_rollout4 instance: its index in R4Instances (shared.hpp); -1: k_rollout5, r5
     oc_detail::R5Sel r5 = {};
-    int head = 0, bulk = 0;         // bulk > 0: the call runs as three calls of head, bulk (whole 8-step blocks) and the other steps
+    int head = 0, bulk = 0;         // bulk > 0: not one launch but three, of head, bulk (whole 8-step blocks) and the other steps
     const char* refusal = nullptr;  // the call is refused (OC_EINVAL) with this message
 };
+// What a choice needs to know of a call's arrays: which ones are there (oc_rollout_plan has no more than that to give)
+struct RolloutArrays {
+    bool state, rewards, flags, flags_aligned8;
+    bool ev_masks, ev_counts;  // the event sink's per-step masks / per-episode counters
+};
+inline bool ev_on(const RolloutArrays& have) { return have.ev_masks || have.ev_counts; }
 
 template <class P>
 RolloutChoice pick() {
@@ -258,11 +271,11 @@ RolloutChoice pick() {
     return RolloutChoice{oc_detail::R4Instances::id<P>()};
 }
 
-RolloutChoice choose_rollout(const OcBatch* b, int n_obj, uint32_t options, int64_t t0, int n_steps, bool rewards, bool flags,
-                             const EvArgs& ea, bool record) {
+RolloutChoice choose_launch(const OcBatch* b, int n_obj, uint32_t options, int64_t t0, int n_steps, const RolloutArrays& have,
+                            bool record) {
     using namespace oc_detail;
     const bool uniform = b->n_layouts == 1, lds = b->n_layouts <= LDS_LAYOUT_MAX, small = b->max_pots >= 1 && b->max_pots <= 2;
-    if (record && ev_on(ea)) return uniform && small ? pick<R4RecEvUniform>() : small ? pick<R4RecEvSmall>() : pick<R4RecEvGeneral>();
+    if (record && ev_on(have)) return uniform && small ? pick<R4RecEvUniform>() : small ? pick<R4RecEvSmall>() : pick<R4RecEvGeneral>();
     if (record) return uniform && small ? pick<R4RecUniform>() : small ? pick<R4RecSmall>() : pick<R4RecGeneral>();
     // Which family runs:
     //   joint   one two-player, one-pot, new-dynamics layout with at most 6 free cells (cramped_room): the JOINT move table.
@@ -270,18 +283,11 @@ RolloutChoice choose_rollout(const OcBatch* b, int n_obj, uint32_t options, int6
     //   mode2   two players everywhere, at most two pots and 64 cells, one set of shaping rewards: per-env terrain with
     //           the pose one step ahead on a floor mask (BASELINE configs[3] / [4], single layouts with more free cells)
     //   else    arithmetic movement (MODE 0): any table, either dynamics, event logging
-    const bool two = (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0, events = ev_on(ea), tiled8 = (options & OC_OPT_FLAGS_TILED8) != 0;
+    const bool two = (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0, events = ev_on(have), tiled8 = (options & OC_OPT_FLAGS_TILED8) != 0;
     const bool old_dyn = (b->batch_flags & OC_BATCH_NEW_DYNAMICS) == 0;  // some layout may use old dynamics
-    const bool out = rewards && flags, noout = !rewards && !flags;  // (noout: a rollout run for its final states / returns / event counters)
-#ifdef OC_AMD_TUNING
-    static const int forced_pipe = []() { const char* e = getenv("OC_ROLLOUT_PIPE"); return e ? atoi(e) : -1; }();  // tuning builds
-    static const bool no_mode2 = getenv("OC_ROLLOUT_NO_MODE2") != nullptr;
-    static const int forced_rounds = []() { const char* e = getenv("OC_DUO_ROUNDS"); return e ? atoi(e) : 0; }();
-#else
-    constexpr int forced_pipe = -1;
-    constexpr bool no_mode2 = false;
-    constexpr int forced_rounds = 0;
-#endif
+    const bool out = have.rewards && have.flags, noout = !have.rewards && !have.flags;  // (noout: a rollout run for its final states / returns / event counters)
+    static const int forced_pipe = tuning_int("OC_ROLLOUT_PIPE", -1), forced_rounds = tuning_int("OC_DUO_ROUNDS", 0);
+    static const bool no_mode2 = tuning_set("OC_ROLLOUT_NO_MODE2");
     // big batches (more than ~1.5 wavefronts per SIMD) hide latency with the other wavefronts: no one-step-ahead reads
     const bool pipe = forced_pipe >= 0 ? forced_pipe != 0 : b->n_envs <= simd_count() * 64 * 3 / 2;
     const bool joint = uniform && two && b->max_pots == 1 && b->max_free_cells >= 2 && b->max_free_cells <= 6u && out && !old_dyn &&
@@ -293,7 +299,7 @@ RolloutChoice choose_rollout(const OcBatch* b, int n_obj, uint32_t options, int6
     const int n_cells = b->width * b->height;
     // (an event log: per-episode counters only — no per-step masks —, table in LDS, <= 64 cells, and the counters must fit the
     //  CU's LDS beside the cell words: grids of up to 48 cells)
-    const bool ev_ok = !events || (ea.events == nullptr && lds && n_cells <= 64 && rollout5_lds_bytes(true, false, true, n_obj) <= (size_t)160 * 1024);
+    const bool ev_ok = !events || (!have.ev_masks && lds && n_cells <= 64 && rollout5_lds_bytes(true, false, true, n_obj) <= (size_t)160 * 1024);
     const bool terrain_shape = two && small && shaping_uniform && (n_cells <= 64 || (n_cells <= 128 && lds)) && ev_ok && !no_mode2;
     const bool terrain_ok = terrain_shape && out;
     const bool mode2 = !joint && terrain_ok && !old_dyn && n_cells <= 64 && !events;
@@ -347,11 +353,64 @@ RolloutChoice choose_rollout(const OcBatch* b, int n_obj, uint32_t options, int6
     return ch;
 }
 
-// launches c's instance through the rollout4.hip unit that compiles it
-void launch_rollout(const oc_detail::Rollout4Call& c) {
+// One launch of a rollout call: n_steps' steps [off, off + len), the options word its kernel receives, its kernel
+struct RolloutPart {
+    int off, len;
+    uint32_t options;
+    RolloutChoice ch;
+};
+// ... and the launches of the whole call, in stream order: one, or the head / bulk / tail split (see choose_launch; a part may be
+// empty).  Head and tail run with OC_OPT_ONE_WAVEFRONT.
+struct RolloutParts {
+    int n = 0;
+    RolloutPart part[3];
+    const char* refusal = nullptr;
+};
+RolloutParts choose_rollout(const OcBatch* b, int n_obj, uint32_t options, int64_t t0, int n_steps, const RolloutArrays& have,
+                            bool record) {
+    RolloutParts r;
+    const RolloutChoice whole = choose_launch(b, n_obj, options, t0, n_steps, have, record);
+    if (whole.bulk == 0) {
+        r.part[r.n++] = RolloutPart{0, n_steps, options, whole};
+        r.refusal = whole.refusal;
+        return r;
+    }
+    const int lens[3] = {whole.head, whole.bulk, n_steps - whole.head - whole.bulk};
+    int off = 0;
+    for (int k = 0; k < 3; ++k) {
+        const uint32_t opt = options | (k == 1 ? 0u : (uint32_t)OC_OPT_ONE_WAVEFRONT);
+        r.part[r.n++] = RolloutPart{off, lens[k], opt, lens[k] > 0 ? choose_launch(b, n_obj, opt, t0 + off, lens[k], have, record) : RolloutChoice{}};
+        if (!r.refusal) r.refusal = r.part[k].ch.refusal;
+        off += lens[k];
+    }
+    return r;
+}
+
+// the rollout4.hip unit that compiles c's instance
+int rollout_unit(const oc_detail::Rollout4Call& c) { return c.r4 < 0 ? 1 : oc_detail::R4Instances::PART[c.r4]; }
+
+// launches the parts of c, the whole call, each through its unit.  Part k gets step t0 + off, the output rows from off on, and
+// draws a restart at its step j from epoch + off + j, as the whole call would.
+int launch_rollout(const RolloutParts& parts, const oc_detail::Rollout4Call& c, const char* who) {
     static void (*const unit[3])(const oc_detail::Rollout4Call&) = {oc_detail::launch_rollout<0>, oc_detail::launch_rollout<1>,
                                                                      oc_detail::launch_rollout<2>};
-    unit[c.r4 < 0 ? 1 : oc_detail::R4Instances::PART[c.r4]](c);
+    for (int k = 0; k < parts.n; ++k) {
+        const RolloutPart& pt = parts.part[k];
+        if (pt.len == 0) continue;
+        oc_detail::Rollout4Call ck = c;
+        const int64_t rows = (int64_t)pt.off * c.b->n_envs;
+        if (c.d_rewards) ck.d_rewards = c.d_rewards + rows * 4;
+        if (c.d_flags) ck.d_flags = c.d_flags + rows;
+        ck.t0 = c.t0 + pt.off;
+        ck.n_steps = pt.len;
+        ck.options = pt.options;
+        if (c.sa.enabled) ck.sa.epoch = c.sa.epoch + (uint32_t)pt.off;
+        ck.r4 = pt.ch.r4;
+        ck.r5 = pt.ch.r5;
+        unit[rollout_unit(ck)](ck);
+        if (int rc = check_launch(who)) return rc;
+    }
+    return OC_OK;
 }
 
 // oc_rollout_record and oc_rollout_record_ex: the checks both make (every one before the first device call) and the launch.
@@ -360,39 +419,111 @@ int rollout_record(bool ex, const OcBatch* b, void* d_state, const oc_detail::Re
                    float* d_ep_returns, int horizon, uint32_t options, uint64_t seed, int64_t env_offset, int64_t t0, int n_steps,
                    const OcStartSpec* start, const OcEventSink* events, void* stream) {
     const char* const who = ex ? "oc_rollout_record_ex" : "oc_rollout_record";
-    auto refuse = [&](const char* why) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "%s: %s", who, why);
-        return fail(OC_EINVAL, msg);
-    };
     int n_obj = 0;
     if (int rc = check_batch(b, &n_obj)) return rc;
     if (!ra.actions && !ra.states && !ra.layout_ids)
-        return refuse(ex ? "the record sink is NULL or all its arrays are" : "d_actions_out and d_states_out are both NULL");
-    if (((uintptr_t)ra.states & 15u) != 0) return refuse(ex ? "d_states must be 16-byte aligned" : "d_states_out must be 16-byte aligned");
-    if (((uintptr_t)ra.actions & 1u) != 0) return refuse(ex ? "d_actions must be 2-byte aligned" : "d_actions_out must be 2-byte aligned");
-    if (((uintptr_t)ra.layout_ids & 1u) != 0) return refuse("d_layout_ids must be 2-byte aligned");
-    if (options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_WAVEFRONT)) return refuse("options other than OC_OPT_AUTO_RESET / OC_OPT_ONE_WAVEFRONT");
-    if (!ex && start && start->regen_count) return refuse("per-episode layout re-draws (start.regen_count > 0) are not recorded");
-    if ((b->batch_flags & OC_BATCH_TWO_PLAYERS) == 0) return refuse("needs a two-player table (OC_BATCH_TWO_PLAYERS)");
+        return refuse(who, ex ? "the record sink is NULL or all its arrays are" : "d_actions_out and d_states_out are both NULL");
+    if (!aligned16(ra.states)) return refuse(who, ex ? "d_states must be 16-byte aligned" : "d_states_out must be 16-byte aligned");
+    if (((uintptr_t)ra.actions & 1u) != 0) return refuse(who, ex ? "d_actions must be 2-byte aligned" : "d_actions_out must be 2-byte aligned");
+    if (((uintptr_t)ra.layout_ids & 1u) != 0) return refuse(who, "d_layout_ids must be 2-byte aligned");
+    if (options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_WAVEFRONT)) return refuse(who, "options other than OC_OPT_AUTO_RESET / OC_OPT_ONE_WAVEFRONT");
+    if (!ex && start && start->regen_count) return refuse(who, "per-episode layout re-draws (start.regen_count > 0) are not recorded");
+    if ((b->batch_flags & OC_BATCH_TWO_PLAYERS) == 0) return refuse(who, "needs a two-player table (OC_BATCH_TWO_PLAYERS)");
     StartArgs sa;
-    if (!start_args(start, &sa, b))
-        return refuse(ex ? "start.rnd_obj_prob_thresh must be in [0, 1] and its regen range within the table"
-                         : "start.rnd_obj_prob_thresh must be in [0, 1]");
-    if (start && start->env_offset != env_offset) return refuse("start.env_offset differs from env_offset");
-    if (!d_state) return refuse("NULL state pointer");
-    if (horizon < 1 || horizon > 65535) return refuse("horizon must be in 1..65535");
-    if (n_steps < 0 || n_steps > (1 << 30)) return refuse("n_steps must be in 0..2^30");
+    if (!start_args(start, &sa, b)) return refuse(who, ex ? START_SPEC_RULE : "start.rnd_obj_prob_thresh must be in [0, 1]");
+    if (start && start->env_offset != env_offset) return refuse(who, "start.env_offset differs from env_offset");
+    if (!d_state) return refuse(who, "NULL state pointer");
+    if (int rc = check_horizon(who, horizon)) return rc;
+    if (n_steps < 0 || n_steps > (1 << 30)) return refuse(who, "n_steps must be in 0..2^30");
     if (b->n_envs == 0 || n_steps == 0) return OC_OK;
     const EvArgs ea = ev_args(events, nullptr);
-    const RolloutChoice ch = choose_rollout(b, n_obj, options, t0, n_steps, d_rewards != nullptr, d_flags != nullptr, ea, true);
-    oc_detail::Rollout4Call c;
-    c.b = b; c.n_obj = n_obj; c.d_state = d_state; c.d_rewards = d_rewards; c.d_flags = d_flags; c.d_ep_returns = d_ep_returns;
-    c.horizon = horizon; c.options = options & OC_OPT_AUTO_RESET; c.seed = seed; c.env_offset = env_offset; c.t0 = t0;
-    c.n_steps = n_steps; c.sa = sa; c.ea = ea; c.stream = (hipStream_t)stream; c.r4 = ch.r4; c.r5 = ch.r5;
-    c.ra = ra;
-    launch_rollout(c);
-    return check_launch(who);
+    const RolloutArrays have = {true, d_rewards != nullptr, d_flags != nullptr, false, ea.events != nullptr, ea.counts != nullptr};
+    const oc_detail::Rollout4Call c = {b, n_obj, d_state, d_rewards, d_flags, d_ep_returns, horizon, options & OC_OPT_AUTO_RESET, seed,
+                                       env_offset, t0, n_steps, sa, ea, (hipStream_t)stream, -1, {}, ra};
+    return launch_rollout(choose_rollout(b, n_obj, c.options, t0, n_steps, have, true), c, who);
+}
+
+// ---- oc_rollout_random: the call is planned first (every check, every choice; no launch, no device memory), then launched —
+//      or, by oc_rollout_plan, described
+struct RolloutPlan {
+    int rc = OC_OK;  // the call is refused with this code (the message: oc_last_error)
+    enum Family { NOTHING, PAIR, PREDICATE, LUT } family = NOTHING;  // no envs or steps / k_rollout_pair / k_rollout / k_rollout4, k_rollout5
+    int n_obj = 0;
+    StartArgs sa = {};
+    RolloutParts parts;  // LUT: its launches
+};
+
+RolloutPlan plan_rollout(const OcBatch* b, const RolloutArrays& have, int horizon, uint32_t options, int64_t env_offset, int64_t t0,
+                         int n_steps, const OcStartSpec* start) {
+    const char* const who = "oc_rollout_random";
+    RolloutPlan p;
+    const auto refused = [&p](int rc) { p.rc = rc; return p; };
+    if (int rc = check_batch(b, &p.n_obj)) return refused(rc);
+    if (int rc = check_start(who, start, &p.sa, b)) return refused(rc);
+    if ((start || ev_on(have)) && (options & (OC_OPT_LANE_PAIR | OC_OPT_PREDICATE_INTERACT)))
+        return refused(refuse(who, "drawn start states / event logging need the default kernel (k_rollout4)"));
+    if (start && start->env_offset != env_offset) return refused(refuse(who, "start.env_offset differs from env_offset"));
+    if (!have.state) return refused(refuse(who, "NULL state pointer"));
+    if (int rc = check_horizon(who, horizon)) return refused(rc);
+    if (n_steps < 0 || n_steps > (1 << 30)) return refused(refuse(who, "n_steps must be in 0..2^30"));
+    if (options & OC_OPT_FLAGS_TILED8) {  // the launch-shape half of the option's conditions (the batch half: choose_launch)
+        if (!have.rewards || !have.flags || !have.flags_aligned8)
+            return refused(refuse(who, "OC_OPT_FLAGS_TILED8 needs d_rewards and an 8-byte aligned d_flags"));
+        if ((t0 & 7) != 0 || (n_steps & 7) != 0) return refused(refuse(who, "OC_OPT_FLAGS_TILED8 needs t0 and n_steps to be multiples of 8"));
+        if (have.ev_masks || (options & (OC_OPT_LANE_PAIR | OC_OPT_PREDICATE_INTERACT)))
+            return refused(refuse(who, "OC_OPT_FLAGS_TILED8 goes with the default kernel and no per-step event masks "
+                                       "(per-episode counters: the mover / interact kernel writes it)"));
+    }
+    if (b->n_envs == 0 || n_steps == 0) return p;
+    // Lane pairs (two lanes per env) halve the per-wavefront instruction stream at ~1.5x the total VALU work.  They
+    // used to win for batches that leave SIMDs without a wavefront (<= 32 768 envs); with the table-driven step built
+    // for ILP the lane-per-env kernel is faster at every batch size (us per batched step, lane vs pair, cramped_room:
+    // 0.55 vs 0.73 at 4 096 envs, 0.57 vs 0.76 at 32 768), so pairs run only when OC_OPT_LANE_PAIR asks for them.
+    const bool pair_ok = b->max_pots >= 1 && b->max_pots <= 2 && (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0;
+    if (pair_ok && (options & OC_OPT_LANE_PAIR)) {
+        p.family = RolloutPlan::PAIR;
+    } else if (options & OC_OPT_PREDICATE_INTERACT) {
+        p.family = RolloutPlan::PREDICATE;
+    } else {  // k_rollout4 / k_rollout5 (their instances are compiled in rollout4.hip)
+        p.family = RolloutPlan::LUT;
+        p.parts = choose_rollout(b, p.n_obj, options, t0, n_steps, have, false);
+        if (p.parts.refusal) return refused(fail(OC_EINVAL, p.parts.refusal));
+    }
+    return p;
+}
+
+// two lanes per env (k_rollout_pair)
+void launch_rollout_pair(const oc_detail::Rollout4Call& c) {
+    const OcBatch* b = c.b;
+    const size_t smem = (size_t)c.n_obj * 8 * PAIR_ENVS * sizeof(uint32_t);
+    const dim3 grid((unsigned)((b->n_envs + PAIR_ENVS - 1) / PAIR_ENVS)), block(BLOCK);
+    const auto go = [&](auto uniform, auto lay_lds) {
+        hipLaunchKernelGGL((k_rollout_pair<decltype(uniform)::value, decltype(lay_lds)::value>), grid, block, smem, c.stream, b->d_layouts,
+                           b->n_layouts, b->d_layout_id, (uint4*)c.d_state, (float4*)c.d_rewards, c.d_flags, (float4*)c.d_ep_returns,
+                           b->n_envs, b->width, c.n_obj, c.horizon, c.options, (uint32_t)c.seed, (uint32_t)(c.seed >> 32),
+                           c.env_offset, c.t0, c.n_steps);
+    };
+    if (b->n_layouts == 1) go(std::true_type(), std::true_type());
+    else if (b->n_layouts <= LDS_LAYOUT_MAX) go(std::false_type(), std::true_type());
+    else go(std::false_type(), std::false_type());
+}
+
+// the predicate-network interact (k_rollout)
+void launch_rollout_predicate(const oc_detail::Rollout4Call& c) {
+    const OcBatch* b = c.b;
+    const size_t smem = (size_t)c.n_obj * 8 * BLOCK * sizeof(uint32_t);
+    const dim3 grid(grid_for(b->n_envs)), block(BLOCK);
+#define GO(U, MP, LL)                                                                                       \
+    do {                                                                                                    \
+        if (!want_lds(k_rollout<U, MP, LL>, smem)) break;                                                   \
+        hipLaunchKernelGGL((k_rollout<U, MP, LL>), grid, block, smem, c.stream, b->d_layouts, b->n_layouts, \
+                           b->d_layout_id, (uint4*)c.d_state, (float4*)c.d_rewards, c.d_flags,              \
+                           (float4*)c.d_ep_returns, b->n_envs, b->width, c.n_obj, c.horizon, c.options,     \
+                           (uint32_t)c.seed, (uint32_t)(c.seed >> 32), c.env_offset, c.t0, c.n_steps);      \
+    } while (0)
+    if (b->n_layouts == 1) { if (b->max_pots >= 1 && b->max_pots <= 2) GO(true, 2, true); else GO(true, 8, true); }
+    else GO(false, 8, false);
+#undef GO
 }
 
 }  // namespace
@@ -447,7 +578,7 @@ int oc_step(const OcBatch* b, const void* d_state_in, void* d_state_out, const u
     int n_obj = 0;
     if (int rc = check_batch(b, &n_obj)) return rc;
     StartArgs sa;
-    if (!start_args(start, &sa, b)) return fail(OC_EINVAL, "oc_step: start.rnd_obj_prob_thresh must be in [0, 1] and its regen range within the table");
+    if (int rc = check_start("oc_step", start, &sa, b)) return rc;
     const EvArgs ea = ev_args(events, d_events);
     if (options & OC_OPT_PREDICATE_INTERACT) {
         if (start) return fail(OC_EINVAL, "oc_step: drawn start states need the table-driven kernel (no PREDICATE_INTERACT)");
@@ -455,15 +586,9 @@ int oc_step(const OcBatch* b, const void* d_state_in, void* d_state_out, const u
     }
     if (!d_state_in || !d_state_out || !d_actions || !d_rewards || !d_flags)
         return fail(OC_EINVAL, "oc_step: NULL state/actions/rewards/flags pointer");
-    if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_step: horizon must be in 1..65535");
+    if (int rc = check_horizon("oc_step", horizon)) return rc;
     if (b->n_envs == 0) return OC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (ev_on(ea))
-        launch_step<true>(b, n_obj, d_state_in, d_state_out, d_actions, d_rewards, d_flags, d_ep_returns, ea.events,
-                          horizon, options, s, sa, ea);
-    else
-        launch_step<false>(b, n_obj, d_state_in, d_state_out, d_actions, d_rewards, d_flags, d_ep_returns, nullptr,
-                           horizon, options, s, sa, ea);
+    launch_step(b, n_obj, d_state_in, d_state_out, d_actions, d_rewards, d_flags, d_ep_returns, horizon, options, (hipStream_t)stream, sa, ea);
     return check_launch("oc_step");
 }
 
@@ -472,7 +597,7 @@ int oc_step_many(const OcBatch* b, void* d_state, const uint8_t* d_actions, floa
                  const OcEventSink* events, void* stream) {
     if (n_steps < 0) return fail(OC_EINVAL, "oc_step_many: n_steps < 0");
     StartArgs sa;
-    if (!start_args(start, &sa, b)) return fail(OC_EINVAL, "oc_step_many: start.rnd_obj_prob_thresh must be in [0, 1] and its regen range within the table");
+    if (int rc = check_start("oc_step_many", start, &sa, b)) return rc;
     const EvArgs ea = ev_args(events, nullptr);
     if ((start || ev_on(ea)) && (options & OC_OPT_PREDICATE_INTERACT))
         return fail(OC_EINVAL, "oc_step_many: drawn start states / event logging need the table-driven kernel");
@@ -480,15 +605,10 @@ int oc_step_many(const OcBatch* b, void* d_state, const uint8_t* d_actions, floa
     if (int rc = check_batch(b, &n_obj)) return rc;
     if (!d_state || !d_actions || !d_rewards || !d_flags)
         return fail(OC_EINVAL, "oc_step_many: NULL state/actions/rewards/flags pointer");
-    if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_step_many: horizon must be in 1..65535");
+    if (int rc = check_horizon("oc_step_many", horizon)) return rc;
     if (b->n_envs == 0 || n_steps == 0) return OC_OK;
     if (!(options & OC_OPT_PREDICATE_INTERACT)) {  // all K transitions in one launch, the envs stay on chip in between
-        if (ev_on(ea))
-            launch_step<true>(b, n_obj, d_state, d_state, d_actions, d_rewards, d_flags, d_ep_returns, nullptr, horizon,
-                              options, (hipStream_t)stream, sa, ea, n_steps);
-        else
-            launch_step<false>(b, n_obj, d_state, d_state, d_actions, d_rewards, d_flags, d_ep_returns, nullptr, horizon,
-                               options, (hipStream_t)stream, sa, ea, n_steps);
+        launch_step(b, n_obj, d_state, d_state, d_actions, d_rewards, d_flags, d_ep_returns, horizon, options, (hipStream_t)stream, sa, ea, n_steps);
         return check_launch("oc_step_many");
     }
     for (int k = 0; k < n_steps; ++k) {
@@ -503,107 +623,16 @@ int oc_step_many(const OcBatch* b, void* d_state, const uint8_t* d_actions, floa
 int oc_rollout_random(const OcBatch* b, void* d_state, float* d_rewards, uint8_t* d_flags, float* d_ep_returns,
                       int horizon, uint32_t options, uint64_t seed, int64_t env_offset, int64_t t0, int n_steps,
                       const OcStartSpec* start, const OcEventSink* events, void* stream) {
-    int n_obj = 0;
-    if (int rc = check_batch(b, &n_obj)) return rc;
-    StartArgs sa;
-    if (!start_args(start, &sa, b)) return fail(OC_EINVAL, "oc_rollout_random: start.rnd_obj_prob_thresh must be in [0, 1] and its regen range within the table");
     const EvArgs ea = ev_args(events, nullptr);
-    if ((start || ev_on(ea)) && (options & (OC_OPT_LANE_PAIR | OC_OPT_PREDICATE_INTERACT)))
-        return fail(OC_EINVAL, "oc_rollout_random: drawn start states / event logging need the default kernel (k_rollout4)");
-    if (start && start->env_offset != env_offset) return fail(OC_EINVAL, "oc_rollout_random: start.env_offset differs from env_offset");
-    if (!d_state) return fail(OC_EINVAL, "oc_rollout_random: NULL state pointer");
-    if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_rollout_random: horizon must be in 1..65535");
-    if (n_steps < 0 || n_steps > (1 << 30)) return fail(OC_EINVAL, "oc_rollout_random: n_steps must be in 0..2^30");
-    const bool tiled8 = (options & OC_OPT_FLAGS_TILED8) != 0;
-    if (tiled8) {  // the launch-shape half of the option's conditions (the batch half: choose_rollout)
-        if (!d_rewards || !d_flags || ((uintptr_t)d_flags & 7u) != 0)
-            return fail(OC_EINVAL, "oc_rollout_random: OC_OPT_FLAGS_TILED8 needs d_rewards and an 8-byte aligned d_flags");
-        if ((t0 & 7) != 0 || (n_steps & 7) != 0)
-            return fail(OC_EINVAL, "oc_rollout_random: OC_OPT_FLAGS_TILED8 needs t0 and n_steps to be multiples of 8");
-        if (ea.events || (options & (OC_OPT_LANE_PAIR | OC_OPT_PREDICATE_INTERACT)))
-            return fail(OC_EINVAL, "oc_rollout_random: OC_OPT_FLAGS_TILED8 goes with the default kernel and no per-step event masks "
-                                   "(per-episode counters: the mover / interact kernel writes it)");
-    }
-    if (b->n_envs == 0 || n_steps == 0) return OC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const bool uniform = b->n_layouts == 1;
-    const bool lds = b->n_layouts <= LDS_LAYOUT_MAX;
-    const bool small = b->max_pots >= 1 && b->max_pots <= 2;
-    // Lane pairs (two lanes per env) halve the per-wavefront instruction stream at ~1.5x the total VALU work.  They
-    // used to win for batches that leave SIMDs without a wavefront (<= 32 768 envs); with the table-driven step built
-    // for ILP the lane-per-env kernel is faster at every batch size (us per batched step, lane vs pair, cramped_room:
-    // 0.55 vs 0.73 at 4 096 envs, 0.57 vs 0.76 at 32 768), so pairs run only when OC_OPT_LANE_PAIR asks for them.
-    const bool pair_ok = small && (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0;
-    const bool want_pair = (options & OC_OPT_LANE_PAIR) != 0;
-    if (pair_ok && want_pair) {
-        // two lanes per env (k_rollout_pair)
-        if (oc_detail::g_describe) { snprintf(oc_detail::g_describe, 256, "k_rollout_pair (OC_OPT_LANE_PAIR: two lanes per env)"); return OC_OK; }
-        const size_t smem2 = (size_t)n_obj * 8 * PAIR_ENVS * sizeof(uint32_t);
-        const dim3 grid2((unsigned)((b->n_envs + PAIR_ENVS - 1) / PAIR_ENVS)), block2(BLOCK);
-        if (uniform)
-            hipLaunchKernelGGL((k_rollout_pair<true, true>), grid2, block2, smem2, s, b->d_layouts, b->n_layouts,
-                               b->d_layout_id, (uint4*)d_state, (float4*)d_rewards, d_flags, (float4*)d_ep_returns,
-                               b->n_envs, b->width, n_obj, horizon, options, (uint32_t)seed, (uint32_t)(seed >> 32),
-                               env_offset, t0, n_steps);
-        else if (lds)
-            hipLaunchKernelGGL((k_rollout_pair<false, true>), grid2, block2, smem2, s, b->d_layouts, b->n_layouts,
-                               b->d_layout_id, (uint4*)d_state, (float4*)d_rewards, d_flags, (float4*)d_ep_returns,
-                               b->n_envs, b->width, n_obj, horizon, options, (uint32_t)seed, (uint32_t)(seed >> 32),
-                               env_offset, t0, n_steps);
-        else
-            hipLaunchKernelGGL((k_rollout_pair<false, false>), grid2, block2, smem2, s, b->d_layouts, b->n_layouts,
-                               b->d_layout_id, (uint4*)d_state, (float4*)d_rewards, d_flags, (float4*)d_ep_returns,
-                               b->n_envs, b->width, n_obj, horizon, options, (uint32_t)seed, (uint32_t)(seed >> 32),
-                               env_offset, t0, n_steps);
-        return check_launch("oc_rollout_random");
-    }
-    if ((options & OC_OPT_PREDICATE_INTERACT) == 0) {  // k_rollout4 / k_rollout5 (their instances are compiled in rollout4.hip)
-        const RolloutChoice ch = choose_rollout(b, n_obj, options, t0, n_steps, d_rewards != nullptr, d_flags != nullptr, ea, false);
-        if (ch.refusal) return fail(OC_EINVAL, ch.refusal);
-        if (ch.bulk > 0) {  // (see choose_rollout)
-            const int lens[3] = {ch.head, ch.bulk, n_steps - ch.head - ch.bulk};
-            int off = 0;
-            for (int part = 0; part < 3; ++part) {
-                const int len = lens[part];
-                if (len > 0 && !(oc_detail::g_describe && part != 1)) {
-                    OcStartSpec sk;
-                    if (start) { sk = *start; sk.epoch = start->epoch + (uint32_t)off; }  // a restart at step k draws from epoch + k
-                    const int rc = oc_rollout_random(b, d_state, d_rewards ? d_rewards + (int64_t)off * b->n_envs * 4 : nullptr,
-                                                     d_flags ? d_flags + (int64_t)off * b->n_envs : nullptr, d_ep_returns, horizon,
-                                                     options | (part == 1 ? 0u : (uint32_t)OC_OPT_ONE_WAVEFRONT), seed, env_offset, t0 + off, len,
-                                                     start ? &sk : nullptr, events, stream);
-                    if (rc) return rc;
-                }
-                off += len;
-            }
-            if (oc_detail::g_describe) {
-                const size_t used = strlen(oc_detail::g_describe);
-                snprintf(oc_detail::g_describe + used, 256 - used, "; %d + %d steps around the whole blocks: one-wavefront launches", lens[0], lens[2]);
-            }
-            return OC_OK;
-        }
-        oc_detail::Rollout4Call c;
-        c.b = b; c.n_obj = n_obj; c.d_state = d_state; c.d_rewards = d_rewards; c.d_flags = d_flags; c.d_ep_returns = d_ep_returns;
-        c.horizon = horizon; c.options = options; c.seed = seed; c.env_offset = env_offset; c.t0 = t0; c.n_steps = n_steps;
-        c.sa = sa; c.ea = ea; c.stream = s; c.r4 = ch.r4; c.r5 = ch.r5;
-        launch_rollout(c);
-        if (oc_detail::g_describe) return OC_OK;  // (oc_rollout_plan: nothing was launched)
-        return check_launch("oc_rollout_random");
-    }
-    if (oc_detail::g_describe) { snprintf(oc_detail::g_describe, 256, "k_rollout (OC_OPT_PREDICATE_INTERACT: the predicate-network interact)"); return OC_OK; }
-    const size_t smem = (size_t)n_obj * 8 * BLOCK * sizeof(uint32_t);
-    const dim3 grid(grid_for(b->n_envs)), block(BLOCK);
-#define GO(U, MP, LL)                                                                                       \
-    do {                                                                                                    \
-        if (!want_lds(k_rollout<U, MP, LL>, smem)) break;                                                   \
-        hipLaunchKernelGGL((k_rollout<U, MP, LL>), grid, block, smem, s, b->d_layouts, b->n_layouts,        \
-                           b->d_layout_id, (uint4*)d_state, (float4*)d_rewards, d_flags,                    \
-                           (float4*)d_ep_returns, b->n_envs, b->width, n_obj, horizon, options,             \
-                           (uint32_t)seed, (uint32_t)(seed >> 32), env_offset, t0, n_steps);                \
-    } while (0)
-    if (uniform) { if (small) GO(true, 2, true); else GO(true, 8, true); }
-    else GO(false, 8, false);
-#undef GO
+    const RolloutArrays have = {d_state != nullptr, d_rewards != nullptr, d_flags != nullptr, ((uintptr_t)d_flags & 7u) == 0,
+                                ea.events != nullptr, ea.counts != nullptr};
+    const RolloutPlan p = plan_rollout(b, have, horizon, options, env_offset, t0, n_steps, start);
+    if (p.rc != OC_OK || p.family == RolloutPlan::NOTHING) return p.rc;
+    const oc_detail::Rollout4Call c = {b, p.n_obj, d_state, d_rewards, d_flags, d_ep_returns, horizon, options, seed,
+                                       env_offset, t0, n_steps, p.sa, ea, (hipStream_t)stream, -1, {}};
+    if (p.family == RolloutPlan::LUT) return launch_rollout(p.parts, c, "oc_rollout_random");
+    if (p.family == RolloutPlan::PAIR) launch_rollout_pair(c);
+    else launch_rollout_predicate(c);
     return check_launch("oc_rollout_random");
 }
 
@@ -626,20 +655,26 @@ int oc_rollout_plan(const OcBatch* b, int horizon, uint32_t options, int64_t t0,
                     const OcStartSpec* start, char* out, size_t out_size) {
     if (!out || out_size == 0) return fail(OC_EINVAL, "oc_rollout_plan: no output buffer");
     out[0] = 0;
+    // the call oc_rollout_random would get: a state, both output arrays (8-byte aligned) or none, the named kind of event sink
+    const RolloutArrays have = {true, with_outputs != 0, with_outputs != 0, true, event_sink == 2, event_sink >= 1};
+    const RolloutPlan p = plan_rollout(b, have, horizon, options, start ? start->env_offset : 0, t0, n_steps, start);
+    if (p.rc != OC_OK) return p.rc;
     char buf[256] = "nothing to launch (no envs or no steps)";
-    // the call is made with stand-in pointers (the launch sites name their instance and launch nothing): every check of
-    // oc_rollout_random applies, every branch of its dispatch is the one a real call takes
-    void* const fake = reinterpret_cast<void*>((uintptr_t)4096);
-    OcEventSink sink;
-    sink.d_events = event_sink == 2 ? reinterpret_cast<uint64_t*>(fake) : nullptr;
-    sink.d_counts = event_sink >= 1 ? reinterpret_cast<uint32_t*>(fake) : nullptr;
-    sink.d_counts_done = nullptr;
-    oc_detail::g_describe = buf;
-    const int rc = oc_rollout_random(b, fake, with_outputs ? reinterpret_cast<float*>(fake) : nullptr,
-                                     with_outputs ? reinterpret_cast<uint8_t*>(fake) : nullptr, nullptr, horizon, options, 0, start ? start->env_offset : 0,
-                                     t0, n_steps, start, event_sink ? &sink : nullptr, nullptr);
-    oc_detail::g_describe = nullptr;
-    if (rc != OC_OK) return rc;
+    if (p.family == RolloutPlan::PAIR) snprintf(buf, sizeof(buf), "k_rollout_pair (OC_OPT_LANE_PAIR: two lanes per env)");
+    if (p.family == RolloutPlan::PREDICATE) snprintf(buf, sizeof(buf), "k_rollout (OC_OPT_PREDICATE_INTERACT: the predicate-network interact)");
+    if (p.family == RolloutPlan::LUT) {  // its unit names the instance; of a split call, that of the whole blocks
+        static void (*const unit[3])(const oc_detail::Rollout4Call&, char*, size_t) = {
+            oc_detail::describe_rollout<0>, oc_detail::describe_rollout<1>, oc_detail::describe_rollout<2>};
+        const bool split = p.parts.n == 3;
+        const RolloutChoice& ch = p.parts.part[split ? 1 : 0].ch;
+        oc_detail::Rollout4Call c = {};
+        c.b = b; c.n_obj = p.n_obj; c.r4 = ch.r4; c.r5 = ch.r5;
+        unit[rollout_unit(c)](c, buf, sizeof(buf));
+        const size_t used = strlen(buf);
+        if (split)
+            snprintf(buf + used, sizeof(buf) - used, "; %d + %d steps around the whole blocks: one-wavefront launches", p.parts.part[0].len,
+                     p.parts.part[2].len);
+    }
     snprintf(out, out_size, "%s", buf);
     return OC_OK;
 }
@@ -718,173 +753,209 @@ int oc_reset(const OcBatch* b, void* d_state, const uint8_t* d_mask, float* d_ep
     return check_launch("oc_reset");
 }
 
+}  // extern "C"
+
+namespace {
+// ---- oc_multi_agent_step: its arguments, checked, and its three paths
+struct TrainStep {
+    const OcBatch* b;
+    int n_obj;
+    void* d_state;
+    const uint8_t* d_actions;
+    float* d_rewards;
+    uint8_t* d_flags;
+    float *d_ep_returns, *d_ep_returns_out;
+    const uint8_t* d_plan_blob;  // the potential: plan tables, phi tables, phi(s'), phi(s), phi(start)
+    const uint32_t* d_plan_off;
+    const uint8_t* d_phi_tables;
+    double *d_phi_next, *d_phi_cur;
+    const double* d_phi_start;
+    double reward_shaping_factor, *d_shaped;
+    uint8_t* d_done;
+    void* d_obs;
+    int obs_dtype, horizon;
+    const OcStartSpec* start;
+    StartArgs sa;
+    EvArgs ea;
+    hipStream_t stream;
+};
+
+// How k_train_step_obs (train_obs.hpp) would run a call: envs per template, wavefronts per workgroup, envs per private image,
+// dynamic LDS.  nwv = 0: it does not apply.
+struct TrainObsShape {
+    int unit = 0, nwv = 0, gmax = 0;
+    size_t smem = 0;
+};
+// Round 5: the step AND its observation in one kernel for single-layout batches (at most two pots, two players, 64 cells, no
+// event sink) that give at least half of the CUs a workgroup of 256 envs (smaller batches: the observation kernel spreads
+// over all CUs)
+bool train_obs_wanted(const TrainStep& a) {
+    static const bool no_fused_obs = tuning_set("OC_TRAIN_NO_FUSED_OBS");
+    const OcBatch* b = a.b;
+    return a.d_obs && b->n_layouts == 1 && b->width * b->height <= 64 && !ev_on(a.ea) && a.n_obj <= STEP1_MAX_PLANES && !step_no_lean() &&
+           !no_fused_obs && obs_dtype_ok(a.obs_dtype) && aligned16(a.d_obs) && b->n_envs >= (simd_count() / 8) * BLOCK;
+}
+TrainObsShape train_obs_shape(const TrainStep& a) {
+    TrainObsShape sh;
+    if (!train_obs_wanted(a)) return sh;
+    const OcBatch* b = a.b;
+    const size_t elem = a.obs_dtype == OC_OBS_U8 ? 1 : 4;
+    const size_t env_bytes = (size_t)2 * b->width * b->height * OC_NUM_LAYERS * elem;
+    const int unit = envs_per_template(env_bytes);
+    const size_t fixed = (size_t)a.n_obj * BLOCK * 16 + env_bytes * unit + (size_t)4 * BLOCK * 16;
+    const size_t budget = 150 * 1024;
+    // wavefronts per workgroup: 16 (4 owners, 4 helpers, 8 encoders; round 6) for u8 observations whose private images
+    // still hold >= 6 envs then (cramped_room-sized grids: the encode loop there is bound by what the wavefronts of a
+    // CU can issue, not by bytes), else 8
+    static const int forced_w = tuning_int("OC_TRAIN_OBS_WAVES", 0), forced_g = tuning_int("OC_TRAIN_OBS_G", 0);
+    for (int w : {16, 8}) {
+        if (forced_w && w != forced_w) continue;
+        if (!forced_w && w == 16 && a.obs_dtype != OC_OBS_U8) continue;
+        int g = fixed < budget ? (int)((budget - fixed) / ((size_t)w * env_bytes)) : 0;
+        if (g > 64) g = 64;
+        if (forced_g > 0 && forced_g < g) g = forced_g;
+        g -= g % unit;
+        if (w == 16 && g < 6 && !forced_w) continue;  // (measured: 7-env images 22.0 -> 19.5 us, 3-env images 31.8 -> 37.6)
+        if (g >= unit && g >= 2) {  // (one env per image — 9x5 f32 — measured slower than the two kernels: 123-127 vs 116-122 us)
+            sh.unit = unit; sh.nwv = w; sh.gmax = g;
+            sh.smem = fixed + (size_t)w * g * env_bytes;
+            break;
+        }
+    }
+    return sh;
+}
+
+// path 1: the step and its observation in one kernel (k_train_step_obs)
+int train_step_obs(const TrainStep& a, const TrainObsShape& sh) {
+    const OcBatch* b = a.b;
+    const dim3 grid(grid_for(b->n_envs));
+#define GOTO(MP, T, NW)                                                                                                 \
+    do {                                                                                                                \
+        if (!want_lds(k_train_step_obs<MP, T, NW>, sh.smem)) break;                                                     \
+        hipLaunchKernelGGL((k_train_step_obs<MP, T, NW>), grid, dim3(NW * 64), sh.smem, a.stream, b->d_layouts,         \
+                           (uint4*)a.d_state, a.d_actions, (float4*)a.d_rewards, a.d_flags, (float4*)a.d_ep_returns,    \
+                           (float4*)a.d_ep_returns_out, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_phi_next,      \
+                           a.d_phi_cur, a.d_phi_start, a.reward_shaping_factor, a.d_shaped, a.d_done, (uint8_t*)a.d_obs, \
+                           b->n_envs, b->width, b->height, a.n_obj, a.horizon, sh.unit, sh.gmax, a.sa);                 \
+    } while (0)
+#define GOTOW(MP, T) do { if (sh.nwv == 16) GOTO(MP, T, 16); else GOTO(MP, T, 8); } while (0)
+    if (a.obs_dtype == OC_OBS_U8) { if (b->max_pots == 1) GOTOW(1, uint8_t); else GOTOW(2, uint8_t); }
+    else { if (b->max_pots == 1) GOTOW(1, float); else GOTOW(2, float); }
+#undef GOTOW
+#undef GOTO
+    return check_launch("oc_multi_agent_step");
+}
+
+// path 2: the whole step in one kernel (k_train_step1; k_train_step with event counters or a grid above 64 cells), then the
+// observation
+int train_step_fused(const TrainStep& a) {
+    const OcBatch* b = a.b;
+    if (b->n_envs > 0) {
+        const bool uniform = b->n_layouts == 1, lds = b->n_layouts <= LDS_LAYOUT_MAX;
+        const dim3 grid(grid_for(b->n_envs)), block(BLOCK);
+        if (!ev_on(a.ea) && a.n_obj <= STEP1_MAX_PLANES && !step_no_lean()) {  // the transition on the wire format itself (step_one.hpp)
+            const size_t smem1 = (size_t)a.n_obj * BLOCK * sizeof(uint4);
+#define GOT1(U, MP, LL)                                                                                                  \
+    hipLaunchKernelGGL((k_train_step1<U, MP, LL>), grid, block, smem1, a.stream, b->d_layouts, b->n_layouts, b->d_layout_id, \
+                       (uint4*)a.d_state, a.d_actions, (float4*)a.d_rewards, a.d_flags, (float4*)a.d_ep_returns,         \
+                       (float4*)a.d_ep_returns_out, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_phi_next,           \
+                       a.d_phi_cur, a.d_phi_start, a.reward_shaping_factor, a.d_shaped, a.d_done, b->n_envs, b->width,   \
+                       b->height, a.n_obj, a.horizon, a.sa)
+            if (uniform && b->max_pots == 1) GOT1(true, 1, true);
+            else if (uniform) GOT1(true, 2, true);
+            else if (lds) GOT1(false, 2, true);
+            else GOT1(false, 2, false);
+#undef GOT1
+        } else {
+            const size_t smem = (size_t)a.n_obj * 16 * BLOCK * sizeof(uint16_t);
+#define GOT(U, EV)                                                                                                    \
+    do {                                                                                                              \
+        if (!want_lds(k_train_step<U, 2, U, false, EV>, smem)) break;                                                 \
+        hipLaunchKernelGGL((k_train_step<U, 2, U, false, EV>), grid, block, smem, a.stream, b->d_layouts,             \
+                           b->n_layouts, b->d_layout_id, (uint4*)a.d_state, a.d_actions, (float4*)a.d_rewards,        \
+                           a.d_flags, (float4*)a.d_ep_returns, (float4*)a.d_ep_returns_out, a.d_plan_blob,            \
+                           a.d_plan_off, a.d_phi_tables, a.d_phi_next, a.d_phi_cur, a.d_phi_start,                    \
+                           a.reward_shaping_factor, a.d_shaped, a.d_done, b->n_envs, b->width, b->height, a.n_obj,    \
+                           a.horizon, a.sa, a.ea);                                                                    \
+    } while (0)
+            if (uniform) { if (ev_on(a.ea)) GOT(true, true); else GOT(true, false); }
+            else { if (ev_on(a.ea)) GOT(false, true); else GOT(false, false); }
+#undef GOT
+        }
+        if (int rc = check_launch("oc_multi_agent_step")) return rc;
+    }
+    if (a.d_obs) return oc_encode_lossless(b, a.d_state, a.d_obs, a.obs_dtype, a.horizon, a.stream);
+    return OC_OK;
+}
+
+// path 3, any table: oc_step (finished envs are restarted below: their counters clear at the DONE step), potential, shaping,
+// restart, observation
+int train_step_general(const TrainStep& a) {
+    const OcBatch* b = a.b;
+    if (b->n_envs > 0) {
+        StartArgs none;
+        start_args(nullptr, &none);
+        launch_step(b, a.n_obj, a.d_state, a.d_state, a.d_actions, a.d_rewards, a.d_flags, a.d_ep_returns, a.horizon, 0u, a.stream, none, a.ea);
+        if (int rc = check_launch("oc_multi_agent_step")) return rc;
+    }
+    if (a.d_phi_tables) {
+        if (int rc = oc_potential(b, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_state, a.d_phi_next, a.stream)) return rc;
+    }
+    if (int rc = oc_shape_rewards(b, a.d_rewards, a.d_flags, a.d_phi_tables ? a.d_phi_next : nullptr, a.d_phi_cur, a.d_phi_start,
+                                  a.reward_shaping_factor, a.d_shaped, a.d_done, a.stream))
+        return rc;
+    if (a.d_ep_returns && a.d_ep_returns_out && b->n_envs > 0) {
+        if (hipMemcpyAsync(a.d_ep_returns_out, a.d_ep_returns, (size_t)b->n_envs * 4 * sizeof(float), hipMemcpyDeviceToDevice,
+                           a.stream) != hipSuccess)
+            return fail(OC_ELAUNCH, "oc_multi_agent_step: copy of the episode returns failed");
+    }
+    if (const OcStartSpec* start = a.start) {  // finished envs restart from drawn states; d_phi_cur = the potential of what every env starts the next step from
+        if (start->regen_count && b->n_layouts > 1) {  // ... on layouts drawn for their new episodes
+            if (int rc = oc_regen_layouts(b, const_cast<uint16_t*>(b->d_layout_id), a.d_done, 0xFF, start, a.stream)) return rc;
+        }
+        if (int rc = oc_reset_random(b, a.d_state, a.d_done, a.d_ep_returns, start->seed, start->env_offset, start->epoch,
+                                     start->random_start_pos, start->rnd_obj_prob_thresh, a.stream))
+            return rc;
+        if (a.d_phi_tables) {
+            if (int rc = oc_potential(b, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_state, a.d_phi_cur, a.stream)) return rc;
+        }
+    } else {
+        if (int rc = oc_reset(b, a.d_state, a.d_done, a.d_ep_returns, a.stream)) return rc;
+    }
+    if (a.d_obs) return oc_encode_lossless(b, a.d_state, a.d_obs, a.obs_dtype, a.horizon, a.stream);
+    return OC_OK;
+}
+}  // namespace
+
+extern "C" {
+
 int oc_multi_agent_step(const OcBatch* b, void* d_state, const uint8_t* d_actions, float* d_rewards, uint8_t* d_flags,
                         float* d_ep_returns, float* d_ep_returns_out, const uint8_t* d_plan_blob,
                         const uint32_t* d_plan_off, const uint8_t* d_phi_tables, double* d_phi_next, double* d_phi_cur,
                         const double* d_phi_start, double reward_shaping_factor, double* d_shaped, uint8_t* d_done,
                         void* d_obs, int obs_dtype, int horizon, const OcStartSpec* start, const OcEventSink* events,
                         void* stream) {
-    if (!d_done) return fail(OC_EINVAL, "oc_multi_agent_step: d_done is required (it is the reset mask)");
-    StartArgs sa;
-    if (!start_args(start, &sa, b)) return fail(OC_EINVAL, "oc_multi_agent_step: start.rnd_obj_prob_thresh must be in [0, 1] and its regen range within the table");
-    const EvArgs ea = ev_args(events, nullptr, 1u);
-    {
-        int n_obj = 0;
-        if (int rc = check_batch(b, &n_obj)) return rc;
-        const bool fused = b->max_pots >= 1 && b->max_pots <= 2 && (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0;
-        if (fused) {  // the whole step in one kernel (k_train_step), then the observation
-            if (!d_state || !d_actions || !d_rewards || !d_flags || !d_shaped)
-                return fail(OC_EINVAL, "oc_multi_agent_step: NULL state/actions/rewards/flags/shaped pointer");
-            if (d_phi_tables && (!d_plan_blob || !d_plan_off || !d_phi_next || !d_phi_cur || !d_phi_start))
-                return fail(OC_EINVAL, "oc_multi_agent_step: use_phi needs the plan tables and the three phi buffers");
-            if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_multi_agent_step: horizon must be in 1..65535");
-            if (((uintptr_t)d_shaped & 15u) != 0) return fail(OC_EINVAL, "oc_multi_agent_step: d_shaped must be 16-byte aligned");
-            if (b->n_envs > 0) {
-                const bool uniform = b->n_layouts == 1, lds = b->n_layouts <= LDS_LAYOUT_MAX;
-                const bool fast = b->width * b->height <= 64;
-                const size_t smem = (size_t)n_obj * 16 * BLOCK * sizeof(uint16_t);
-                const dim3 grid(grid_for(b->n_envs)), block(BLOCK);
-#define GOT(U, MP, LL, F)                                                                                             \
-    do {                                                                                                              \
-        if (ev_on(ea)) { GOT_(U, MP, LL, F, true); } else { GOT_(U, MP, LL, F, false); }                              \
-    } while (0)
-#define GOT_(U, MP, LL, F, EV)                                                                                        \
-    do {                                                                                                              \
-        if (!want_lds(k_train_step<U, MP, LL, F, EV>, smem)) break;                                                   \
-        hipLaunchKernelGGL((k_train_step<U, MP, LL, F, EV>), grid, block, smem, (hipStream_t)stream, b->d_layouts,    \
-                           b->n_layouts, b->d_layout_id, (uint4*)d_state, d_actions, (float4*)d_rewards, d_flags,     \
-                           (float4*)d_ep_returns, (float4*)d_ep_returns_out, d_plan_blob, d_plan_off, d_phi_tables,   \
-                           d_phi_next, d_phi_cur, d_phi_start, reward_shaping_factor, d_shaped, d_done, b->n_envs,    \
-                           b->width, b->height, n_obj, horizon, sa, ea);                                              \
-    } while (0)
-#ifdef OC_AMD_TUNING
-                static const bool no_lean = getenv("OC_STEP_NO_LEAN") != nullptr;  // tuning builds: k_train_step always
-#else
-                constexpr bool no_lean = false;
-#endif
-                // Round 5: the step AND its observation in one kernel (train_obs.hpp) for single-layout batches that give at
-                // least half of the CUs a workgroup of 256 envs (smaller batches: the observation kernel below spreads over all CUs)
-#ifdef OC_AMD_TUNING
-                static const bool no_fused_obs = getenv("OC_TRAIN_NO_FUSED_OBS") != nullptr;
-#else
-                constexpr bool no_fused_obs = false;
-#endif
-                if (d_obs && uniform && fast && !ev_on(ea) && n_obj <= STEP1_MAX_PLANES && !no_lean && !no_fused_obs &&
-                    (obs_dtype == OC_OBS_U8 || obs_dtype == OC_OBS_F32) && ((uintptr_t)d_obs & 15u) == 0 &&
-                    b->n_envs >= (simd_count() / 8) * BLOCK) {
-                    const size_t elem = obs_dtype == OC_OBS_U8 ? 1 : 4;
-                    const size_t env_bytes = (size_t)2 * b->width * b->height * OC_NUM_LAYERS * elem;
-                    int unit = 1;
-                    while (((env_bytes * unit) & 15u) != 0) unit *= 2;  // 1, 2 or 4 envs per template
-                    const size_t fixed = (size_t)n_obj * BLOCK * 16 + env_bytes * unit + (size_t)4 * BLOCK * 16;
-                    const size_t budget = 150 * 1024;
-                    // wavefronts per workgroup: 16 (4 owners, 4 helpers, 8 encoders; round 6) for u8 observations whose private images
-                    // still hold >= 6 envs then (cramped_room-sized grids: the encode loop there is bound by what the wavefronts of a
-                    // CU can issue, not by bytes), else 8
-#ifdef OC_AMD_TUNING
-                    static const int forced_w = []() { const char* e = getenv("OC_TRAIN_OBS_WAVES"); return e ? atoi(e) : 0; }();
-                    static const int forced_g = []() { const char* e = getenv("OC_TRAIN_OBS_G"); return e ? atoi(e) : 0; }();
-#else
-                    constexpr int forced_w = 0, forced_g = 0;
-#endif
-                    int nwv = 0, gmax = 0;
-                    for (int w : {16, 8}) {
-                        if (forced_w && w != forced_w) continue;
-                        if (!forced_w && w == 16 && obs_dtype != OC_OBS_U8) continue;
-                        int g = fixed < budget ? (int)((budget - fixed) / ((size_t)w * env_bytes)) : 0;
-                        if (g > 64) g = 64;
-                        if (forced_g > 0 && forced_g < g) g = forced_g;
-                        g -= g % unit;
-                        if (w == 16 && g < 6 && !forced_w) continue;  // (measured: 7-env images 22.0 -> 19.5 us, 3-env images 31.8 -> 37.6)
-                        if (g >= unit && g >= 2) { nwv = w; gmax = g; break; }
-                    }
-                    if (nwv) {  // (one env per image — 9x5 f32 — measured slower than the two kernels: 123-127 vs 116-122 us)
-                        const size_t smem_o = fixed + (size_t)nwv * gmax * env_bytes;
-#define GOTO(MP, T, NW)                                                                                                 \
-    do {                                                                                                                \
-        if (!want_lds(k_train_step_obs<MP, T, NW>, smem_o)) break;                                                      \
-        hipLaunchKernelGGL((k_train_step_obs<MP, T, NW>), grid, dim3(NW * 64), smem_o, (hipStream_t)stream, b->d_layouts, \
-                           (uint4*)d_state, d_actions, (float4*)d_rewards, d_flags, (float4*)d_ep_returns,              \
-                           (float4*)d_ep_returns_out, d_plan_blob, d_plan_off, d_phi_tables, d_phi_next, d_phi_cur,     \
-                           d_phi_start, reward_shaping_factor, d_shaped, d_done, (uint8_t*)d_obs, b->n_envs, b->width,  \
-                           b->height, n_obj, horizon, unit, gmax, sa);                                                  \
-    } while (0)
-#define GOTOW(MP, T) do { if (nwv == 16) GOTO(MP, T, 16); else GOTO(MP, T, 8); } while (0)
-                        if (obs_dtype == OC_OBS_U8) { if (b->max_pots == 1) GOTOW(1, uint8_t); else GOTOW(2, uint8_t); }
-                        else { if (b->max_pots == 1) GOTOW(1, float); else GOTOW(2, float); }
-#undef GOTOW
-#undef GOTO
-                        return check_launch("oc_multi_agent_step");
-                    }
-                }
-                if (!ev_on(ea) && n_obj <= STEP1_MAX_PLANES && !no_lean) {  // the transition on the wire format itself (step_one.hpp)
-                    const size_t smem1 = (size_t)n_obj * BLOCK * sizeof(uint4);
-#define GOT1(U, MP, LL)                                                                                                \
-    hipLaunchKernelGGL((k_train_step1<U, MP, LL>), grid, block, smem1, (hipStream_t)stream, b->d_layouts, b->n_layouts, \
-                       b->d_layout_id, (uint4*)d_state, d_actions, (float4*)d_rewards, d_flags, (float4*)d_ep_returns,  \
-                       (float4*)d_ep_returns_out, d_plan_blob, d_plan_off, d_phi_tables, d_phi_next, d_phi_cur,         \
-                       d_phi_start, reward_shaping_factor, d_shaped, d_done, b->n_envs, b->width, b->height, n_obj,     \
-                       horizon, sa)
-                    if (uniform && b->max_pots == 1) GOT1(true, 1, true);
-                    else if (uniform) GOT1(true, 2, true);
-                    else if (lds) GOT1(false, 2, true);
-                    else GOT1(false, 2, false);
-#undef GOT1
-                }
-                // (k_train_step: event counters attached, or a grid above 64 cells)
-                else if (uniform) GOT(true, 2, true, false);
-                else GOT(false, 2, false, false);
-#undef GOT
-#undef GOT_
-                if (int rc = check_launch("oc_multi_agent_step")) return rc;
-            }
-            if (d_obs) return oc_encode_lossless(b, d_state, d_obs, obs_dtype, horizon, stream);
-            return OC_OK;
-        }
+    const char* const who = "oc_multi_agent_step";
+    if (!d_done) return refuse(who, "d_done is required (it is the reset mask)");
+    TrainStep a = {b, 0, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off, d_phi_tables,
+                   d_phi_next, d_phi_cur, d_phi_start, reward_shaping_factor, d_shaped, d_done, d_obs, obs_dtype, horizon, start,
+                   {}, ev_args(events, nullptr, 1u), (hipStream_t)stream};
+    if (int rc = check_start(who, start, &a.sa, b)) return rc;
+    if (int rc = check_batch(b, &a.n_obj)) return rc;
+    // at most two pots and two players: the whole step in one kernel
+    const bool fused = b->max_pots >= 1 && b->max_pots <= 2 && (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0;
+    if (!d_state || !d_actions || !d_rewards || !d_flags || (fused && !d_shaped))
+        return refuse(who, fused ? "NULL state/actions/rewards/flags/shaped pointer" : "NULL state/actions/rewards/flags pointer");
+    if (fused && d_phi_tables && (!d_plan_blob || !d_plan_off || !d_phi_next || !d_phi_cur || !d_phi_start))
+        return refuse(who, "use_phi needs the plan tables and the three phi buffers");
+    if (int rc = check_horizon(who, horizon)) return rc;
+    if (fused && !aligned16(d_shaped)) return refuse(who, "d_shaped must be 16-byte aligned");
+    if (!fused) return train_step_general(a);
+    if (b->n_envs > 0) {
+        const TrainObsShape sh = train_obs_shape(a);
+        if (sh.nwv) return train_step_obs(a, sh);
     }
-    {  // the general sequence: oc_step (finished envs are restarted below: their counters clear at the DONE step)
-        int n_obj = 0;
-        if (int rc = check_batch(b, &n_obj)) return rc;
-        if (!d_state || !d_actions || !d_rewards || !d_flags) return fail(OC_EINVAL, "oc_multi_agent_step: NULL state/actions/rewards/flags pointer");
-        if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_multi_agent_step: horizon must be in 1..65535");
-        if (b->n_envs > 0) {
-            StartArgs none;
-            start_args(nullptr, &none);
-            if (ev_on(ea))
-                launch_step<true>(b, n_obj, d_state, d_state, d_actions, d_rewards, d_flags, d_ep_returns, nullptr, horizon, 0u,
-                                  (hipStream_t)stream, none, ea);
-            else
-                launch_step<false>(b, n_obj, d_state, d_state, d_actions, d_rewards, d_flags, d_ep_returns, nullptr, horizon, 0u,
-                                   (hipStream_t)stream, none, ea);
-            if (int rc = check_launch("oc_multi_agent_step")) return rc;
-        }
-    }
-    if (d_phi_tables) {
-        if (int rc = oc_potential(b, d_plan_blob, d_plan_off, d_phi_tables, d_state, d_phi_next, stream)) return rc;
-    }
-    if (int rc = oc_shape_rewards(b, d_rewards, d_flags, d_phi_tables ? d_phi_next : nullptr, d_phi_cur, d_phi_start,
-                                  reward_shaping_factor, d_shaped, d_done, stream))
-        return rc;
-    if (d_ep_returns && d_ep_returns_out && b->n_envs > 0) {
-        if (hipMemcpyAsync(d_ep_returns_out, d_ep_returns, (size_t)b->n_envs * 4 * sizeof(float), hipMemcpyDeviceToDevice,
-                           (hipStream_t)stream) != hipSuccess)
-            return fail(OC_ELAUNCH, "oc_multi_agent_step: copy of the episode returns failed");
-    }
-    if (start) {  // finished envs restart from drawn states; d_phi_cur = the potential of what every env starts the next step from
-        if (start->regen_count && b->n_layouts > 1) {  // ... on layouts drawn for their new episodes
-            if (int rc = oc_regen_layouts(b, const_cast<uint16_t*>(b->d_layout_id), d_done, 0xFF, start, stream)) return rc;
-        }
-        if (int rc = oc_reset_random(b, d_state, d_done, d_ep_returns, start->seed, start->env_offset, start->epoch,
-                                     start->random_start_pos, start->rnd_obj_prob_thresh, stream))
-            return rc;
-        if (d_phi_tables) {
-            if (int rc = oc_potential(b, d_plan_blob, d_plan_off, d_phi_tables, d_state, d_phi_cur, stream)) return rc;
-        }
-    } else {
-        if (int rc = oc_reset(b, d_state, d_done, d_ep_returns, stream)) return rc;
-    }
-    if (d_obs) return oc_encode_lossless(b, d_state, d_obs, obs_dtype, horizon, stream);
-    return OC_OK;
+    return train_step_fused(a);
 }
 
 int oc_regen_layouts(const OcBatch* b, uint16_t* d_layout_id, const uint8_t* d_mask, uint8_t mask_bits, const OcStartSpec* start,
@@ -895,10 +966,10 @@ int oc_regen_layouts(const OcBatch* b, uint16_t* d_layout_id, const uint8_t* d_m
     if ((uint64_t)start->regen_first + start->regen_count > (uint64_t)b->n_layouts)
         return fail(OC_EINVAL, "oc_regen_layouts: regen_first + regen_count exceeds the layout table");
     if (b->n_envs == 0) return OC_OK;
-    StartArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.enabled = 1; sa.seed_lo = (uint32_t)start->seed; sa.seed_hi = (uint32_t)(start->seed >> 32); sa.epoch = start->epoch;
-    sa.env_offset = start->env_offset; sa.regen_first = start->regen_first; sa.regen_count = start->regen_count;
+    StartArgs sa;  // (the ids of the call, not the batch's; one layout is a range too: nothing else of the spec is read or checked)
+    start_keys(start, &sa);
+    sa.regen_first = start->regen_first;
+    sa.regen_count = start->regen_count;
     sa.layout_ids = d_layout_id;
     hipLaunchKernelGGL(k_regen_layouts, dim3(grid_for(b->n_envs)), dim3(BLOCK), 0, (hipStream_t)stream, d_layout_id, d_mask,
                        mask_bits, b->n_envs, sa);
@@ -924,8 +995,7 @@ int oc_encode_lossless(const OcBatch* b, const void* d_state, void* d_obs, int o
     int n_obj = 0;
     if (int rc = check_batch(b, &n_obj)) return rc;
     if (!d_state || !d_obs) return fail(OC_EINVAL, "oc_encode_lossless: NULL pointer");
-    if (obs_dtype != OC_OBS_U8 && obs_dtype != OC_OBS_F32) return fail(OC_EINVAL, "oc_encode_lossless: bad obs_dtype");
-    if (((uintptr_t)d_obs & 15u) != 0) return fail(OC_EINVAL, "oc_encode_lossless: d_obs must be 16-byte aligned");
+    if (int rc = check_obs("oc_encode_lossless", obs_dtype, d_obs)) return rc;
     if (b->n_envs == 0) return OC_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n_planes = 1 + n_obj;
@@ -946,8 +1016,7 @@ int oc_encode_lossless(const OcBatch* b, const void* d_state, void* d_obs, int o
     // asymmetric_advantages envs).  f32 is HBM-write bound either way: through the template kernel 5x4 grids gain when
     // encodes run back to back (43.5 vs 54.4 us) but not inside a training loop (43.5 vs 41.9 us), 9x5 is 112 us both ways
     if (b->n_layouts == 1 && obs_dtype == OC_OBS_U8) {
-        int unit = 1;
-        while (((env_bytes * unit) & 15u) != 0) unit *= 2;              // 1, 2 or 4 envs per template
+        const int unit = envs_per_template(env_bytes);
         const size_t unit_bytes = env_bytes * unit;
         int upg = (int)(enc_uniform_budget(env_bytes) / unit_bytes);     // units per group
         if (upg < 1) upg = 1;
@@ -990,11 +1059,10 @@ int oc_step_encode(const OcBatch* b, void* d_state, const uint8_t* d_actions, fl
     int n_obj = 0;
     if (int rc = check_batch(b, &n_obj)) return rc;
     if (!d_state || !d_actions || !d_rewards || !d_flags || !d_obs) return fail(OC_EINVAL, "oc_step_encode: NULL pointer");
-    if (obs_dtype != OC_OBS_U8 && obs_dtype != OC_OBS_F32) return fail(OC_EINVAL, "oc_step_encode: bad obs_dtype");
-    if (((uintptr_t)d_obs & 15u) != 0) return fail(OC_EINVAL, "oc_step_encode: d_obs must be 16-byte aligned");
-    if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_step_encode: horizon must be in 1..65535");
+    if (int rc = check_obs("oc_step_encode", obs_dtype, d_obs)) return rc;
+    if (int rc = check_horizon("oc_step_encode", horizon)) return rc;
     StartArgs sa;
-    if (!start_args(start, &sa, b)) return fail(OC_EINVAL, "oc_step_encode: start.rnd_obj_prob_thresh must be in [0, 1] and its regen range within the table");
+    if (int rc = check_start("oc_step_encode", start, &sa, b)) return rc;
     if (b->n_envs == 0) return OC_OK;
     if (!start && !(options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_KERNEL)))  // one kernel where that applies
         return oc_rollout_encode(b, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_obs, obs_dtype, 0, horizon, options,
@@ -1012,12 +1080,12 @@ int oc_rollout_encode(const OcBatch* b, void* d_state, const uint8_t* d_actions,
     int n_obj = 0;
     if (int rc = check_batch(b, &n_obj)) return rc;
     StartArgs sa;
-    if (!start_args(start, &sa, b)) return fail(OC_EINVAL, "oc_rollout_encode: start.rnd_obj_prob_thresh must be in [0, 1] and its regen range within the table");
+    if (int rc = check_start("oc_rollout_encode", start, &sa, b)) return rc;
     if (!d_state || !d_obs) return fail(OC_EINVAL, "oc_rollout_encode: NULL state / observation pointer");
-    if (obs_dtype != OC_OBS_U8 && obs_dtype != OC_OBS_F32) return fail(OC_EINVAL, "oc_rollout_encode: bad obs_dtype");
-    if (((uintptr_t)d_obs & 15u) != 0 || obs_step_stride < 0 || (obs_step_stride & 15) != 0)
+    if (!obs_dtype_ok(obs_dtype)) return fail(OC_EINVAL, "oc_rollout_encode: bad obs_dtype");
+    if (!aligned16(d_obs) || obs_step_stride < 0 || (obs_step_stride & 15) != 0)
         return fail(OC_EINVAL, "oc_rollout_encode: d_obs and obs_step_stride must be multiples of 16 bytes");
-    if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_rollout_encode: horizon must be in 1..65535");
+    if (int rc = check_horizon("oc_rollout_encode", horizon)) return rc;
     if (n_steps < 0 || n_steps > (1 << 30)) return fail(OC_EINVAL, "oc_rollout_encode: n_steps must be in 0..2^30");
     if (options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_KERNEL))
         return fail(OC_EINVAL, "oc_rollout_encode: options other than OC_OPT_AUTO_RESET / OC_OPT_ONE_KERNEL");
@@ -1037,8 +1105,7 @@ int oc_rollout_encode(const OcBatch* b, void* d_state, const uint8_t* d_actions,
     const bool fills_gpu = b->n_envs >= (simd_count() / 4) * 192 && n_steps >= 2;
     const uint32_t step_options = options & (uint32_t)OC_OPT_AUTO_RESET;
     if ((fills_gpu || (options & OC_OPT_ONE_KERNEL)) && b->n_layouts == 1 && b->max_pots >= 1 && b->max_pots <= 2 && n_obj <= 3) {
-        int unit = 1;
-        while (((env_bytes * unit) & 15u) != 0) unit *= 2;  // 1, 2 or 4 envs per template
+        const int unit = envs_per_template(env_bytes);
         const size_t cell_bytes = (size_t)n_obj * 16 * BLOCK * sizeof(uint16_t);
         const size_t fixed = cell_bytes + env_bytes * unit + (size_t)BLOCK * 16 + RE_LIST_BYTES;
         const bool fast = (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0 && cells <= 64;
@@ -1054,11 +1121,7 @@ int oc_rollout_encode(const OcBatch* b, void* d_state, const uint8_t* d_actions,
         // eight wavefronts (four of them helpers that only encode) when eight images of at least 8 envs fit: small grids,
         // where four wavefronts cannot encode 256 envs in the time HBM takes them (5x4 u8: 14.4 vs 17.4 us per step); 9x5
         // is at the write ceiling either way (30.1 vs 30.4 us), f32 loses with one-env images (128 vs 117 us)
-#ifdef OC_AMD_TUNING
-        static const int forced_nw = []() { const char* e = getenv("OC_ROLLOUT_ENCODE_WAVES"); return e ? atoi(e) : 0; }();  // tuning builds
-#else
-        constexpr int forced_nw = 0;
-#endif
+        static const int forced_nw = tuning_int("OC_ROLLOUT_ENCODE_WAVES", 0);
         // round 6: u8 observations take eight wavefronts down to 4-env images — a wavefront that is issuing its image's stores into a
         // busy store path is not building the next one, and eight of them leave the path idle less often (65 536 envs, us per step,
         // four vs eight: 9x5 29.2 -> 27.6-28.3, 8x5 26.1 -> 24.2, 5x5 16.1 -> 15.4; profiles/r06_rollout_encode_ablation.txt)
@@ -1076,10 +1139,8 @@ int oc_rollout_encode(const OcBatch* b, void* d_state, const uint8_t* d_actions,
             int g = (span + parts - 1) / parts;
             g = (g + unit - 1) / unit * unit;
             if (g > gmax) g = gmax / unit * unit;
-#ifdef OC_AMD_TUNING
-            static const int forced_reg = []() { const char* e = getenv("OC_ROLLOUT_ENCODE_G"); return e ? atoi(e) : 0; }();  // tuning builds
+            static const int forced_reg = tuning_int("OC_ROLLOUT_ENCODE_G", 0);
             if (forced_reg > 0 && forced_reg <= g && forced_reg % unit == 0) g = forced_reg;
-#endif
             const size_t smem = fixed + (size_t)nw * g * env_bytes;
             const dim3 grid(grid_for(b->n_envs));
 #define GORE(FAST, T, NW)                                                                                              \
@@ -1280,9 +1341,9 @@ int oc_step_server_open(const OcBatch* b, void* d_state, float* d_ep_returns, in
     *out = nullptr;
     if (int rc = check_batch(b, &n_obj)) return rc;
     StartArgs sa;
-    if (!start_args(start, &sa, b)) return fail(OC_EINVAL, "oc_step_server_open: start.rnd_obj_prob_thresh must be in [0, 1] and its regen range within the table");
+    if (int rc = check_start("oc_step_server_open", start, &sa, b)) return rc;
     if (!d_state) return fail(OC_EINVAL, "oc_step_server_open: NULL state pointer");
-    if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_step_server_open: horizon must be in 1..65535");
+    if (int rc = check_horizon("oc_step_server_open", horizon)) return rc;
     if (options & ~(uint32_t)OC_OPT_AUTO_RESET) return fail(OC_EINVAL, "oc_step_server_open: the only option is OC_OPT_AUTO_RESET");
     if (b->n_envs < 1) return fail(OC_EINVAL, "oc_step_server_open: no envs");
     if (!(idle_ms >= 0.0 && idle_ms <= 10000.0) || !(life_s >= 0.0 && life_s <= 86400.0))
@@ -1477,7 +1538,7 @@ int oc_mailbox_open(const OcBatch* b, int horizon, OcMailbox** out) {
     *out = nullptr;
     if (int rc = check_batch(b, &n_obj)) return rc;
     if (b->n_layouts != 1 || n_obj > STEP1_MAX_PLANES) return fail(OC_EINVAL, "oc_mailbox_open: one layout, grids of at most 64 cells");
-    if (horizon < 1 || horizon > 65535) return fail(OC_EINVAL, "oc_mailbox_open: horizon must be in 1..65535");
+    if (int rc = check_horizon("oc_mailbox_open", horizon)) return rc;
     OcMailbox* m = new OcMailbox();
     if (hipGetDevice(&m->device) != hipSuccess || hipHostMalloc((void**)&m->h, MB_BYTES, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
         delete m;
@@ -1549,6 +1610,17 @@ int oc_mailbox_step(OcMailbox* m) {
     return OC_OK;
 }
 
+int oc_mailbox_close(OcMailbox* m) {
+    if (!m) return OC_OK;
+    mailbox_post(m, MB_STOP, 16 * (1 + m->n_obj));
+    (void)hipStreamSynchronize(m->stream);
+    (void)hipStreamDestroy(m->stream);
+    (void)hipHostFree(m->h);
+    (void)hipGetLastError();
+    delete m;
+    return OC_OK;
+}
+
 #ifdef OC_AMD_TUNING
 // tuning builds: the phase stamps of the last k_train_step_obs launch (train_obs.hpp: g_obs_dbg), n_words u32
 int oc_debug_train_obs(uint32_t* out, int n_words) {
@@ -1583,17 +1655,6 @@ int oc_output_stores_only(int64_t n_envs, int n_steps, float* d_rewards, uint8_t
     hipLaunchKernelGGL(k_output_stores_only, dim3(grid_for(n_envs)), dim3(BLOCK), 0, (hipStream_t)stream, (float4*)d_rewards, d_flags,
                        n_envs, n_steps);
     return check_launch("oc_output_stores_only");
-}
-
-int oc_mailbox_close(OcMailbox* m) {
-    if (!m) return OC_OK;
-    mailbox_post(m, MB_STOP, 16 * (1 + m->n_obj));
-    (void)hipStreamSynchronize(m->stream);
-    (void)hipStreamDestroy(m->stream);
-    (void)hipHostFree(m->h);
-    (void)hipGetLastError();
-    delete m;
-    return OC_OK;
 }
 
 }  // extern "C"

@@ -21,9 +21,6 @@ namespace oc_detail {
 //  round 4 on the error paths of the rollout4 units)
 extern __thread char g_err[256] OC_HIDDEN;       // oc_last_error()
 extern __thread bool g_lds_refused OC_HIDDEN;    // a dynamic-LDS request was refused: nothing was launched
-// oc_rollout_plan: when set, the launch sites of oc_rollout_random write the kernel instance they would launch here (256 bytes)
-// and launch nothing
-extern __thread char* g_describe OC_HIDDEN;
 
 // Launch-time description of the start_state_fn (include/oc_amd.h, OcStartSpec), by value in kernel arguments.
 struct StartArgs {
@@ -213,8 +210,12 @@ struct Rollout4Call {
     R5Sel r5;
     RecArgs ra = {nullptr, nullptr, nullptr};  // oc_rollout_record / oc_rollout_record_ex: the recording outputs
 };
-// rollout4.hip, compiled with -DOC_R4_PART=UNIT (one explicit instantiation per unit): launches c's instance, which that unit compiles
+// rollout4.hip, compiled with -DOC_R4_PART=UNIT (one explicit instantiation of each per unit): launches c's instance, which that
+// unit compiles ...
 template <int UNIT> OC_HIDDEN void launch_rollout(const Rollout4Call& c);
+// ... or names it and its dynamic LDS in out (oc_rollout_plan: only the unit knows Lds4<P> / Lds5<>).  Reads c.b, c.n_obj, c.r4 and
+// c.r5; launches nothing.
+template <int UNIT> OC_HIDDEN void describe_rollout(const Rollout4Call& c, char* out, size_t out_size);
 OC_HIDDEN size_t rollout5_lds_bytes(bool lay_lds, bool big, bool ev, int n_obj);  // rollout4.hip, OC_R4_PART 1
 
 }  // namespace oc_detail

@@ -1,7 +1,7 @@
 """Which rollout kernel instance serves which batch: the host side of oc_rollout_plan (include/oc_amd.h, ABI 6).
 
-The answers come from oc_rollout_random's own dispatch walked with stand-in pointers (nothing is launched, no device memory is
-touched), so this works on a host without a GPU.  `table()` is what tools/gen_dispatch_table.py writes to docs/DISPATCH.md and
+The answers are the plan oc_rollout_random makes of a call before it launches anything, put into words (the planner holds no
+launch and no device pointer), so this works on a host without a GPU.  `table()` is what tools/gen_dispatch_table.py writes to docs/DISPATCH.md and
 what tests/test_dispatch_table.py compares that file with."""
 import ctypes
 
@@ -80,7 +80,7 @@ def table(names=None):
 def render(rows):
     out = ["# Rollout dispatch per layout (generated: `python tools/gen_dispatch_table.py`; checked by tests/test_dispatch_table.py)", "",
            "What `oc_rollout_random` launches for a batch of ONE registry layout, as `oc_rollout_plan` (include/oc_amd.h) reports it — the",
-           "library's own dispatch walked with stand-in pointers.  `k_rollout5` = mover + interact wavefronts (csrc/step_duo5.hpp);",
+           "plan the library makes of a call before it launches, in words.  `k_rollout5` = mover + interact wavefronts (csrc/step_duo5.hpp);",
            "`k_rollout4` = one wavefront per 64 envs (csrc/step_lut4.hpp: MODE 0 arithmetic movement, 1 joint move table, 2 floor mask).", "",
            "| layout | cells | pots | dynamics | " + " | ".join(t for t, _ in SHAPES) + " |", "|---|---|---|---|" + "---|" * len(SHAPES)]
     for name, cells, pots, old, cols in rows:

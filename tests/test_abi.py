@@ -109,6 +109,37 @@ def test_argument_validation_without_gpu():
     assert b"needs d_rewards" in L.oc_last_error()
     assert L.oc_rollout_random(br, 4096, 4096, 4096, None, 400, 0x45, 0, 0, 0, 16, None, None, None) == -1
     assert b"default kernel" in L.oc_last_error()
+    # every entry point with a horizon argument that it checks (oc_encode_lossless only passes it on; oc_mailbox_open has no
+    # empty-batch exit): out of range is refused by name, and before the empty-batch exit — a lost check would show as OC_OK here
+    e = _lib.OcBatch(d_layouts=4096, d_layout_id=None, n_envs=0, n_layouts=1, width=5, height=4, max_pots=1,
+                     batch_flags=_lib.BATCH_TWO_PLAYERS | _lib.BATCH_NEW_DYNAMICS)
+    er, P = ctypes.byref(e), 4096
+    rec = _lib.OcRecordSink(d_actions=P, d_states=P, d_layout_ids=None)
+    text, server = ctypes.create_string_buffer(320), ctypes.c_void_p()
+    for horizon in (0, 65536):
+        calls = {
+            "oc_step": lambda: L.oc_step(er, P, P, P, P, P, None, None, horizon, 0, None, None, None),
+            "oc_step_many": lambda: L.oc_step_many(er, P, P, P, P, None, 3, horizon, 0, None, None, None),
+            "oc_rollout_random": lambda: L.oc_rollout_random(er, P, P, P, None, horizon, 1, 0, 0, 0, 8, None, None, None),
+            "oc_rollout_record": lambda: L.oc_rollout_record(er, P, P, P, None, None, None, horizon, 1, 0, 0, 0, 8, None, None),
+            "oc_rollout_record_ex": lambda: L.oc_rollout_record_ex(er, P, ctypes.byref(rec), None, None, None, horizon, 1, 0, 0, 0, 8,
+                                                                   None, None, None),
+            "oc_step_encode": lambda: L.oc_step_encode(er, P, P, P, P, None, P, 0, horizon, 1, None, None),
+            "oc_rollout_encode": lambda: L.oc_rollout_encode(er, P, None, None, None, None, P, 0, 0, horizon, 1, 0, 0, 0, 3, None, None),
+            "oc_multi_agent_step": lambda: L.oc_multi_agent_step(er, P, P, P, P, None, None, None, None, None, None, None, None, 1.0, P,
+                                                                 P, None, 0, horizon, None, None, None),
+            "oc_step_server_open": lambda: L.oc_step_server_open(er, P, None, horizon, 1, None, 0.0, 0.0, ctypes.byref(server)),
+        }
+        for name, call in calls.items():
+            assert call() == -1, (name, horizon)
+            assert L.oc_last_error().decode() == name + ": horizon must be in 1..65535", (name, horizon)
+        # (the plan of a rollout is oc_rollout_random's: so is the name in its refusals)
+        assert L.oc_rollout_plan(er, horizon, 1, 0, 8, 1, 0, None, text, len(text)) == -1
+        assert L.oc_last_error().decode() == "oc_rollout_random: horizon must be in 1..65535"
+        # ... and the general sequence of oc_multi_agent_step (a table of more than two pots) checks it too
+        e.max_pots = 3
+        assert calls["oc_multi_agent_step"]() == -1 and L.oc_last_error().decode() == "oc_multi_agent_step: horizon must be in 1..65535"
+        e.max_pots = 1
     # the measurement aid: argument checks before the launch, nothing to do for an empty job
     assert L.oc_output_stores_only(64, 8, None, None, 0, None) == -1 and b"no rewards array" in L.oc_last_error()
     assert L.oc_output_stores_only(64, 8, 4100, None, 0, None) == -1 and b"16-byte aligned" in L.oc_last_error()

@@ -1,5 +1,5 @@
 """docs/DISPATCH.md (which rollout kernel instance serves which registry layout) must be what the library's own dispatch answers
-through oc_rollout_plan — no GPU needed: the dispatch is walked with stand-in pointers and nothing is launched."""
+through oc_rollout_plan — no GPU needed: the library plans a call before it launches anything, and the plan is all that is asked for."""
 import os
 
 import pytest
