@@ -156,8 +156,11 @@ def test_config4_4096_generated_terrains(kernel, gpu):
 
 def test_big_batch_variant_of_the_rollout_kernel(gpu):
     """More than ~1.5 wavefronts per SIMD (here 131 072 cramped_room envs) selects k_rollout4's lean instance (no
-    one-step-ahead cell reads, cooking starts in the rare branch): same results as the oracle across a restart."""
-    from overcooked_ai_amd.layouts import spec_from_name
+    one-step-ahead cell reads, cooking starts in the rare branch) where the mover / interact kernel does not take the batch —
+    here because 100 steps are not whole 8-step blocks, which the planner's answer is asked for: same results as the oracle
+    across a restart."""
+    import rollout_cases as RC
+    from overcooked_ai_amd.layouts import LayoutTable, spec_from_name
     from overcooked_ai_amd.vec_env import VecOvercookedEnv
 
     n = 131072
@@ -169,6 +172,7 @@ def test_big_batch_variant_of_the_rollout_kernel(gpu):
     T = 100
     rew = torch.zeros((T, n, 4), dtype=torch.float32, device=gpu)
     fl = torch.zeros((T, n), dtype=torch.uint8, device=gpu)
+    assert RC.plan_of(LayoutTable([spec]), n, T, 0, 70).startswith(RC.R4["R4JointLean"])
     env.rollout_random(T, rew, fl)
     rew_o, fl_o = orc.rollout_random(st, T, horizon=70, options=1, seed=9, ep_returns=ep_o)
     assert np.array_equal(env.get_packed_state(), st) and np.array_equal(fl.cpu().numpy(), fl_o)

@@ -1,7 +1,8 @@
 """GPU parity at the shapes that actually launch: the 4 000-step launch `bench.py` times — ten episodes
 per launch, nine in-kernel restarts plus the one at the last step — and the per-env-terrain instances BASELINE
-configs[3] / configs[4] put on EACH of 8 GPUs (65 536 and 131 072 envs per GPU; `k_rollout4` MODE 0, layout table in LDS
-or read through L2, global env offset of an inner rank), compared with the C oracle (pinned to the reference by
+configs[3] / configs[4] put on EACH of 8 GPUs (65 536 and 131 072 envs per GPU; layout table in LDS or read through L2,
+global env offset of an inner rank), and every instance `oc_rollout_random` can launch (tests/rollout_cases.py), compared with
+the C oracle (pinned to the reference by
 tests/test_oracle_golden.py): every reward quad and flag byte of every env-step, the final packed states and the
 episode returns, bit for bit.  The oracle runs in 400-step chunks to bound host memory."""
 import os
@@ -9,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import rollout_cases as RC
 from helpers import CANONICAL_5
 
 pytestmark = pytest.mark.gpu
@@ -34,77 +36,109 @@ def _oracle(specs):
     return O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in specs])
 
 
+def _first_difference(got, want, lid, c0=0):
+    """'; first at (step, env, ...) on layout L: got x, oracle y' for two arrays [steps or planes][envs]..., for an assertion's message"""
+    bad = np.argwhere(np.asarray(got) != np.asarray(want))
+    if len(bad) == 0:
+        return ""
+    i = tuple(bad[0])
+    return "; %d values differ, first at (step or plane, env, ...) %s on layout %d: got %s, oracle %s" % (
+        len(bad), [int(i[0]) + c0] + [int(v) for v in i[1:]], 0 if lid is None else int(lid[i[1]]), got[i], want[i])
+
+
+def _packed_counters(t):
+    """[n_envs, 25] int32, player 0 in the low half-word -> [n_envs, 25, 2]"""
+    c = t.cpu().numpy().astype(np.int64)
+    return np.stack([c & 0xFFFF, (c >> 16) & 0xFFFF], -1)
+
+
 def _long_launch_against_oracle(gpu, table, n, lid=None, env_offset=0, seed=0, steps=T, horizon=HORIZON, start=None,
-                                flags_tiled8=False, one_wavefront=False, expect_shaped=True, **env_kw):
+                                flags_tiled8=False, one_wavefront=False, expect_shaped=True, t0=0, outputs=True, events=0,
+                                regen_layout=False, expect=None, **env_kw):
     """flags_tiled8: the launch writes the OC_OPT_FLAGS_TILED8 layout (the instances bench.py times), untiled before the
-    comparison; one_wavefront: OC_OPT_ONE_WAVEFRONT (no mover / interact split where the batch would get it)."""
+    comparison; one_wavefront: OC_OPT_ONE_WAVEFRONT (no mover / interact split where the batch would get it); t0: the launch's
+    first global step; outputs=False: no rewards / flags arrays — states, returns and counters are compared all the same;
+    events: 1 per-episode counters (running and published), 2 also the per-step masks, against the popcounts of the oracle's
+    event_infos; regen_layout: every restart re-draws the env's layout, the ids are compared; expect: the instance
+    oc_rollout_plan must name for exactly this call, asked on this device before the launch."""
     from overcooked_ai_amd.vec_env import VecOvercookedEnv
 
     env = VecOvercookedEnv(table, n, horizon=horizon, device=gpu, auto_reset=True, seed=seed, env_offset=env_offset,
-                           layout_id=lid, **env_kw)
+                           layout_id=lid, track_events=events > 0, regen_layout=regen_layout, **env_kw)
     env.one_wavefront = one_wavefront
-    orc = _oracle(env.table.specs)
-    rew = torch.zeros((steps, n, 4), dtype=torch.float32, device=gpu)
-    fl = torch.zeros((steps // 8, n, 8) if flags_tiled8 else (steps, n), dtype=torch.uint8, device=gpu)
-    st = env.get_packed_state().copy()
-    st_o = orc.reset(orc.new_state(n), layout_id=lid)
-    if start is None:
-        assert np.array_equal(st, st_o)
-    else:
-        st_o = st
-    env.rollout_random(steps, rew, fl, flags_tiled8=flags_tiled8)  # ONE launch
+    env.t_global = t0
+    assert bool(start) == env.random_starts, "start must name the env's own start_state_fn keywords"
+    if expect is not None:
+        plan = RC.plan_of(env.table, n, steps, t0, horizon, tiled=flags_tiled8, one_wavefront=one_wavefront, outputs=outputs,
+                       events=events, start=start, regen=env.regen, seed=seed, env_offset=env_offset, epoch=env.reset_epoch)
+        assert plan.startswith(expect), "this launch is planned as\n  %s\nnot as\n  %s" % (plan, expect)
+    run = RC.OracleLaunch(env.table.specs, n, layout_id=lid, seed=seed, env_offset=env_offset, horizon=horizon, start=start,
+                       regen=env.regen, events=events > 0)
+    rew = torch.zeros((steps, n, 4), dtype=torch.float32, device=gpu) if outputs else None
+    fl = torch.zeros((steps // 8, n, 8) if flags_tiled8 else (steps, n), dtype=torch.uint8, device=gpu) if outputs else None
+    ev = torch.zeros((steps, n), dtype=torch.int64, device=gpu) if events == 2 else None
+    assert np.array_equal(env.get_packed_state(), run.state), "first states differ"
+    epoch = env.reset_epoch
+    env.rollout_random(steps, rew, fl, events_out=ev, flags_tiled8=flags_tiled8)  # ONE call
     if flags_tiled8:
         fl = VecOvercookedEnv.untile_flags(fl)
-    ep_o = np.zeros((n, 4), np.float32)
     restarts = shaped = sparse = 0
-    for c0 in range(0, steps, 400):
-        k = min(400, steps - c0)
-        sp = None
-        if start is not None:
-            from oracle import oracle as O
-
-            sp = O.start_spec(seed=seed, env_offset=env_offset, epoch=1 + c0, **start)
-        rew_o, fl_o = orc.rollout_random(st_o, k, horizon=horizon, options=1, seed=seed, env_offset=env_offset, t0=c0,
-                                         layout_id=lid, ep_returns=ep_o, start=sp)
-        assert np.array_equal(fl[c0:c0 + k].cpu().numpy(), fl_o), "flags differ in steps %d..%d" % (c0, c0 + k)
-        assert np.array_equal(rew[c0:c0 + k].cpu().numpy(), rew_o), "rewards differ in steps %d..%d" % (c0, c0 + k)
+    for c0, rew_o, fl_o, masks_o in run.chunks(steps, t0=t0, epoch=epoch):
+        k = len(fl_o)
+        if outputs:
+            got_fl, got_rew = fl[c0:c0 + k].cpu().numpy(), rew[c0:c0 + k].cpu().numpy()
+            assert np.array_equal(got_fl, fl_o), "flags differ in steps %d..%d%s" % (c0, c0 + k, _first_difference(got_fl, fl_o, lid, c0))
+            assert np.array_equal(got_rew, rew_o), "rewards differ in steps %d..%d%s" % (c0, c0 + k, _first_difference(got_rew, rew_o, lid, c0))
+        if ev is not None:
+            got_ev = ev[c0:c0 + k].cpu().numpy().view(np.uint64)
+            assert np.array_equal(got_ev, masks_o), "event masks differ in steps %d..%d%s" % (c0, c0 + k, _first_difference(got_ev, masks_o, lid, c0))
         restarts += int(((fl_o & 4) != 0).sum())
         sparse += float(rew_o[..., :2].sum())
         shaped += float(rew_o[..., 2:].sum())
-    assert np.array_equal(env.get_packed_state(), st_o), "final states differ"
-    assert np.array_equal(env.ep_returns.cpu().numpy(), ep_o), "episode returns differ"
+    if env.regen is not None:
+        assert np.array_equal(env.layout_ids(), run.layout_id), "layout ids differ" + _first_difference(env.layout_ids()[None], run.layout_id[None], None)
+    got_st = env.get_packed_state()
+    assert np.array_equal(got_st, run.state), "final states differ" + _first_difference(got_st, run.state, lid)
+    got_ep = env.ep_returns.cpu().numpy()
+    assert np.array_equal(got_ep, run.ep_returns), "episode returns differ" + _first_difference(got_ep[None], run.ep_returns[None], lid)
+    if events:
+        got_c, got_d = _packed_counters(env.event_counts), _packed_counters(env.event_counts_done)
+        assert np.array_equal(got_c, run.counts), "running event counters differ" + _first_difference(got_c[None], run.counts[None], lid)
+        assert np.array_equal(got_d, run.counts_done), "published event counters differ" + _first_difference(got_d[None], run.counts_done[None], lid)
+        assert run.counts_done.sum() > 0
     assert restarts == n * (steps // horizon) and (shaped > 0 or not expect_shaped)
     return sparse, shaped
 
 
 def test_bench_launch_shape_cramped_room_65536_x_4000(gpu):
     """Exactly bench.py's launch: 65 536 cramped_room envs from the standard start, seed 0, horizon 400, auto-reset,
-    4 000 fused steps (k_rollout4, joint move table, one-step-ahead cell reads)."""
-    sparse, _ = _long_launch_against_oracle(gpu, "cramped_room", 65536)
+    4 000 fused steps (whole workgroups in one round: k_rollout5, table in LDS)."""
+    sparse, _ = _long_launch_against_oracle(gpu, "cramped_room", 65536, expect=RC.r5())
     assert sparse > 0  # soups were delivered somewhere in 262 M env-steps
 
 
 def test_config4_launch_shape_131072_generated_terrains_inner_rank(gpu):
     """BASELINE configs[4] as rank 3 of 8 launches it: 131 072 envs per GPU, the reference LayoutGenerator's 4 096 terrains
-    (global env e -> terrain e % 4096, table read through L2), global env offset 3 x 131 072, 4 000 fused steps."""
+    (global env e -> terrain e % 4096, table read through L2: k_rollout5 in two rounds), global env offset 3 x 131 072, 4 000
+    fused steps."""
     from overcooked_ai_amd.layout_gen import reference_generated_layouts
     from overcooked_ai_amd.layouts import LayoutTable
 
     n, K, rank = 131072, 4096, 3
     table = LayoutTable(reference_generated_layouts(K))
     lid = ((np.arange(n) + rank * n) % K).astype(np.uint16)
-    _long_launch_against_oracle(gpu, table, n, lid=lid, env_offset=rank * n)
+    _long_launch_against_oracle(gpu, table, n, lid=lid, env_offset=rank * n, expect=RC.r5(LAY_LDS=False))
 
 
 def test_config3_launch_shape_five_layout_mix_65536_x_4000(gpu):
     """BASELINE configs[3] as rank 5 of 8 launches it: 65 536 envs per GPU, the five canonical layouts padded to 9x5
-    (global env e -> layout e % 5, table staged in LDS), 4 000 fused steps."""
+    (global env e -> layout e % 5, table staged in LDS: k_rollout5), 4 000 fused steps."""
     from overcooked_ai_amd.layouts import LayoutTable, spec_from_name
 
     n, rank = 65536, 5
     table = LayoutTable([spec_from_name(nm) for nm in CANONICAL_5], pad_to=(9, 5))
     lid = ((np.arange(n) + rank * n) % 5).astype(np.uint16)
-    sparse, _ = _long_launch_against_oracle(gpu, table, n, lid=lid, env_offset=rank * n)
+    sparse, _ = _long_launch_against_oracle(gpu, table, n, lid=lid, env_offset=rank * n, expect=RC.r5())
     assert sparse > 0
 
 
@@ -118,20 +152,22 @@ def _mix_table_and_ids(n, rank):
 @pytest.mark.parametrize("shape", ["cramped_room_65536", "five_layout_mix_65536", "generated_4096_131072",
                                    "cramped_room_131072_two_rounds", "five_layout_mix_196608_three_rounds"])
 def test_tiled_flags_launch_shapes_against_oracle(shape, gpu):
-    """The OC_OPT_FLAGS_TILED8 instances — the ones every number of bench.py's default line is timed on (headline: joint-table
-    kernel; configs[3]: the mover / interact kernel on the 5-layout mix; configs[4]: the one-pot per-env-terrain kernel at
-    131 072 envs) — against the ORACLE at exactly those launch shapes: 4 000 fused steps, flags untiled, every reward quad and
+    """The OC_OPT_FLAGS_TILED8 instances — the ones every number of bench.py's default line is timed on: the mover / interact
+    kernel with tiled flags (headline: cramped_room, table in LDS; configs[3]: the 5-layout mix, table in LDS; configs[4]: the
+    4 096 terrains read through L2, 131 072 envs in two rounds), each asked of oc_rollout_plan — against the ORACLE at exactly those launch shapes: 4 000 fused steps, flags untiled, every reward quad and
     flag byte, final states, episode returns (VERDICT r4 #3: they used to be compared with their [step][env] siblings only)."""
     if shape == "cramped_room_65536":
-        sparse, _ = _long_launch_against_oracle(gpu, "cramped_room", 65536, flags_tiled8=True)
+        sparse, _ = _long_launch_against_oracle(gpu, "cramped_room", 65536, flags_tiled8=True, expect=RC.r5(FT8=True))
     elif shape == "cramped_room_131072_two_rounds":  # (round 5: the mover / interact workgroups of a bigger batch run in rounds of one per CU)
-        sparse, _ = _long_launch_against_oracle(gpu, "cramped_room", 131072, flags_tiled8=True, steps=400)
+        sparse, _ = _long_launch_against_oracle(gpu, "cramped_room", 131072, flags_tiled8=True, steps=400, expect=RC.r5(FT8=True))
     elif shape == "five_layout_mix_196608_three_rounds":
         table, lid = _mix_table_and_ids(196608, 1)
-        sparse, _ = _long_launch_against_oracle(gpu, table, 196608, lid=lid, env_offset=196608, flags_tiled8=True, steps=400)
+        sparse, _ = _long_launch_against_oracle(gpu, table, 196608, lid=lid, env_offset=196608, flags_tiled8=True, steps=400,
+                                                expect=RC.r5(FT8=True))
     elif shape == "five_layout_mix_65536":
         table, lid = _mix_table_and_ids(65536, 5)
-        sparse, _ = _long_launch_against_oracle(gpu, table, 65536, lid=lid, env_offset=5 * 65536, flags_tiled8=True)
+        sparse, _ = _long_launch_against_oracle(gpu, table, 65536, lid=lid, env_offset=5 * 65536, flags_tiled8=True,
+                                                expect=RC.r5(FT8=True))
     else:
         from overcooked_ai_amd.layout_gen import reference_generated_layouts
         from overcooked_ai_amd.layouts import LayoutTable
@@ -139,7 +175,7 @@ def test_tiled_flags_launch_shapes_against_oracle(shape, gpu):
         n, K, rank = 131072, 4096, 3
         lid = ((np.arange(n) + rank * n) % K).astype(np.uint16)
         sparse, _ = _long_launch_against_oracle(gpu, LayoutTable(reference_generated_layouts(K)), n, lid=lid, env_offset=rank * n,
-                                                flags_tiled8=True)
+                                                flags_tiled8=True, expect=RC.r5(LAY_LDS=False, FT8=True))
     assert sparse > 0
 
 
@@ -183,7 +219,7 @@ def test_mover_interact_split_against_oracle(layout, tiled, gpu):
     b = _long_launch_against_oracle(gpu, table, n, one_wavefront=True, **kw,
                                     flags_tiled8=tiled and lid is not None and not layout.endswith("_old") and layout != "big_mix")
     assert a == b
-    # standard start states, a launch that begins in the middle of an episode (t0 = 96 from the env's own counter)
+    # standard start states, a longer launch: one restart, at step 400 of 416
     _long_launch_against_oracle(gpu, table, n, lid=lid, env_offset=rank * n, seed=3, steps=416, horizon=HORIZON, flags_tiled8=tiled,
                                 expect_shaped=layout != "corridor")
 
@@ -230,11 +266,26 @@ def test_mover_interact_split_with_layouts_redrawn_at_every_restart(table_kind, 
 
 
 def test_long_launch_with_drawn_start_states_131072(gpu):
-    """The big-batch (lean) joint-table instance with the env's start_state_fn drawn inside the fused auto-reset:
-    131 072 cramped_room envs, 2 000 steps = five restarts per env, each from a state drawn with its own epoch."""
-    _long_launch_against_oracle(gpu, "cramped_room", 131072, seed=5, steps=2000,
-                                start={"random_start_pos": True, "rnd_obj_prob_thresh": 0.4},
-                                random_start_pos=True, rnd_obj_prob_thresh=0.4)
+    """The env's start_state_fn drawn inside the fused auto-reset: 131 072 cramped_room envs, 2 000 steps = five restarts per env,
+    each from a state drawn with its own epoch — on the mover / interact kernel in two rounds (what whole workgroups get), and
+    with OC_OPT_ONE_WAVEFRONT on the big-batch (lean) joint-table instance."""
+    kw = dict(seed=5, steps=2000, start={"random_start_pos": True, "rnd_obj_prob_thresh": 0.4}, random_start_pos=True,
+              rnd_obj_prob_thresh=0.4)
+    _long_launch_against_oracle(gpu, "cramped_room", 131072, expect=RC.r5(), **kw)
+    _long_launch_against_oracle(gpu, "cramped_room", 131072, one_wavefront=True, expect=RC.R4["R4JointLean"], **kw)
+
+
+@pytest.mark.parametrize("case", RC.CASES, ids=lambda c: c.id)
+def test_every_rollout_instance_against_oracle(case, gpu):
+    """Every instance oc_rollout_random can launch (tests/rollout_cases.py: one case or more per k_rollout4 / k_rollout5 instance,
+    held to the planner and to the sources' lists by tests/test_host_rollout_instances.py), each asked of oc_rollout_plan on this
+    device before it runs, against the oracle: first states, every reward quad and flag byte, event masks and counters, re-drawn
+    layout ids, final states, episode returns — with or without output arrays."""
+    start = None if case.start == "standard" else RC.DRAWN
+    _long_launch_against_oracle(gpu, RC.table_of(case.table), case.n_envs, lid=RC.layout_ids(case), env_offset=case.env_offset,
+                                seed=case.seed, steps=case.n_steps, horizon=case.horizon, start=start, flags_tiled8=case.tiled,
+                                one_wavefront=case.one_wavefront, t0=case.t0, outputs=case.outputs, events=case.events,
+                                regen_layout=case.start == "regen", expect=case.expect, **(start or {}))
 
 
 @pytest.mark.parametrize("table_kind", ["generated_4096", "canonical_5"])

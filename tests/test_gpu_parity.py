@@ -1261,16 +1261,18 @@ def test_rollout_with_observations_edge_sizes(gpu):
 
 @pytest.mark.gpu
 def test_rollout_random_with_flags_tiled_by_8_steps(gpu):
-    """OC_OPT_FLAGS_TILED8: flags[k // 8][e][k % 8] from the pipelined joint-table kernel == the [step][env] flags of the
-    default call, rewards / states / episode returns identical, across in-kernel restarts and a second launch that starts at
-    step 16; launches that are not whole 8-step blocks and batches other kernels serve are refused."""
+    """OC_OPT_FLAGS_TILED8: flags[k // 8][e][k % 8] from the pipelined joint-table kernel (ragged batches: whole 256-env
+    workgroups go to the mover / interact kernel) == the [step][env] flags of the default call, rewards / states / episode returns
+    identical, across in-kernel restarts and a second launch that starts at step 16; the instance of every tiled launch is the
+    one oc_rollout_plan names; launches that are not whole 8-step blocks and batches other kernels serve are refused."""
+    import rollout_cases as RC
     from overcooked_ai_amd import _lib
     from overcooked_ai_amd.layouts import LayoutTable, spec_from_name
     from overcooked_ai_amd.vec_env import VecOvercookedEnv
 
     table = LayoutTable([spec_from_name("cramped_room")])
     rng = np.random.default_rng(41)
-    for n, horizon in ((1000, 20), (4096, 400), (65536, 12)):
+    for n, horizon in ((1000, 20), (4096 + 64, 400), (65536 + 64, 12)):
         st = random_packed_states(table.specs[0], n, rng, timestep_max=min(horizon - 1, 9))
         a = make_env(table, n, gpu, horizon=horizon, auto_reset=True, seed=11)
         b = make_env(table, n, gpu, horizon=horizon, auto_reset=True, seed=11)
@@ -1281,19 +1283,22 @@ def test_rollout_random_with_flags_tiled_by_8_steps(gpu):
             rew_b = torch.zeros_like(rew_a)
             fl_a = torch.full((K // 8, n, 8), 0x55, dtype=torch.uint8, device=gpu)
             fl_b = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
+            assert RC.plan_of(table, n, K, a.t_global, horizon, tiled=True).startswith(RC.R4["R4JointTiled"]), (n, horizon, K)
             a.rollout_random(K, rew_a, fl_a, flags_tiled8=True)
             b.rollout_random(K, rew_b, fl_b)
             assert torch.equal(VecOvercookedEnv.untile_flags(fl_a), fl_b), (n, horizon, K)
             assert torch.equal(rew_a, rew_b) and torch.equal(a.state, b.state) and torch.equal(a.ep_returns, b.ep_returns), (n, horizon, K)
             assert int((fl_b & 1).sum()) > 0 or horizon == 400  # (episode ends are inside the launches)
     # the per-env-terrain instances that write the tiled array: the 5-layout mix (table in LDS, one wavefront per SIMD or less)
-    # and a one-pot table of more than 32 layouts (in HBM), with and without the one-step-ahead reads (131 072 envs)
+    # and a one-pot table of more than 32 layouts (in HBM), with and without the one-step-ahead reads (131 072 + 64 envs: ragged,
+    # or the mover / interact kernel takes the batch in two rounds)
     mix = LayoutTable([spec_from_name(nm) for nm in CANONICAL_5], pad_to=(9, 5))
     forty = LayoutTable([spec_from_name(nm) for nm in ("cramped_room", "forced_coordination_tomato", "cramped_room_tomato",
                                                          "cramped_room_single") if spec_from_name(nm).num_players == 2
                          and len(spec_from_name(nm).cells_of("P")) == 1] * 20, pad_to=(9, 5))
     assert len(forty) > 32 and forty.max_pots == 1
-    for tab, n, K in ((mix, 3000, 48), (forty, 2500, 32), (forty, 131072, 16)):
+    for tab, n, K, inst in ((mix, 3000, 48, "R4TerrainLdsTiled"), (forty, 2500, 32, "R4TerrainL2OnePotTiled"),
+                            (forty, 131072 + 64, 16, "R4TerrainL2OnePotLeanTiled")):
         lid = (np.arange(n) % len(tab)).astype(np.uint16)
         st = np.zeros((tab.n_planes, n, 16), np.uint8)
         for l in range(len(tab)):
@@ -1307,6 +1312,7 @@ def test_rollout_random_with_flags_tiled_by_8_steps(gpu):
         rew_b = torch.zeros_like(rew_a)
         fl_a = torch.full((K // 8, n, 8), 0x55, dtype=torch.uint8, device=gpu)
         fl_b = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
+        assert RC.plan_of(tab, n, K, 0, 24, tiled=True).startswith(RC.R4[inst]), (len(tab), n)
         a.rollout_random(K, rew_a, fl_a, flags_tiled8=True)
         b.rollout_random(K, rew_b, fl_b)
         assert torch.equal(VecOvercookedEnv.untile_flags(fl_a), fl_b), (len(tab), n)
