@@ -605,7 +605,8 @@ int oc_output_stores_only(int64_t n_envs, int n_steps, float* d_rewards, uint8_t
 
 /*
  * oc_rollout_plan (ABI 6) — which kernel instance oc_rollout_random would launch for this batch and launch shape, as text
- * (e.g. "k_rollout5<LAY_LDS=true, FT8=true, OLD=false, BIG=false, EV=false> mover + interact wavefronts, 1 round(s), 130864 B LDS").
+ * (e.g. "k_rollout5<LAY_LDS=true, FT8=true, OLD=false, BIG=false, EV=false> mover + interact wavefronts, 1 round(s), 130864 B LDS";
+ * "> one pot slot, mover + ..." where max_pots == 1 selects the instance compiled for one pot).
  * oc_rollout_random plans every call before it launches anything (its argument checks, then the choice of kernels); this is that
  * plan, put into words instead of launched: every check applies, every choice is the one a real call gets, and the code that answers
  * holds no launch and no device pointer — so it also runs on a host without a GPU

@@ -326,7 +326,9 @@ RolloutChoice choose_launch(const OcBatch* b, int n_obj, uint32_t options, int64
     if (duo_batch && n_steps >= 8 && (t0 & 7) == 0 && (n_steps & 7) == 0) {
         // (event counters: tables in LDS, at most 64 cells; 65..128 cells: tables in LDS only)
         const bool big = !events && n_cells > 64;
-        ch.r5 = R5Sel{events || big || lds, tiled8, old_dyn, big, events, noout};
+        // (one pot everywhere: the one-slot instances, where they exist — cooking starts without the rare branch)
+        const bool one_pot = b->max_pots == 1 && !old_dyn && !big && !events;
+        ch.r5 = R5Sel{events || big || lds, tiled8, old_dyn, big, events, noout, one_pot};
     } else if (events) {  // the general instances (arithmetic movement, either dynamics; mixed tables: the records are read through L2)
         ch = uniform && small ? pick<R4EvUniform>() : small ? pick<R4EvSmall>() : pick<R4EvGeneral>();
     } else if (joint) {  // (32-bit cell words and the faced cells read a step ahead where no two players can face the same cell)

@@ -81,27 +81,41 @@ struct R5 {
 template <class K>
 size_t smem5(const Rollout4Call& c) { return oc_detail::rollout5_lds_bytes(K::LAY_LDS, K::BIG, K::EV, c.n_obj); }
 
+// The pot slots of an instance are resolved here, where it is launched and described: the six instances of new dynamics, 32-bit cell
+// words and no event log ({table in LDS, through L2} x {tiled flags, flat flags, no output arrays}) exist with one slot as well, for
+// tables whose layouts all have one pot (R5Sel.one_pot); every other instance has two
 template <class K>
-void go5(const Rollout4Call& c) {
+constexpr bool r5_has_one_pot() { return !K::OLD && !K::BIG && !K::EV; }
+template <class K>
+bool one_pot5(const Rollout4Call& c) { return r5_has_one_pot<K>() && c.r5.one_pot; }
+
+template <class K, int MAXP>
+void go5_slots(const Rollout4Call& c) {
     const OcBatch* b = c.b;
     const size_t smem = smem5<K>(c);
-    if (!want_lds(k_rollout5<K::LAY_LDS, K::FT8, K::OLD, K::BIG, K::EV, K::NOOUT>, smem)) return;
-    hipLaunchKernelGGL((k_rollout5<K::LAY_LDS, K::FT8, K::OLD, K::BIG, K::EV, K::NOOUT>), dim3(grid_for(b->n_envs)), dim3(2 * BLOCK), smem,
+    if (!want_lds(k_rollout5<K::LAY_LDS, K::FT8, K::OLD, K::BIG, K::EV, K::NOOUT, MAXP>, smem)) return;
+    hipLaunchKernelGGL((k_rollout5<K::LAY_LDS, K::FT8, K::OLD, K::BIG, K::EV, K::NOOUT, MAXP>), dim3(grid_for(b->n_envs)), dim3(2 * BLOCK), smem,
                        c.stream, b->d_layouts, b->n_layouts, b->d_layout_id, (uint4*)c.d_state, (float4*)c.d_rewards, c.d_flags,
                        (float4*)c.d_ep_returns, b->n_envs, b->width, c.n_obj, c.horizon, c.options, (uint32_t)c.seed,
                        (uint32_t)(c.seed >> 32), c.env_offset, c.t0, c.n_steps, c.sa, c.ea);
+}
+template <class K>
+void go5(const Rollout4Call& c) {
+    if constexpr (r5_has_one_pot<K>())
+        if (c.r5.one_pot) return go5_slots<K, 1>(c);
+    go5_slots<K, 2>(c);
 }
 
 template <class K>
 void describe5(const Rollout4Call& c, char* out, size_t out_size) {
     const int64_t per_round = (simd_count() / 4) * BLOCK;
-    snprintf(out, out_size, "k_rollout5<LAY_LDS=%s, FT8=%s, OLD=%s, BIG=%s, EV=%s%s> mover + interact wavefronts, %d round(s), %zu B LDS",
+    snprintf(out, out_size, "k_rollout5<LAY_LDS=%s, FT8=%s, OLD=%s, BIG=%s, EV=%s%s>%s mover + interact wavefronts, %d round(s), %zu B LDS",
              tf(K::LAY_LDS), tf(K::FT8), tf(K::OLD), tf(K::BIG), tf(K::EV), K::NOOUT ? ", NOOUT=true" : "",
-             (int)((c.b->n_envs + per_round - 1) / per_round), smem5<K>(c));
+             one_pot5<K>(c) ? " one pot slot," : "", (int)((c.b->n_envs + per_round - 1) / per_round), smem5<K>(c));
 }
 
 // f(R5<...>()) for the instance s selects, of k_rollout5's 24: four table kinds x {tiled flags, flat flags, no output arrays} x
-// {new, old dynamics}
+// {new, old dynamics} (go5 / describe5 then take the one-slot form of the six that have one)
 template <bool LAY_LDS, bool BIG, bool EV, class F>
 void with_r5_table(const oc_detail::R5Sel& s, F f) {
     if (s.noout) s.old ? f(R5<LAY_LDS, false, true, BIG, EV, true>()) : f(R5<LAY_LDS, false, false, BIG, EV, true>());

@@ -185,9 +185,11 @@ using R4Instances = R4List<R4EvUniform, R4EvSmall, R4EvGeneral, R4JointTiled, R4
                            R4TerrainL2Lean, R4ArithUniformOut, R4ArithUniform, R4ArithLdsOut, R4ArithL2Out, R4ArithSmall, R4ArithGeneral,
                            R4RecUniform, R4RecSmall, R4RecGeneral, R4RecEvUniform, R4RecEvSmall, R4RecEvGeneral>;
 
-// k_rollout5<LAY_LDS, FT8, OLD, BIG, EV, NOOUT> (step_duo5.hpp): the mover / interact kernel, chosen by its own six flags
+// k_rollout5<LAY_LDS, FT8, OLD, BIG, EV, NOOUT, MAXP> (step_duo5.hpp): the mover / interact kernel, chosen by its own six flags;
+// one_pot: every layout of the table has one pot (OcBatch.max_pots == 1) and the instance exists with one pot slot (new
+// dynamics, not big, no event log): MAXP = 1
 struct R5Sel {
-    bool lay_lds, ft8, old, big, ev, noout;
+    bool lay_lds, ft8, old, big, ev, noout, one_pot;
 };
 
 // One oc_rollout_random / oc_rollout_record(_ex) launch, as oc_amd.hip hands it to the unit that compiles the chosen instance.

@@ -168,7 +168,25 @@ struct Cw5 {
 //     u32 in LDS behind the cell words for the launch (row 0 takes what is not an event), logged with ds_add
 // NOOUT: the launch has no output arrays (rewards and flags both NULL: a rollout run for its final states, episode returns or event
 //     counters) — the same step without the two stores (round 6: these launches used to fall to the general one-wavefront path)
-template <bool LAY_LDS, bool FT8, bool OLD = false, bool BIG = false, bool EV = false, bool NOOUT = false>
+// MAXP: pot slots, 2 or 1 (tables whose layouts all have one pot, OcBatch.max_pots == 1: new dynamics, 32-bit cell words, no event
+//     log).  With one slot there is no K5_POT_B type, no second countdown / pot address / "ready" store, and a cooking start needs no
+//     branch where the lane's layout cooks every recipe equally long (cook_u below)
+// One-slot instances: the cook time of a layout if every recipe a pot can start with (one to three ingredients: recipe n_onion +
+// 4 * n_tomato is byte n_onion of C.cook[n_tomato]) has the same one and it is at least 2, else 0; and what a lane with that cook time
+// keeps of START in its gate.  (Free functions, not lambdas of the kernel: a lambda the two-slot instances never call still changed
+// their register allocation.)
+__device__ __forceinline__ uint32_t r5_uniform_cook(const LayC& C) {
+    const uint32_t t = C.cook[3] & 0xFFu, t4 = t * 0x01010101u;
+    const bool same = ((C.cook[0] ^ t4) >> 8) == 0u && ((C.cook[1] ^ t4) & 0xFFFFFFu) == 0u && ((C.cook[2] ^ t4) & 0xFFFFu) == 0u;
+    return same && t >= 2u ? t : 0u;
+}
+__device__ __forceinline__ uint32_t r5_start_gate(uint32_t cook_u, uint32_t exotic) { return cook_u != 0u && exotic == 0u ? 0u : Z5_START_A; }
+#ifdef OC_R5_BRANCH_START  // (measurement builds: one-pot instances that keep every cooking start in the rare branch)
+constexpr bool R5_FAST_START = false;
+#else
+constexpr bool R5_FAST_START = true;
+#endif
+template <bool LAY_LDS, bool FT8, bool OLD = false, bool BIG = false, bool EV = false, bool NOOUT = false, int MAXP = 2>
 __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_rollout5(
     const OcLayout* __restrict__ g_layouts, int n_layouts, const uint16_t* layout_id, uint4* st, float4* __restrict__ rewards,
     uint8_t* __restrict__ flags, float4* __restrict__ ep_returns, int64_t n, int W, int n_obj, int horizon, uint32_t options,
@@ -178,7 +196,8 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
     if ((uint32_t)(uintptr_t)(OC_LDS uint8_t*)s_dyn5 != 0u) __builtin_trap();  // folds away: the region starts at address 0
     uint4* const s_lay = reinterpret_cast<uint4*>(s_dyn5 + M::LAY);
     uint4* const s_lut = reinterpret_cast<uint4*>(s_dyn5 + M::LUT);
-    constexpr int MAXP = 2;
+    static_assert(MAXP == 2 || (MAXP == 1 && !OLD && !BIG && !EV), "one pot slot: new dynamics, <= 64 cells, no event log");
+    constexpr bool FAST = MAXP == 1 && R5_FAST_START;
     using CW = Cw5<BIG>;
     constexpr uint32_t CS = CW::CS;
     static_assert(M::LUT == 0, "K16 = 80 * key: the LUT starts at LDS address 0");
@@ -334,6 +353,11 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
     // its class), N, the pots' countdowns (k_rollout4's: steps until ready, REM_IDLE when not cooking) and cell addresses
     uint32_t h0, h1, hz0, hz1, rem[MAXP], tk[MAXP], pa[MAXP], exotic = 0;
     int32_t N = 0;
+    // FAST: cook_u = the cook time of the lane's layout if every recipe a pot can start with (one to three ingredients) has the same
+    // one and it is at least 2 (a pot that starts is not ready with that step's env effects), else 0.  A lane with such a layout and
+    // no soup object without ingredients in its pot (exotic) loads the countdown of a start in the straight line and leaves START out
+    // of its gate (start_gate 0); every other lane keeps START in its gate and takes the rare branch
+    uint32_t cook_u = 0, start_gate = Z5_START_A;
     int32_t F = 0;  // EV: pots that are full (three idle items, cooking or ready), kept by the entries' deltas like N
     static_assert(!EV || !BIG, "the counters' row 0 is the spare cell row in front of them: 4-byte cell words");
     const uint32_t cnt0 = dummy;  // EV: this lane's column of event counters, [row][BLOCK] u32: row 0 = the spare cell word, rows 1.. behind it
@@ -365,7 +389,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
     auto write_empty_grid = [&]() __attribute__((always_inline)) {
         for (int c = 0; c < n_obj * 16; ++c) {
             const uint32_t tb = L.terrain((uint32_t)c), type = tb & 7u;
-            const uint32_t type5 = (type == OC_T_POT && (tb >> 3) == 1u) ? (uint32_t)K5_POT_B : type;
+            const uint32_t type5 = (MAXP > 1 && type == OC_T_POT && (tb >> 3) == 1u) ? (uint32_t)K5_POT_B : type;
             CW::wr(col + (uint32_t)c * CS, CW::make(type5, 0u, 0u));
         }
     };
@@ -385,7 +409,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
                     const uint32_t o = (ow[q] >> (8 * b)) & 0xFFu, tb = (T >> (8 * b)) & 0xFFu, type = tb & 7u;
-                    const uint32_t type5 = (type == OC_T_POT && (tb >> 3) == 1u) ? (uint32_t)K5_POT_B : type;
+                    const uint32_t type5 = (MAXP > 1 && type == OC_T_POT && (tb >> 3) == 1u) ? (uint32_t)K5_POT_B : type;
                     const uint32_t cls = type == OC_T_COUNTER ? counter_class5(o) : 0u;
                     dishes += (type == OC_T_COUNTER && o == OC_O_DISH) ? 1 : 0;
                     CW::wr(col + (uint32_t)(16 * p + 4 * q + b) * CS, CW::make(type5, cls, o));
@@ -411,6 +435,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
             }
         }
         N = 64 * dishes - useful;
+        if (FAST) { cook_u = r5_uniform_cook(C); start_gate = r5_start_gate(cook_u, exotic); }
     }
     float4 ep = ep_returns ? ep_returns[e] : make_float4(0.f, 0.f, 0.f, 0.f);
     typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -489,7 +514,9 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
         if (OLD) { late_now = N_late; N_late = 0; }
         // ---- ONE branch for everything rare: cooking starts, deliveries, dish pick-ups that may be useful (N < 0 before or
         //      after player 0's interact: no loose dish, some useful pot), a shared cell player 0 has changed, the horizon
-        const uint32_t gate = ((uint32_t)(N | N_mid) & Z5_TAKE) | Z5_SERVE | Z5_START_A | Z5_START_B | (EV ? Z5_PLACE : 0u);
+        // (FAST: a lane whose cooking starts need no branch leaves them out of its gate)
+        const uint32_t gate = ((uint32_t)(N | N_mid) & Z5_TAKE) | Z5_SERVE | (FAST ? start_gate : Z5_START_A) | (MAXP > 1 ? Z5_START_B : 0u) |
+                              (EV ? Z5_PLACE : 0u);
         uint32_t c1_seen = c1;  // EV: the cell word player 1's interact saw (player 0's result when it redoes it)
         const uint32_t rare_bits = ((e0.z | e1.z) & gate) | ((e0.z | REC5_DONE) & f_rec);
         uint64_t q_lo, q_hi;  // the reward quad as two register pairs: zeros, and the two entries' shaped floats
@@ -500,6 +527,19 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
         }
         uint32_t nh0 = r0, nh1 = r1, nz0 = e0.z, nz1 = e1.z;
         int32_t F_reset = -1;  // EV: the full pots of a new episode's start state
+        // FAST: begin_cooking in the straight line — the countdown takes cook_u + k8 where an entry carries the START flag (a sign
+        // extension of the flag's bit and a bit-field insert).  This uses the entries as they were looked up, and it runs on EVERY lane:
+        // the rare branch puts the old countdown back and decides again for the lanes it serves — those whose START is in their gate
+        // (no usable cook_u: every START of theirs enters the branch), a shared-cell replay of player 1's interact (which may add a
+        // start or drop a stale one: the entries that finally count decide), a restart (the new episode's countdown stands)
+        const uint32_t rem_was = rem[0];
+        if (FAST) {
+            // (written out: the compiler makes an and, a compare, an add and a select of the C form)
+            static_assert(Z5_START_A == 1u << 19, "the START flag's bit");
+            uint32_t m;
+            asm("v_bfe_i32 %1, %2, 19, 1\n\tv_bfi_b32 %0, %1, %3, %4"
+                : "=v"(rem[0]), "=&v"(m) : "v"(e0.z | e1.z), "v"(cook_u + (uint32_t)k8), "v"(rem_was));
+        }
         if (__builtin_expect(rare_bits != 0u, 0)) {
             bool grid_changed = false;
             const uint32_t hb0 = CW::hand(h0), hb1 = CW::hand(h1), hn0 = CW::hand(r0);
@@ -513,15 +553,17 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
                 grid_changed = true;
             }
             const uint32_t fz = e0.z | e1.z;
+            if (FAST) rem[0] = (start_gate == 0u && (fz & Z5_START_A)) ? cook_u + (uint32_t)k8 : rem_was;  // (behind the replay)
             // begin_cooking (mdp.py:1515-1522) = load the countdown: tick 0 now, cooked once by this step's env effects (Q4)
 #pragma unroll
             for (int k = 0; k < MAXP; ++k) {
                 const uint32_t sk = k == 0 ? Z5_START_A : Z5_START_B;
-                if (fz & sk) {
+                if (fz & sk & (FAST ? start_gate : 0xFFFFFFFFu)) {  // (FAST: the lanes that start in the straight line do not come here)
                     const uint32_t soup = CW::obj((e0.z & sk) ? r0 : r1);
                     const uint32_t cook = cook_of(C, soup);
                     rem[k] = cook + (uint32_t)k8;  // (= cook - 1 steps after this one, counted from the block's first step)
                     exotic &= ~(1u << k);
+                    if (FAST) start_gate = r5_start_gate(cook_u, exotic);
                     if (cook <= 1u) {  // ready with this step's env effects (cook == 0: at once, never ticks)
                         CW::wr_key(pa[k], pot_type5(k), PC_READY);
                         grid_changed = true;
@@ -576,6 +618,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
                                         : Lay{reinterpret_cast<const uint8_t*>(g_layouts) + (size_t)lid * 256u};
                             C = load_consts<false>(L);
                             pot_addrs();
+                            if (FAST) cook_u = r5_uniform_cook(C);
                         }
                         d = draw_start(L, g, sa.epoch + step_k, sa.seed_lo, sa.seed_hi, sa.random_start_pos, sa.thresh);
                     }
@@ -597,6 +640,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
                             CW::wr(pa[k], CW::make(pot_type5(k), pc, o));
                         }
                     }
+                    if (FAST) start_gate = r5_start_gate(cook_u, exotic);
                     N_new = -useful;
                     late_now = 0;  // (pots drawn idle and full for the new episode: N_late, from the next step on)
                     nh0 = d.held0 << (8 * CW::HAND_BYTE); nh1 = d.held1 << (8 * CW::HAND_BYTE);

@@ -44,11 +44,12 @@ SHAPES = (
 
 
 def _short(text):
-    """'k_rollout5<LAY_LDS=true, ...> mover + ..., 130864 B LDS' -> instance name + LDS bytes"""
+    """'k_rollout5<LAY_LDS=true, ...>[ one pot slot,] mover + ..., 130864 B LDS' -> instance name, pot slots, rounds, LDS bytes"""
     head = text.split(">")[0] + ">" if "<" in text else text
     lds = text.rsplit(",", 1)[-1].strip() if "B LDS" in text else ""
     rounds = [p.strip() for p in text.split(",") if "round(s)" in p]
-    return head + (" " + rounds[0] if rounds else "") + (" " + lds if lds else "")
+    slots = " one pot slot" if "> one pot slot," in text else ""
+    return head + slots + (" " + rounds[0] if rounds else "") + (" " + lds if lds else "")
 
 
 def table(names=None):
