@@ -451,6 +451,11 @@ int oc_shape_rewards(const OcBatch* batch, const float* d_rewards, const uint8_t
  * wavefronts per 256 envs — four step and restart, four compute phi and the shaped rewards, all eight encode and stream the
  * observations): 65 536 cramped_room envs with u8 observations 26.2 -> 20.3 us per call, asymmetric_advantages 37.6 -> 30.7 us
  * (profiles/r05_train_step_obs.txt); same results bit for bit.
+ * The paths, chosen once per call by one planner (oc_multi_agent_plan below says which one a call takes, and which kernel
+ * instance of it): k_train_step_obs<MAXP, T, NWV> (the step and its observation; ABI 5 above) — k_train_step1<UNIFORM, MAXP,
+ * LAY_LDS> (two players, at most two pots, at most 64 cells, no event sink: the whole step in one kernel on the wire format, then
+ * oc_encode_lossless) — k_train_step<UNIFORM, EV> (the same with event counters or on 65..128 cells) — the sequence of entry
+ * points listed first (any other table).
  */
 int oc_multi_agent_step(const OcBatch* batch, void* d_state, const uint8_t* d_actions, float* d_rewards,
                         uint8_t* d_flags, float* d_ep_returns, float* d_ep_returns_out, const uint8_t* d_plan_blob,
@@ -619,6 +624,26 @@ int oc_output_stores_only(int64_t n_envs, int n_steps, float* d_rewards, uint8_t
  */
 int oc_rollout_plan(const OcBatch* batch, int horizon, uint32_t options, int64_t t0, int n_steps, int with_outputs,
                     int event_sink, const OcStartSpec* start, char* out, size_t out_size);
+
+/*
+ * oc_multi_agent_plan (ABI 6: an entry point added beside the others; no existing signature, struct or option changes, so the
+ * version stays, and a binding that wants it on an older ABI 6 library looks the symbol up) — which path, and which kernel instance of it, oc_multi_agent_step would run for this batch and these
+ * arrays, as text: "k_train_step_obs<MAXP=1, T=u8, NWV=16> unit=1, G=7, 142096 B LDS",
+ * "k_train_step1<UNIFORM=false, MAXP=2, LAY_LDS=true> + oc_encode_lossless", "k_train_step<UNIFORM=true, EV=true> + oc_encode_lossless",
+ * "sequence: oc_step, oc_potential, oc_shape_rewards, copy of the episode returns, oc_reset, oc_encode_lossless"; up to and
+ * including '>' the text is the instance's name and stable.  oc_multi_agent_step plans every call before it launches anything (its
+ * argument checks, then the choice of path and instance) and launches from that plan; this is the same plan put into words: every
+ * check applies (refusals carry oc_multi_agent_step's name), the code that answers is told which arrays a call has, not where they
+ * are, and holds no launch — so it also runs on a host without a GPU (the device's SIMD count then defaults to MI355X's 1 024).
+ * The call described has every required array (aligned) and both episode-return arrays, and
+ *   with_obs      1: d_obs is given (16-byte aligned), of obs_dtype; 0: NULL
+ *   use_phi       1: the phi tables, the plan tables and the three phi buffers are given; 0: d_phi_tables is NULL
+ *   event_sink    0 none, 1 per-episode counters (OcEventSink.d_counts)
+ *   start         NULL or the start-state description the call would carry
+ *   out, out_size caller's text buffer (>= 256 bytes holds every answer)
+ */
+int oc_multi_agent_plan(const OcBatch* batch, int horizon, int with_obs, int obs_dtype, int use_phi, int event_sink,
+                        const OcStartSpec* start, char* out, size_t out_size);
 
 #ifdef __cplusplus
 }

@@ -758,7 +758,12 @@ int oc_reset(const OcBatch* b, void* d_state, const uint8_t* d_mask, float* d_ep
 }  // extern "C"
 
 namespace {
-// ---- oc_multi_agent_step: its arguments, checked, and its three paths
+// ---- oc_multi_agent_step: the call is planned first (plan_train_step: every check, then the path and its kernel instance;
+//      no launch, no device memory), then launched from that plan — or, by oc_multi_agent_plan, described.  The paths:
+//        k_train_step_obs<MAXP, T, NWV>          the step and its observation in one kernel (train_step_obs)
+//        k_train_step1<UNIFORM, MAXP, LAY_LDS>   the step in one kernel on the wire format, then oc_encode_lossless (train_step_fused)
+//        k_train_step<UNIFORM, EV>               the same with event counters or on 65..128 cells (train_step_fused)
+//        the sequence of entry points            any other table (train_step_general)
 struct TrainStep {
     const OcBatch* b;
     int n_obj;
@@ -788,23 +793,41 @@ struct TrainObsShape {
     int unit = 0, nwv = 0, gmax = 0;
     size_t smem = 0;
 };
+// What a plan needs to know of a call's arrays: which ones are there, never where (oc_multi_agent_plan has no more than that
+// to give)
+struct TrainArrays {
+    bool state, actions, rewards, flags, shaped, shaped_aligned16, done;
+    bool phi_tables, phi_rest;  // use_phi: the phi tables / the plan tables and the three phi buffers
+    bool ep_returns, ep_returns_out;  // (no choice depends on them: read by describe_train_plan only, for the sequence's copy)
+    bool obs, obs_aligned16;
+    bool events;  // an event sink with counters or masks
+};
+// The plan of one oc_multi_agent_step call: every check, every choice; no launch, no device memory
+struct TrainPlan {
+    int rc = OC_OK;  // the call is refused with this code (the message: oc_last_error)
+    enum Path { OBS, FUSED, GENERAL } path = GENERAL;  // k_train_step_obs / k_train_step1 or k_train_step, then the observation / the sequence
+    int n_obj = 0;
+    StartArgs sa = {};
+    TrainObsShape sh;    // OBS
+    bool lean = false;   // FUSED: k_train_step1 (else k_train_step)
+    bool uniform = false, lay_lds = false, ev = false;  // FUSED: the instance's UNIFORM, LAY_LDS (k_train_step1), EV (k_train_step)
+    int maxp = 2;        // OBS, FUSED: the instance's MAXP
+};
 // Round 5: the step AND its observation in one kernel for single-layout batches (at most two pots, two players, 64 cells, no
 // event sink) that give at least half of the CUs a workgroup of 256 envs (smaller batches: the observation kernel spreads
 // over all CUs)
-bool train_obs_wanted(const TrainStep& a) {
+bool train_obs_wanted(const OcBatch* b, int n_obj, const TrainArrays& have, int obs_dtype) {
     static const bool no_fused_obs = tuning_set("OC_TRAIN_NO_FUSED_OBS");
-    const OcBatch* b = a.b;
-    return a.d_obs && b->n_layouts == 1 && b->width * b->height <= 64 && !ev_on(a.ea) && a.n_obj <= STEP1_MAX_PLANES && !step_no_lean() &&
-           !no_fused_obs && obs_dtype_ok(a.obs_dtype) && aligned16(a.d_obs) && b->n_envs >= (simd_count() / 8) * BLOCK;
+    return have.obs && b->n_layouts == 1 && b->width * b->height <= 64 && !have.events && n_obj <= STEP1_MAX_PLANES && !step_no_lean() &&
+           !no_fused_obs && obs_dtype_ok(obs_dtype) && have.obs_aligned16 && b->n_envs >= (simd_count() / 8) * BLOCK;
 }
-TrainObsShape train_obs_shape(const TrainStep& a) {
+TrainObsShape train_obs_shape(const OcBatch* b, int n_obj, const TrainArrays& have, int obs_dtype) {
     TrainObsShape sh;
-    if (!train_obs_wanted(a)) return sh;
-    const OcBatch* b = a.b;
-    const size_t elem = a.obs_dtype == OC_OBS_U8 ? 1 : 4;
+    if (!train_obs_wanted(b, n_obj, have, obs_dtype)) return sh;
+    const size_t elem = obs_dtype == OC_OBS_U8 ? 1 : 4;
     const size_t env_bytes = (size_t)2 * b->width * b->height * OC_NUM_LAYERS * elem;
     const int unit = envs_per_template(env_bytes);
-    const size_t fixed = (size_t)a.n_obj * BLOCK * 16 + env_bytes * unit + (size_t)4 * BLOCK * 16;
+    const size_t fixed = (size_t)n_obj * BLOCK * 16 + env_bytes * unit + (size_t)4 * BLOCK * 16;
     const size_t budget = 150 * 1024;
     // wavefronts per workgroup: 16 (4 owners, 4 helpers, 8 encoders; round 6) for u8 observations whose private images
     // still hold >= 6 envs then (cramped_room-sized grids: the encode loop there is bound by what the wavefronts of a
@@ -812,7 +835,7 @@ TrainObsShape train_obs_shape(const TrainStep& a) {
     static const int forced_w = tuning_int("OC_TRAIN_OBS_WAVES", 0), forced_g = tuning_int("OC_TRAIN_OBS_G", 0);
     for (int w : {16, 8}) {
         if (forced_w && w != forced_w) continue;
-        if (!forced_w && w == 16 && a.obs_dtype != OC_OBS_U8) continue;
+        if (!forced_w && w == 16 && obs_dtype != OC_OBS_U8) continue;
         int g = fixed < budget ? (int)((budget - fixed) / ((size_t)w * env_bytes)) : 0;
         if (g > 64) g = 64;
         if (forced_g > 0 && forced_g < g) g = forced_g;
@@ -827,9 +850,47 @@ TrainObsShape train_obs_shape(const TrainStep& a) {
     return sh;
 }
 
+// Which of oc_multi_agent_step's paths, and which kernel instance of it, serves a call: the one place that reads the batch
+// and the call for it.  The train_step_* functions below launch what it returns; oc_multi_agent_plan puts it into words.
+TrainPlan plan_train_step(const OcBatch* b, const TrainArrays& have, int obs_dtype, int horizon, const OcStartSpec* start) {
+    const char* const who = "oc_multi_agent_step";
+    TrainPlan p;
+    const auto refused = [&p](int rc) { p.rc = rc; return p; };
+    if (!have.done) return refused(refuse(who, "d_done is required (it is the reset mask)"));
+    if (int rc = check_start(who, start, &p.sa, b)) return refused(rc);
+    if (int rc = check_batch(b, &p.n_obj)) return refused(rc);
+    // at most two pots and two players: the whole step in one kernel
+    const bool fused = b->max_pots >= 1 && b->max_pots <= 2 && (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0;
+    if (!have.state || !have.actions || !have.rewards || !have.flags || (fused && !have.shaped))
+        return refused(refuse(who, fused ? "NULL state/actions/rewards/flags/shaped pointer" : "NULL state/actions/rewards/flags pointer"));
+    if (fused && have.phi_tables && !have.phi_rest) return refused(refuse(who, "use_phi needs the plan tables and the three phi buffers"));
+    if (int rc = check_horizon(who, horizon)) return refused(rc);
+    if (fused && !have.shaped_aligned16) return refused(refuse(who, "d_shaped must be 16-byte aligned"));
+    if (!fused) return p;
+    p.path = TrainPlan::FUSED;
+    p.uniform = b->n_layouts == 1;
+    if (b->n_envs > 0) {
+        p.sh = train_obs_shape(b, p.n_obj, have, obs_dtype);
+        if (p.sh.nwv) {
+            p.path = TrainPlan::OBS;
+            p.maxp = b->max_pots == 1 ? 1 : 2;
+            return p;
+        }
+    }
+    p.lean = !have.events && p.n_obj <= STEP1_MAX_PLANES && !step_no_lean();  // the transition on the wire format itself (step_one.hpp)
+    if (p.lean) {
+        p.maxp = p.uniform && b->max_pots == 1 ? 1 : 2;
+        p.lay_lds = b->n_layouts <= LDS_LAYOUT_MAX;
+    } else {
+        p.ev = have.events;
+    }
+    return p;
+}
+
 // path 1: the step and its observation in one kernel (k_train_step_obs)
-int train_step_obs(const TrainStep& a, const TrainObsShape& sh) {
+int train_step_obs(const TrainStep& a, const TrainPlan& p) {
     const OcBatch* b = a.b;
+    const TrainObsShape& sh = p.sh;
     const dim3 grid(grid_for(b->n_envs));
 #define GOTO(MP, T, NW)                                                                                                 \
     do {                                                                                                                \
@@ -841,8 +902,8 @@ int train_step_obs(const TrainStep& a, const TrainObsShape& sh) {
                            b->n_envs, b->width, b->height, a.n_obj, a.horizon, sh.unit, sh.gmax, a.sa);                 \
     } while (0)
 #define GOTOW(MP, T) do { if (sh.nwv == 16) GOTO(MP, T, 16); else GOTO(MP, T, 8); } while (0)
-    if (a.obs_dtype == OC_OBS_U8) { if (b->max_pots == 1) GOTOW(1, uint8_t); else GOTOW(2, uint8_t); }
-    else { if (b->max_pots == 1) GOTOW(1, float); else GOTOW(2, float); }
+    if (a.obs_dtype == OC_OBS_U8) { if (p.maxp == 1) GOTOW(1, uint8_t); else GOTOW(2, uint8_t); }
+    else { if (p.maxp == 1) GOTOW(1, float); else GOTOW(2, float); }
 #undef GOTOW
 #undef GOTO
     return check_launch("oc_multi_agent_step");
@@ -850,12 +911,11 @@ int train_step_obs(const TrainStep& a, const TrainObsShape& sh) {
 
 // path 2: the whole step in one kernel (k_train_step1; k_train_step with event counters or a grid above 64 cells), then the
 // observation
-int train_step_fused(const TrainStep& a) {
+int train_step_fused(const TrainStep& a, const TrainPlan& p) {
     const OcBatch* b = a.b;
     if (b->n_envs > 0) {
-        const bool uniform = b->n_layouts == 1, lds = b->n_layouts <= LDS_LAYOUT_MAX;
         const dim3 grid(grid_for(b->n_envs)), block(BLOCK);
-        if (!ev_on(a.ea) && a.n_obj <= STEP1_MAX_PLANES && !step_no_lean()) {  // the transition on the wire format itself (step_one.hpp)
+        if (p.lean) {
             const size_t smem1 = (size_t)a.n_obj * BLOCK * sizeof(uint4);
 #define GOT1(U, MP, LL)                                                                                                  \
     hipLaunchKernelGGL((k_train_step1<U, MP, LL>), grid, block, smem1, a.stream, b->d_layouts, b->n_layouts, b->d_layout_id, \
@@ -863,9 +923,9 @@ int train_step_fused(const TrainStep& a) {
                        (float4*)a.d_ep_returns_out, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_phi_next,           \
                        a.d_phi_cur, a.d_phi_start, a.reward_shaping_factor, a.d_shaped, a.d_done, b->n_envs, b->width,   \
                        b->height, a.n_obj, a.horizon, a.sa)
-            if (uniform && b->max_pots == 1) GOT1(true, 1, true);
-            else if (uniform) GOT1(true, 2, true);
-            else if (lds) GOT1(false, 2, true);
+            if (p.uniform && p.maxp == 1) GOT1(true, 1, true);
+            else if (p.uniform) GOT1(true, 2, true);
+            else if (p.lay_lds) GOT1(false, 2, true);
             else GOT1(false, 2, false);
 #undef GOT1
         } else {
@@ -880,8 +940,8 @@ int train_step_fused(const TrainStep& a) {
                            a.reward_shaping_factor, a.d_shaped, a.d_done, b->n_envs, b->width, b->height, a.n_obj,    \
                            a.horizon, a.sa, a.ea);                                                                    \
     } while (0)
-            if (uniform) { if (ev_on(a.ea)) GOT(true, true); else GOT(true, false); }
-            else { if (ev_on(a.ea)) GOT(false, true); else GOT(false, false); }
+            if (p.uniform) { if (p.ev) GOT(true, true); else GOT(true, false); }
+            else { if (p.ev) GOT(false, true); else GOT(false, false); }
 #undef GOT
         }
         if (int rc = check_launch("oc_multi_agent_step")) return rc;
@@ -927,6 +987,43 @@ int train_step_general(const TrainStep& a) {
     if (a.d_obs) return oc_encode_lossless(b, a.d_state, a.d_obs, a.obs_dtype, a.horizon, a.stream);
     return OC_OK;
 }
+
+TrainArrays train_arrays_of(const void* d_state, const void* d_actions, const void* d_rewards, const void* d_flags, const void* d_ep_returns,
+                            const void* d_ep_returns_out, const void* d_plan_blob, const void* d_plan_off, const void* d_phi_tables,
+                            const void* d_phi_next, const void* d_phi_cur, const void* d_phi_start, const void* d_shaped,
+                            const void* d_done, const void* d_obs, bool events) {
+    TrainArrays have = {};
+    have.state = d_state != nullptr; have.actions = d_actions != nullptr; have.rewards = d_rewards != nullptr; have.flags = d_flags != nullptr;
+    have.shaped = d_shaped != nullptr; have.shaped_aligned16 = aligned16(d_shaped); have.done = d_done != nullptr;
+    have.phi_tables = d_phi_tables != nullptr;
+    have.phi_rest = d_plan_blob && d_plan_off && d_phi_next && d_phi_cur && d_phi_start;
+    have.ep_returns = d_ep_returns != nullptr; have.ep_returns_out = d_ep_returns_out != nullptr;
+    have.obs = d_obs != nullptr; have.obs_aligned16 = aligned16(d_obs);
+    have.events = events;
+    return have;
+}
+
+// A plan in words (oc_multi_agent_plan): up to and including '>' the kernel instance, as tests match it
+void describe_train_plan(const OcBatch* b, const TrainPlan& p, const TrainArrays& have, int obs_dtype, const OcStartSpec* start, char* out,
+                         size_t out_size) {
+    const auto tf = [](bool v) { return v ? "true" : "false"; };
+    const char* const then_obs = have.obs ? " + oc_encode_lossless" : "";
+    if (p.path == TrainPlan::GENERAL) {  // what train_step_general enqueues, in its order
+        const bool regen = start && start->regen_count && b->n_layouts > 1;
+        snprintf(out, out_size, "sequence: oc_step%s, oc_shape_rewards%s%s, %s%s%s", have.phi_tables ? ", oc_potential" : "",
+                 have.ep_returns && have.ep_returns_out ? ", copy of the episode returns" : "", regen ? ", oc_regen_layouts" : "",
+                 start ? "oc_reset_random" : "oc_reset", start && have.phi_tables ? ", oc_potential" : "", have.obs ? ", oc_encode_lossless" : "");
+    } else if (b->n_envs == 0) {
+        snprintf(out, out_size, "nothing to launch (no envs)");
+    } else if (p.path == TrainPlan::OBS) {
+        snprintf(out, out_size, "k_train_step_obs<MAXP=%d, T=%s, NWV=%d> unit=%d, G=%d, %zu B LDS", p.maxp, obs_dtype == OC_OBS_U8 ? "u8" : "f32",
+                 p.sh.nwv, p.sh.unit, p.sh.gmax, p.sh.smem);
+    } else if (p.lean) {
+        snprintf(out, out_size, "k_train_step1<UNIFORM=%s, MAXP=%d, LAY_LDS=%s>%s", tf(p.uniform), p.maxp, tf(p.lay_lds), then_obs);
+    } else {
+        snprintf(out, out_size, "k_train_step<UNIFORM=%s, EV=%s>%s", tf(p.uniform), tf(p.ev), then_obs);
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -937,27 +1034,35 @@ int oc_multi_agent_step(const OcBatch* b, void* d_state, const uint8_t* d_action
                         const double* d_phi_start, double reward_shaping_factor, double* d_shaped, uint8_t* d_done,
                         void* d_obs, int obs_dtype, int horizon, const OcStartSpec* start, const OcEventSink* events,
                         void* stream) {
-    const char* const who = "oc_multi_agent_step";
-    if (!d_done) return refuse(who, "d_done is required (it is the reset mask)");
-    TrainStep a = {b, 0, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off, d_phi_tables,
-                   d_phi_next, d_phi_cur, d_phi_start, reward_shaping_factor, d_shaped, d_done, d_obs, obs_dtype, horizon, start,
-                   {}, ev_args(events, nullptr, 1u), (hipStream_t)stream};
-    if (int rc = check_start(who, start, &a.sa, b)) return rc;
-    if (int rc = check_batch(b, &a.n_obj)) return rc;
-    // at most two pots and two players: the whole step in one kernel
-    const bool fused = b->max_pots >= 1 && b->max_pots <= 2 && (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0;
-    if (!d_state || !d_actions || !d_rewards || !d_flags || (fused && !d_shaped))
-        return refuse(who, fused ? "NULL state/actions/rewards/flags/shaped pointer" : "NULL state/actions/rewards/flags pointer");
-    if (fused && d_phi_tables && (!d_plan_blob || !d_plan_off || !d_phi_next || !d_phi_cur || !d_phi_start))
-        return refuse(who, "use_phi needs the plan tables and the three phi buffers");
-    if (int rc = check_horizon(who, horizon)) return rc;
-    if (fused && !aligned16(d_shaped)) return refuse(who, "d_shaped must be 16-byte aligned");
-    if (!fused) return train_step_general(a);
-    if (b->n_envs > 0) {
-        const TrainObsShape sh = train_obs_shape(a);
-        if (sh.nwv) return train_step_obs(a, sh);
-    }
-    return train_step_fused(a);
+    const EvArgs ea = ev_args(events, nullptr, 1u);
+    const TrainArrays have = train_arrays_of(d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
+                                             d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, d_shaped, d_done, d_obs, ev_on(ea));
+    const TrainPlan p = plan_train_step(b, have, obs_dtype, horizon, start);
+    if (p.rc != OC_OK) return p.rc;
+    const TrainStep a = {b, p.n_obj, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
+                         d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, reward_shaping_factor, d_shaped, d_done, d_obs, obs_dtype,
+                         horizon, start, p.sa, ea, (hipStream_t)stream};
+    if (p.path == TrainPlan::GENERAL) return train_step_general(a);
+    if (p.path == TrainPlan::OBS) return train_step_obs(a, p);
+    return train_step_fused(a, p);
+}
+
+int oc_multi_agent_plan(const OcBatch* b, int horizon, int with_obs, int obs_dtype, int use_phi, int event_sink, const OcStartSpec* start,
+                        char* out, size_t out_size) {
+    if (!out || out_size == 0) return fail(OC_EINVAL, "oc_multi_agent_plan: no output buffer");
+    out[0] = 0;
+    // the call VecOvercookedMultiAgent.step makes: every required array (aligned), the named optional ones
+    TrainArrays have = {};
+    have.state = have.actions = have.rewards = have.flags = have.shaped = have.shaped_aligned16 = have.done = true;
+    have.phi_tables = have.phi_rest = use_phi != 0;
+    have.ep_returns = have.ep_returns_out = true;
+    have.obs = with_obs != 0;
+    have.obs_aligned16 = true;
+    have.events = event_sink != 0;
+    const TrainPlan p = plan_train_step(b, have, obs_dtype, horizon, start);
+    if (p.rc != OC_OK) return p.rc;
+    describe_train_plan(b, p, have, obs_dtype, start, out, out_size);
+    return OC_OK;
 }
 
 int oc_regen_layouts(const OcBatch* b, uint16_t* d_layout_id, const uint8_t* d_mask, uint8_t mask_bits, const OcStartSpec* start,

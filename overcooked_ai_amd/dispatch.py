@@ -1,4 +1,5 @@
-"""Which rollout kernel instance serves which batch: the host side of oc_rollout_plan (include/oc_amd.h, ABI 6).
+"""Which rollout kernel instance serves which batch, and which path and kernel instance a training step takes: the host side of
+oc_rollout_plan and oc_multi_agent_plan (include/oc_amd.h, ABI 6).
 
 The answers are the plan oc_rollout_random makes of a call before it launches anything, put into words (the planner holds no
 launch and no device pointer), so this works on a host without a GPU.  `table()` is what tools/gen_dispatch_table.py writes to docs/DISPATCH.md and
@@ -30,6 +31,19 @@ def rollout_plan(table, n_envs, n_steps=4000, t0=0, horizon=400, options=_lib.OP
     rc = L.oc_rollout_plan(ctypes.byref(b), int(horizon), int(options), int(t0), int(n_steps), int(bool(with_outputs)),
                            int(event_sink), ctypes.byref(start) if start is not None else None, out, len(out))
     _lib.check(rc, "oc_rollout_plan")
+    return out.value.decode()
+
+
+def multi_agent_plan(table, n_envs, horizon=400, obs_dtype=_lib.OBS_F32, with_obs=True, use_phi=True, event_sink=0, start=None):
+    """The path and kernel instance `oc_multi_agent_step` runs for this table, batch size and set of arrays (text; up to and
+    including '>' the instance's name), or the library's refusal (OcAmdError).  obs_dtype: _lib.OBS_U8 / OBS_F32; event_sink: 0 or
+    1 (per-episode counters); start: None or the OcStartSpec the call would carry."""
+    L = _lib.load()
+    b = batch_for(table, n_envs)
+    out = ctypes.create_string_buffer(320)
+    rc = L.oc_multi_agent_plan(ctypes.byref(b), int(horizon), int(bool(with_obs)), int(obs_dtype), int(bool(use_phi)), int(event_sink),
+                               ctypes.byref(start) if start is not None else None, out, len(out))
+    _lib.check(rc, "oc_multi_agent_plan")
     return out.value.decode()
 
 

@@ -242,14 +242,35 @@ class VecOvercookedMultiAgent:
             self.phi_cur.copy_(self.phi_start[lid.long() & 0xFFFF] if lid is not None else self.phi_start.expand(self.n_envs))
         return self.observations()
 
+    def _call_args(self):
+        """What step() hands to oc_multi_agent_step beside the arrays every call has: (observation buffer or None, obs_dtype
+        code, OcStartSpec* or None — random starts: finished envs restart from drawn states in the same call —, OcEventSink* or
+        None)."""
+        v = self.venv
+        obs = self._obs_buffer() if self.obs_kind == "ppo" else None
+        code = {self._torch.uint8: self._lib.OBS_U8, self._torch.float32: self._lib.OBS_F32}[self.obs_dtype]
+        return obs, code, v._start_spec(), v._event_sink() if v.event_counts is not None else None
+
+    def plan(self):
+        """The path and kernel instance the next step() runs, in oc_multi_agent_plan's words (up to and including '>' the
+        instance's name): asked for this env's own batch and for the optional arrays step() itself would pass."""
+        import ctypes
+
+        v = self.venv
+        obs, code, start, sink = self._call_args()
+        out = ctypes.create_string_buffer(320)
+        rc = v.lib.oc_multi_agent_plan(v._bref, self.horizon, int(obs is not None), code, int(self.use_phi), int(sink is not None),
+                                       start, out, len(out))
+        self._lib.check(rc, "oc_multi_agent_plan")
+        return out.value.decode()
+
     def step(self, actions):
         """One batched training step, enqueued by a single C call (oc_multi_agent_step)."""
         v, torch = self.venv, self._torch
         if actions.dtype != torch.uint8 or actions.shape != (self.n_envs, 2) or not actions.is_contiguous() \
                 or actions.device != v.state.device:
             raise ValueError("actions must be a contiguous uint8 [n_envs, 2] tensor on %s" % v.device)
-        obs = self._obs_buffer() if self.obs_kind == "ppo" else None
-        code = {torch.uint8: self._lib.OBS_U8, torch.float32: self._lib.OBS_F32}[self.obs_dtype]
+        obs, code, start, sink = self._call_args()
         if self.use_phi:
             if self._phi_args is None:
                 v.potential(self.gamma, out=self.phi_next)  # builds and caches the tables
@@ -262,8 +283,7 @@ class VecOvercookedMultiAgent:
                        v._ep_ptr, self.ep_returns.data_ptr(), plan, off, tables, self.phi_next.data_ptr(),
                        self.phi_cur.data_ptr(), self.phi_start.data_ptr(), float(self.reward_shaping_factor),
                        self.shaped.data_ptr(), self.done.data_ptr(), obs.data_ptr() if obs is not None else None, code,
-                       self.horizon, v._start_spec(),  # random starts: finished envs restart from drawn states in the same call
-                       v._event_sink() if v.event_counts is not None else None)
+                       self.horizon, start, sink)
         self._lib.check(rc, "oc_multi_agent_step")
         v._advance(1)
         infos = {"sparse_r_by_agent": v.rewards[:, 0:2], "shaped_r_by_agent": v.rewards[:, 2:4], "flags": v.flags,

@@ -74,3 +74,4 @@ def select_kernel(env, kernel):
     assert kernel in (None, "step") + ROLLOUT_KERNELS, kernel
     for name in ROLLOUT_KERNELS[1:]:
         setattr(env, name, name == kernel)
+

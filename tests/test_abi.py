@@ -136,10 +136,20 @@ def test_argument_validation_without_gpu():
         # (the plan of a rollout is oc_rollout_random's: so is the name in its refusals)
         assert L.oc_rollout_plan(er, horizon, 1, 0, 8, 1, 0, None, text, len(text)) == -1
         assert L.oc_last_error().decode() == "oc_rollout_random: horizon must be in 1..65535"
+        # (... and the plan of a training step is oc_multi_agent_step's)
+        assert L.oc_multi_agent_plan(er, horizon, 1, 0, 0, 0, None, text, len(text)) == -1
+        assert L.oc_last_error().decode() == "oc_multi_agent_step: horizon must be in 1..65535"
         # ... and the general sequence of oc_multi_agent_step (a table of more than two pots) checks it too
         e.max_pots = 3
         assert calls["oc_multi_agent_step"]() == -1 and L.oc_last_error().decode() == "oc_multi_agent_step: horizon must be in 1..65535"
         e.max_pots = 1
+    # oc_multi_agent_plan: its own buffer, then every check of oc_multi_agent_step that its arguments can fail, under that name
+    assert L.oc_multi_agent_plan(er, 400, 1, 0, 0, 0, None, None, 0) == -1 and b"oc_multi_agent_plan: no output buffer" in L.oc_last_error()
+    assert L.oc_multi_agent_plan(None, 400, 1, 0, 0, 0, None, text, len(text)) == -1 and b"batch is NULL" in L.oc_last_error()
+    bad_start = _lib.OcStartSpec(0, 0, 1, 0, 0.0, 0, 5)  # (a layout range beyond the table of one)
+    assert L.oc_multi_agent_plan(er, 400, 1, 0, 0, 0, ctypes.byref(bad_start), text, len(text)) == -1
+    assert L.oc_last_error().decode().startswith("oc_multi_agent_step: ")
+    assert L.oc_multi_agent_plan(er, 400, 1, 0, 1, 0, None, text, len(text)) == 0 and text.value == b"nothing to launch (no envs)"
     # the measurement aid: argument checks before the launch, nothing to do for an empty job
     assert L.oc_output_stores_only(64, 8, None, None, 0, None) == -1 and b"no rewards array" in L.oc_last_error()
     assert L.oc_output_stores_only(64, 8, 4100, None, 0, None) == -1 and b"16-byte aligned" in L.oc_last_error()

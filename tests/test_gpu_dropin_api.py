@@ -247,6 +247,7 @@ def test_vec_multi_agent_random_start_states():
     spec = spec_from_name("coordination_ring")
     env = VecOvercookedMultiAgent(spec, n, horizon=horizon, reward_shaping_factor=1.0, use_phi=True, device=dev, seed=4,
                                   random_start_pos=True, rnd_obj_prob_thresh=0.4)
+    assert env.plan() == "k_train_step1<UNIFORM=true, MAXP=2, LAY_LDS=true> + oc_encode_lossless"
     orc = O.Oracle([O.mdp_from_layout_dict(spec.to_layout_dict())])
     pp = [potential_params(spec, 0.99)]
     st = orc.reset_random(orc.new_state(n), seed=4, epoch=0, random_start_pos=True, rnd_obj_prob_thresh=0.4)
@@ -295,7 +296,8 @@ def test_infinite_order_bonus_delivery():
 
 def test_vec_multi_agent_event_counters():
     """The batched training env keeps the per-agent event counters RLlib reports (rllib.py:453-483, env.py:382-401):
-    fused kernel (k_train_step) and the general sequence, against the oracle's event_infos summed per episode."""
+    fused kernel (k_train_step<UNIFORM=true, EV=true>) and the general sequence, against the oracle's event_infos summed per
+    episode."""
     import torch
 
     from oracle import oracle as O
@@ -305,10 +307,12 @@ def test_vec_multi_agent_event_counters():
     dev = torch.device("cuda:0")
     seven = LayoutSpec({"grid": "XPPPPPX\nO 1 2 O\nX     X\nXDPSPTX", "onion_time": 3, "tomato_time": 5,
                         "onion_value": 7, "tomato_value": 4})
-    for spec in (spec_from_name("cramped_room"), seven):
+    for spec, expect in ((spec_from_name("cramped_room"), "k_train_step<UNIFORM=true, EV=true> + oc_encode_lossless"),
+                         (seven, "sequence: oc_step, oc_shape_rewards, copy of the episode returns, oc_reset, oc_encode_lossless")):
         n, horizon = 1500, 30
         env = VecOvercookedMultiAgent(spec, n, horizon=horizon, use_phi=False, reward_shaping_factor=1.0, device=dev,
                                       track_events=True)
+        assert env.plan() == expect
         orc = O.Oracle([O.mdp_from_layout_dict(spec.to_layout_dict())])
         st = orc.reset(orc.new_state(n))
         counts = np.zeros((n, 25, 2), np.int64)

@@ -7,6 +7,7 @@ import pytest
 
 from conftest import GOLDEN
 from helpers import CANONICAL_5, random_packed_states, select_kernel
+from train_cases import sequence
 
 pytestmark = pytest.mark.gpu
 
@@ -695,7 +696,7 @@ def test_hip_graph_capture_of_step_and_encode(gpu):
 
 
 def test_hip_graph_capture_of_the_training_step(gpu):
-    """oc_multi_agent_step (k_train_step1 + k_encode: step, phi, shaped rewards, restart, observation) enqueues on the
+    """oc_multi_agent_step (k_train_step1 + oc_encode_lossless: step, phi, shaped rewards, restart, observation) enqueues on the
     caller's stream without synchronising: captured in a HIP graph and replayed with new actions it gives what the eager
     calls give — the (actions -> step -> observation) chain of a policy loop without per-kernel launches."""
     from overcooked_ai_amd.multi_agent import VecOvercookedMultiAgent
@@ -704,6 +705,7 @@ def test_hip_graph_capture_of_the_training_step(gpu):
     kw = dict(horizon=40, reward_shaping_factor=0.7, use_phi=True, obs_dtype=torch.uint8, device=gpu)
     env = VecOvercookedMultiAgent("cramped_room", n, **kw)
     ref = VecOvercookedMultiAgent("cramped_room", n, **kw)
+    assert env.plan() == ref.plan() == "k_train_step1<UNIFORM=true, MAXP=1, LAY_LDS=true> + oc_encode_lossless"
     acts = torch.zeros((n, 2), dtype=torch.uint8, device=gpu)
     side = torch.cuda.Stream(device=gpu)
     side.wait_stream(torch.cuda.current_stream(gpu))
@@ -727,19 +729,23 @@ def test_hip_graph_capture_of_the_training_step(gpu):
 
 
 def test_fused_training_step_equals_the_kernel_sequence(gpu):
-    """oc_multi_agent_step runs k_train_step (one kernel) for two-player tables with <= 2 pots and the sequence
+    """oc_multi_agent_step runs one kernel (k_train_step1; k_train_step for corridor's 126 cells; these batches of 3 000 envs
+    never k_train_step_obs) for two-player tables with <= 2 pots and the sequence
     oc_step -> oc_potential -> oc_shape_rewards -> copy -> oc_reset otherwise; both must produce identical states,
     rewards, flags, episode returns, potentials, shaped rewards and done masks, with and without use_phi, across
-    episode ends and illegal actions."""
+    episode ends and illegal actions.  Each table's plan is asserted by name."""
     from overcooked_ai_amd.layouts import LayoutSpec, LayoutTable, spec_from_name
     from overcooked_ai_amd.multi_agent import VecOvercookedMultiAgent
 
     seven = LayoutSpec({"grid": "XPPPPPX\nO 1 2 O\nX     X\nXDPSPTX", "onion_time": 3, "tomato_time": 5,
                         "onion_value": 7, "tomato_value": 4})
-    cases = [("cramped_room", None), ("coordination_ring", None), ("corridor", None), ("counter_circuit", None),
-             (LayoutTable([spec_from_name(nm) for nm in CANONICAL_5], pad_to=(9, 5)), 5), (seven, None)]
+    one, two = "k_train_step1<UNIFORM=true, MAXP=1, LAY_LDS=true>", "k_train_step1<UNIFORM=true, MAXP=2, LAY_LDS=true>"
+    cases = [("cramped_room", None, one), ("coordination_ring", None, two), ("corridor", None, "k_train_step<UNIFORM=true, EV=false>"),
+             ("counter_circuit", None, two),
+             (LayoutTable([spec_from_name(nm) for nm in CANONICAL_5], pad_to=(9, 5)), 5, "k_train_step1<UNIFORM=false, MAXP=2, LAY_LDS=true>"),
+             (seven, None, None)]  # (the sequence: its whole text, below)
     rng = np.random.default_rng(8)
-    for layouts, n_lay in cases:
+    for layouts, n_lay, expect in cases:
         for use_phi in (True, False):
             n = 3000
             lid = (np.arange(n) % n_lay).astype(np.uint16) if n_lay else None
@@ -748,6 +754,9 @@ def test_fused_training_step_equals_the_kernel_sequence(gpu):
             ref = VecOvercookedMultiAgent(layouts, n, horizon=23, reward_shaping_factor=0.37, use_phi=use_phi, device=gpu,
                                           layout_id=lid, seed=1)
             v = ref.venv
+            plan = env.plan()
+            want = expect + " + oc_encode_lossless" if expect else sequence(use_phi, "standard")
+            assert plan == want, (getattr(layouts, "layout_name", layouts), plan)
             env.venv.reset(random_start_pos=True, rnd_obj_prob_thresh=0.5)
             v.set_packed_state(env.venv.get_packed_state())
             if use_phi:
@@ -779,7 +788,9 @@ def test_fused_training_step_equals_the_kernel_sequence(gpu):
 
 def test_training_step_with_its_observation_in_one_kernel(gpu):
     """Single-layout batches of >= 32 768 envs run oc_multi_agent_step as ONE kernel (k_train_step_obs: transition, phi,
-    shaped rewards, restart AND the lossless observation).  The same envs over a table that holds the layout TWICE (a mixed
+    shaped rewards, restart AND the lossless observation) where a private image holds at least two envs — four of the five
+    cases here; asymmetric_advantages with f32 observations does not, and runs k_train_step1 and the observation kernel, as
+    the asserted plans say.  The same envs over a table that holds the layout TWICE (a mixed
     table: k_train_step1's per-env-layout instance + the generic observation kernel) must give identical states, rewards,
     flags, episode returns, potentials, shaped rewards, done masks and observations — u8 and f32, one and two pots, with
     and without use_phi, standard and drawn restarts, across episode ends, illegal actions and a ragged last workgroup."""
@@ -788,15 +799,20 @@ def test_training_step_with_its_observation_in_one_kernel(gpu):
 
     rng = np.random.default_rng(21)
     n = 128 * 256 + 232  # at least half of the CUs get a workgroup; the last workgroup is ragged
-    cases = [("cramped_room", torch.uint8, True, True), ("cramped_room", torch.float32, False, False),
-             ("coordination_ring", torch.uint8, True, False), ("asymmetric_advantages", torch.uint8, False, True),
-             ("asymmetric_advantages", torch.float32, True, True)]
-    for name, dt, use_phi, random_starts in cases:
+    # (9 x 5 f32: one env per private image — train_obs_shape declines, and k_train_step1 runs with the observation kernel)
+    cases = [("cramped_room", torch.uint8, True, True, "k_train_step_obs<MAXP=1, T=u8, NWV=16>"),
+             ("cramped_room", torch.float32, False, False, "k_train_step_obs<MAXP=1, T=f32, NWV=8>"),
+             ("coordination_ring", torch.uint8, True, False, "k_train_step_obs<MAXP=2, T=u8, NWV=8>"),
+             ("asymmetric_advantages", torch.uint8, False, True, "k_train_step_obs<MAXP=2, T=u8, NWV=8>"),
+             ("asymmetric_advantages", torch.float32, True, True, "k_train_step1<UNIFORM=true, MAXP=2, LAY_LDS=true> + oc_encode_lossless")]
+    for name, dt, use_phi, random_starts, expect in cases:
         spec = spec_from_name(name)
         kw = dict(horizon=11, reward_shaping_factor=0.37, use_phi=use_phi, device=gpu, obs_dtype=dt, seed=5,
                   random_start_pos=random_starts, rnd_obj_prob_thresh=0.4 if random_starts else 0.0)
         one = VecOvercookedMultiAgent(spec, n, **kw)
         two = VecOvercookedMultiAgent(LayoutTable([spec, spec]), n, layout_id=(np.arange(n) % 2).astype(np.uint16), **kw)
+        assert one.plan().startswith(expect), (name, dt, one.plan())
+        assert two.plan() == "k_train_step1<UNIFORM=false, MAXP=2, LAY_LDS=true> + oc_encode_lossless", (name, dt, two.plan())
         one.venv.reset(random_start_pos=True, rnd_obj_prob_thresh=0.5)
         two.venv.set_packed_state(one.venv.get_packed_state())
         if use_phi:

@@ -173,6 +173,8 @@ def test_sharded_multi_agent_equals_the_unsharded_training_env(gpu):
               rnd_obj_prob_thresh=0.3, seed=13)
     whole = VecOvercookedMultiAgent("asymmetric_advantages", n, device=gpu, env_offset=500, **kw)
     sh = ShardedVecOvercookedMultiAgent("asymmetric_advantages", n, devices=[gpu, gpu, gpu], env_offset=500, **kw)
+    for ma in [whole] + sh.agents:
+        assert ma.plan() == "k_train_step1<UNIFORM=true, MAXP=2, LAY_LDS=true> + oc_encode_lossless"
     o0, o1 = whole.reset(), sh.reset()
     sh.synchronize()
     assert np.array_equal(_cat(o1, 0), o0.cpu().numpy())
