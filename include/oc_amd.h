@@ -645,6 +645,35 @@ int oc_rollout_plan(const OcBatch* batch, int horizon, uint32_t options, int64_t
 int oc_multi_agent_plan(const OcBatch* batch, int horizon, int with_obs, int obs_dtype, int use_phi, int event_sink,
                         const OcStartSpec* start, char* out, size_t out_size);
 
+/*
+ * oc_observation_plan (ABI 6: an entry point added beside the others, as oc_multi_agent_plan was) — which kernel instance
+ * oc_encode_lossless (n_steps == 0) or oc_rollout_encode (n_steps >= 1) would launch for this batch, as text; up to and including
+ * '>' the text is the instance's name and stable:
+ *   "k_encode_uniform<T=u8> unit=4, upg=4, grid=768, 47824 B LDS"       one layout, u8: envs per template, templates per group
+ *   "k_encode<T=f32, LAY_LDS=true> epb=4, grid=16384, 37696 B LDS"       any table, u8 or f32: envs per workgroup
+ *   "k_rollout_encode<MAXP=2, FAST=3, T=u8, NW=8> unit=4, G=4, 120336 B LDS, budget 158528 B (queried)"
+ *                                                  one layout, at most two pots and 48 cells, u8 or f32, a batch that gives every
+ *                                                  CU a workgroup (or OC_OPT_ONE_KERNEL): envs per template and per LDS image
+ *   "step by step: oc_rollout_random + k_encode_uniform<T=u8> ..."       every other oc_rollout_encode call: per step the one-step
+ *   "step by step: oc_step + k_encode<T=f32, LAY_LDS=true> ..."          entry point (oc_step with caller actions), then
+ *                                                                       oc_encode_lossless, whose instance follows
+ *   "nothing to launch (no envs)" / "nothing to launch (no steps)"
+ * Both entry points plan a call before they launch anything (their argument checks, then every choice) and launch from that
+ * plan; this is the same plan put into words: every check applies (a refusal returns its code, with the entry point's own
+ * message in oc_last_error), the code that answers is told which arrays a call has, not where they are, and holds no launch.
+ * The LDS budget k_rollout_encode's shape is chosen within is asked of the runtime ("queried"); on a host without a GPU the plan
+ * assumes 144 KiB and says so ("fallback"; the device's SIMD count then defaults to MI355X's 1 024).
+ * The call described has a state and a 16-byte aligned observation array (obs_step_stride a multiple of 16), env_offset equal
+ * to the start spec's, and
+ *   with_actions  1: d_actions is given; 0: NULL (the random policy)
+ *   with_outputs  1: d_rewards and d_flags are given; 0: both NULL
+ *   start         NULL or the start-state description the call would carry
+ *   out, out_size caller's text buffer (>= 256 bytes holds every answer)
+ * horizon, options, with_actions, with_outputs and start are not read when n_steps == 0.
+ */
+int oc_observation_plan(const OcBatch* batch, int obs_dtype, int horizon, uint32_t options, int n_steps, int with_actions,
+                        int with_outputs, const OcStartSpec* start, char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

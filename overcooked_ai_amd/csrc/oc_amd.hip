@@ -18,7 +18,11 @@
 //   shaping.hpp         OvercookedMultiAgent.step reward, rllib.py:306-329: k_shape_rewards
 //   train_obs.hpp       the training step with its observation in one kernel: k_train_step_obs
 //   stores_only.hpp     the output stores of a rollout and nothing else: k_output_stores_only (oc_output_stores_only)
-//   this file           launch dispatch and the extern "C" entry points declared in include/oc_amd.h
+//   observation_plan.hpp  host only: the observation geometry and the plans of oc_encode_lossless / oc_rollout_encode
+//   this file           launch dispatch and the extern "C" entry points declared in include/oc_amd.h: oc_rollout_random,
+//                       oc_multi_agent_step, oc_encode_lossless and oc_rollout_encode plan a call (checks, then choices; no
+//                       launch, no device address), then launch from the plan; oc_rollout_plan, oc_multi_agent_plan and
+//                       oc_observation_plan put the plans into words
 //
 // Execution model: one lane per env, 64-lane wavefronts, 256-lane workgroups.  This is integer /
 // indexing work (no MFMA).  Per-env state arrives as coalesced 16-byte planes (1 KiB per wavefront
@@ -143,16 +147,9 @@ int check_start(const char* who, const OcStartSpec* sp, StartArgs* sa, const OcB
 }
 inline bool obs_dtype_ok(int obs_dtype) { return obs_dtype == OC_OBS_U8 || obs_dtype == OC_OBS_F32; }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-int check_obs(const char* who, int obs_dtype, const void* d_obs) {
+int check_obs(const char* who, int obs_dtype, bool obs_aligned16) {
     if (!obs_dtype_ok(obs_dtype)) return refuse(who, "bad obs_dtype");
-    return aligned16(d_obs) ? OC_OK : refuse(who, "d_obs must be 16-byte aligned");
-}
-
-// envs per observation template: the fewest whose bytes are a multiple of 16 (1, 2 or 4)
-inline int envs_per_template(size_t env_bytes) {
-    int unit = 1;
-    while (((env_bytes * unit) & 15u) != 0) unit *= 2;
-    return unit;
+    return obs_aligned16 ? OC_OK : refuse(who, "d_obs must be 16-byte aligned");
 }
 
 // tuning builds: OC_STEP_NO_LEAN sends every single step to the general kernels (k_step3, k_train_step)
@@ -160,6 +157,8 @@ inline bool step_no_lean() {
     static const bool v = tuning_set("OC_STEP_NO_LEAN");
     return v;
 }
+
+#include "observation_plan.hpp"
 
 EvArgs ev_args(const OcEventSink* sink, uint64_t* d_events, uint32_t clear_on_done = 0) {
     EvArgs ea = {d_events, nullptr, nullptr, clear_on_done};
@@ -824,10 +823,9 @@ bool train_obs_wanted(const OcBatch* b, int n_obj, const TrainArrays& have, int 
 TrainObsShape train_obs_shape(const OcBatch* b, int n_obj, const TrainArrays& have, int obs_dtype) {
     TrainObsShape sh;
     if (!train_obs_wanted(b, n_obj, have, obs_dtype)) return sh;
-    const size_t elem = obs_dtype == OC_OBS_U8 ? 1 : 4;
-    const size_t env_bytes = (size_t)2 * b->width * b->height * OC_NUM_LAYERS * elem;
-    const int unit = envs_per_template(env_bytes);
-    const size_t fixed = (size_t)n_obj * BLOCK * 16 + env_bytes * unit + (size_t)4 * BLOCK * 16;
+    const ObsGeometry geo(b->width, b->height, obs_dtype);
+    const int unit = geo.unit;
+    const size_t fixed = (size_t)n_obj * BLOCK * 16 + geo.env_bytes * unit + (size_t)4 * BLOCK * 16;
     const size_t budget = 150 * 1024;
     // wavefronts per workgroup: 16 (4 owners, 4 helpers, 8 encoders; round 6) for u8 observations whose private images
     // still hold >= 6 envs then (cramped_room-sized grids: the encode loop there is bound by what the wavefronts of a
@@ -836,14 +834,13 @@ TrainObsShape train_obs_shape(const OcBatch* b, int n_obj, const TrainArrays& ha
     for (int w : {16, 8}) {
         if (forced_w && w != forced_w) continue;
         if (!forced_w && w == 16 && obs_dtype != OC_OBS_U8) continue;
-        int g = fixed < budget ? (int)((budget - fixed) / ((size_t)w * env_bytes)) : 0;
-        if (g > 64) g = 64;
+        int g = geo.envs_per_image(fixed, budget, w);
         if (forced_g > 0 && forced_g < g) g = forced_g;
-        g -= g % unit;
+        g = geo.whole_units(g);
         if (w == 16 && g < 6 && !forced_w) continue;  // (measured: 7-env images 22.0 -> 19.5 us, 3-env images 31.8 -> 37.6)
         if (g >= unit && g >= 2) {  // (one env per image — 9x5 f32 — measured slower than the two kernels: 123-127 vs 116-122 us)
             sh.unit = unit; sh.nwv = w; sh.gmax = g;
-            sh.smem = fixed + (size_t)w * g * env_bytes;
+            sh.smem = fixed + (size_t)w * g * geo.env_bytes;
             break;
         }
     }
@@ -1098,66 +1095,113 @@ int oc_reset_random(const OcBatch* b, void* d_state, const uint8_t* d_mask, floa
     return check_launch("oc_reset_random");
 }
 
-int oc_encode_lossless(const OcBatch* b, const void* d_state, void* d_obs, int obs_dtype, int horizon, void* stream) {
-    int n_obj = 0;
-    if (int rc = check_batch(b, &n_obj)) return rc;
-    if (!d_state || !d_obs) return fail(OC_EINVAL, "oc_encode_lossless: NULL pointer");
-    if (int rc = check_obs("oc_encode_lossless", obs_dtype, d_obs)) return rc;
-    if (b->n_envs == 0) return OC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const int n_planes = 1 + n_obj;
-    const int cells = b->width * b->height;
-    const size_t elem = obs_dtype == OC_OBS_U8 ? 1 : 4;
-    const size_t env_bytes = (size_t)2 * cells * OC_NUM_LAYERS * elem;
-    // envs per workgroup: fill ~40 KiB of LDS; a multiple of 4 keeps every block's byte range 16-byte aligned
-    int epb = (int)((size_t)enc_lds_budget() / (env_bytes + (size_t)n_planes * 16));
-    if (epb >= 4) epb &= ~3;
-    if (epb < 1) epb = 1;
-    if (epb > 32) epb = 32;
-    if (obs_dtype == OC_OBS_U8 && (epb & 3) != 0 && (env_bytes & 15u) != 0) {
-        epb = 4;  // u8 rows of odd cell counts are only 4-byte multiples: keep blocks 16-byte aligned
-    }
-    const size_t smem = (size_t)epb * n_planes * 16 + (((size_t)epb * env_bytes + 15) & ~(size_t)15);
-    if (smem > 160 * 1024) return fail(OC_EINVAL, "oc_encode_lossless: grid too large for LDS staging");
-    // single layout + u8: the persistent template kernel (27.4 vs 32.4 us for the generic kernel on 65 536
-    // asymmetric_advantages envs).  f32 is HBM-write bound either way: through the template kernel 5x4 grids gain when
-    // encodes run back to back (43.5 vs 54.4 us) but not inside a training loop (43.5 vs 41.9 us), 9x5 is 112 us both ways
-    if (b->n_layouts == 1 && obs_dtype == OC_OBS_U8) {
-        const int unit = envs_per_template(env_bytes);
-        const size_t unit_bytes = env_bytes * unit;
-        int upg = (int)(enc_uniform_budget(env_bytes) / unit_bytes);     // units per group
-        if (upg < 1) upg = 1;
-        if (upg * unit > 32) upg = 32 / unit > 0 ? 32 / unit : 1;
-        const size_t smem_u = unit_bytes + unit_bytes * upg + (size_t)unit * upg * n_planes * 16;
-        if (smem_u <= 150 * 1024) {
-            const int64_t n_groups = (b->n_envs + (int64_t)unit * upg - 1) / ((int64_t)unit * upg);
-            int per_cu = (int)((150 * 1024) / (smem_u + 512));
-            if (per_cu > 8) per_cu = 8;
-            if (per_cu < 1) per_cu = 1;
-            int64_t grid_u = (simd_count() / 4) * per_cu;
-            if (grid_u > n_groups) grid_u = n_groups;
-            if (!want_lds(k_encode_uniform<uint8_t>, smem_u)) return check_launch("oc_encode_lossless");
-            hipLaunchKernelGGL((k_encode_uniform<uint8_t>), dim3((unsigned)grid_u), dim3(BLOCK), smem_u, s, b->d_layouts,
-                               (const uint4*)d_state, (uint8_t*)d_obs, b->n_envs, b->width, b->height, n_planes, unit, upg, horizon);
-            return check_launch("oc_encode_lossless");
-        }
-    }
-    const unsigned grid = (unsigned)((b->n_envs + epb - 1) / epb);
-    const bool lds = b->n_layouts <= LDS_LAYOUT_MAX;
-#define LAUNCH_ENC(T, LDSFLAG)                                                                                        \
-    do {                                                                                                              \
-        if (!want_lds(k_encode<T, LDSFLAG>, smem)) break;                                                             \
-        hipLaunchKernelGGL((k_encode<T, LDSFLAG>), dim3(grid), dim3(BLOCK), smem, s, b->d_layouts, b->n_layouts,      \
-                           b->d_layout_id, (const uint4*)d_state, (T*)d_obs, b->n_envs, b->width, b->height,          \
-                           n_planes, epb, horizon);                                                                   \
-    } while (0)
-    if (obs_dtype == OC_OBS_U8) {
-        if (lds) LAUNCH_ENC(uint8_t, true); else LAUNCH_ENC(uint8_t, false);
+}  // extern "C"
+
+namespace {
+// ---- the observation paths: oc_encode_lossless and oc_rollout_encode plan a call first (observation_plan.hpp: every check, every
+//      choice; no launch, no device memory), then launch from that plan — or, by oc_observation_plan, describe it
+int launch_encode(const EncodePlan& p, const OcBatch* b, const void* d_state, void* d_obs, int horizon, hipStream_t s) {
+    const auto generic = [&](auto t, auto lay_lds) {
+        using T = decltype(t);
+        constexpr bool LAY_LDS = decltype(lay_lds)::value;
+        if (!want_lds(k_encode<T, LAY_LDS>, p.smem)) return;
+        hipLaunchKernelGGL((k_encode<T, LAY_LDS>), dim3(p.grid), dim3(BLOCK), p.smem, s, b->d_layouts, b->n_layouts, b->d_layout_id,
+                           (const uint4*)d_state, (T*)d_obs, b->n_envs, b->width, b->height, p.n_planes, p.epb, horizon);
+    };
+    if (p.kernel == EncodePlan::UNIFORM) {
+        if (want_lds(k_encode_uniform<uint8_t>, p.smem))
+            hipLaunchKernelGGL((k_encode_uniform<uint8_t>), dim3(p.grid), dim3(BLOCK), p.smem, s, b->d_layouts, (const uint4*)d_state,
+                               (uint8_t*)d_obs, b->n_envs, b->width, b->height, p.n_planes, p.unit, p.upg, horizon);
+    } else if (!p.f32) {
+        if (p.lay_lds) generic(uint8_t(), std::true_type()); else generic(uint8_t(), std::false_type());
     } else {
-        if (lds) LAUNCH_ENC(float, true); else LAUNCH_ENC(float, false);
+        if (p.lay_lds) generic(float(), std::true_type()); else generic(float(), std::false_type());
     }
-#undef LAUNCH_ENC
     return check_launch("oc_encode_lossless");
+}
+
+// What a workgroup of the k_rollout_encode instances that would serve the batch may ask for on top of their static LDS (160 KiB
+// per CU; the instances of one FAST and T keep the same, the eight-wavefront ones 32 bytes more)
+LdsBudget rollout_encode_lds(const OcBatch* b, int obs_dtype) {
+    const bool fast = b && rollout_encode_fast(b);
+    const void* const kernel = obs_dtype == OC_OBS_U8
+        ? (fast ? (const void*)k_rollout_encode<2, 3, uint8_t, 4> : (const void*)k_rollout_encode<2, 0, uint8_t, 4>)
+        : (fast ? (const void*)k_rollout_encode<2, 3, float, 4> : (const void*)k_rollout_encode<2, 0, float, 4>);
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) { (void)hipGetLastError(); return lds_budget_fallback(); }
+    return {(size_t)160 * 1024 - (size_t)fa.sharedSizeBytes - 64, true};
+}
+
+// The arrays and scalars of one oc_rollout_encode call
+struct RolloutEncodeCall {
+    const OcBatch* b;
+    void* d_state;
+    const uint8_t* d_actions;
+    float* d_rewards;
+    uint8_t* d_flags;
+    float* d_ep_returns;
+    void* d_obs;
+    int obs_dtype;
+    int64_t obs_step_stride;
+    int horizon;
+    uint32_t step_options;  // OC_OPT_AUTO_RESET or nothing
+    uint64_t seed;
+    int64_t env_offset, t0;
+    int n_steps;
+    const OcStartSpec* start;
+    hipStream_t stream;
+};
+
+// the whole trajectory in one launch (k_rollout_encode)
+int launch_rollout_encode(const RolloutEncodePlan& p, const RolloutEncodeCall& c) {
+    const OcBatch* b = c.b;
+    const auto go = [&](auto fast, auto t, auto nw) {
+        using T = decltype(t);
+        constexpr int FAST = decltype(fast)::value, NW = decltype(nw)::value;
+        if (!want_lds(k_rollout_encode<2, FAST, T, NW>, p.smem)) return;
+        hipLaunchKernelGGL((k_rollout_encode<2, FAST, T, NW>), dim3(grid_for(b->n_envs)), dim3(NW * 64), p.smem, c.stream, b->d_layouts,
+                           (uint4*)c.d_state, c.d_actions, (float4*)c.d_rewards, c.d_flags, (float4*)c.d_ep_returns, (uint8_t*)c.d_obs,
+                           c.obs_step_stride, b->n_envs, b->width, b->height, p.n_obj, c.horizon, c.step_options, (uint32_t)c.seed,
+                           (uint32_t)(c.seed >> 32), c.env_offset, c.t0, c.n_steps, p.unit, p.g, p.sa);
+    };
+    const auto go_t = [&](auto fast, auto nw) { if (!p.f32) go(fast, uint8_t(), nw); else go(fast, float(), nw); };
+    using std::integral_constant;
+    if (p.nw == 8) {
+        if (p.fast) go_t(integral_constant<int, 3>(), integral_constant<int, 8>()); else go_t(integral_constant<int, 0>(), integral_constant<int, 8>());
+    } else {
+        if (p.fast) go_t(integral_constant<int, 3>(), integral_constant<int, 4>()); else go_t(integral_constant<int, 0>(), integral_constant<int, 4>());
+    }
+    return check_launch("oc_rollout_encode");
+}
+
+// every other table: the same result from the one-step kernels, step by step
+int rollout_encode_step_by_step(const RolloutEncodeCall& c) {
+    const OcBatch* b = c.b;
+    for (int k = 0; k < c.n_steps; ++k) {
+        const int64_t off = (int64_t)k * b->n_envs;
+        OcStartSpec sk;
+        if (c.start) { sk = *c.start; sk.epoch = c.start->epoch + (uint32_t)k; }  // a restart at step k draws from epoch + k
+        const OcStartSpec* spk = c.start ? &sk : nullptr;
+        int rc;
+        if (c.d_actions)
+            rc = oc_step(b, c.d_state, c.d_state, c.d_actions + 2 * off, c.d_rewards + 4 * off, c.d_flags + off, c.d_ep_returns, nullptr,
+                         c.horizon, c.step_options, spk, nullptr, c.stream);
+        else
+            rc = oc_rollout_random(b, c.d_state, c.d_rewards ? c.d_rewards + 4 * off : nullptr, c.d_flags ? c.d_flags + off : nullptr,
+                                   c.d_ep_returns, c.horizon, c.step_options, c.seed, c.env_offset, c.t0 + k, 1, spk, nullptr, c.stream);
+        if (rc) return rc;
+        if ((rc = oc_encode_lossless(b, c.d_state, (uint8_t*)c.d_obs + (int64_t)k * c.obs_step_stride, c.obs_dtype, c.horizon, c.stream))) return rc;
+    }
+    return OC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int oc_encode_lossless(const OcBatch* b, const void* d_state, void* d_obs, int obs_dtype, int horizon, void* stream) {
+    const EncodePlan p = plan_encode(b, obs_dtype, d_state != nullptr, d_obs != nullptr, aligned16(d_obs));
+    if (p.rc != OC_OK || p.kernel == EncodePlan::NOTHING) return p.rc;
+    return launch_encode(p, b, d_state, d_obs, horizon, (hipStream_t)stream);
 }
 
 int oc_step_encode(const OcBatch* b, void* d_state, const uint8_t* d_actions, float* d_rewards, uint8_t* d_flags,
@@ -1166,7 +1210,7 @@ int oc_step_encode(const OcBatch* b, void* d_state, const uint8_t* d_actions, fl
     int n_obj = 0;
     if (int rc = check_batch(b, &n_obj)) return rc;
     if (!d_state || !d_actions || !d_rewards || !d_flags || !d_obs) return fail(OC_EINVAL, "oc_step_encode: NULL pointer");
-    if (int rc = check_obs("oc_step_encode", obs_dtype, d_obs)) return rc;
+    if (int rc = check_obs("oc_step_encode", obs_dtype, aligned16(d_obs))) return rc;
     if (int rc = check_horizon("oc_step_encode", horizon)) return rc;
     StartArgs sa;
     if (int rc = check_start("oc_step_encode", start, &sa, b)) return rc;
@@ -1184,107 +1228,36 @@ int oc_rollout_encode(const OcBatch* b, void* d_state, const uint8_t* d_actions,
                       float* d_ep_returns, void* d_obs, int obs_dtype, int64_t obs_step_stride, int horizon,
                       uint32_t options, uint64_t seed, int64_t env_offset, int64_t t0, int n_steps,
                       const OcStartSpec* start, void* stream) {
-    int n_obj = 0;
-    if (int rc = check_batch(b, &n_obj)) return rc;
-    StartArgs sa;
-    if (int rc = check_start("oc_rollout_encode", start, &sa, b)) return rc;
-    if (!d_state || !d_obs) return fail(OC_EINVAL, "oc_rollout_encode: NULL state / observation pointer");
-    if (!obs_dtype_ok(obs_dtype)) return fail(OC_EINVAL, "oc_rollout_encode: bad obs_dtype");
-    if (!aligned16(d_obs) || obs_step_stride < 0 || (obs_step_stride & 15) != 0)
-        return fail(OC_EINVAL, "oc_rollout_encode: d_obs and obs_step_stride must be multiples of 16 bytes");
-    if (int rc = check_horizon("oc_rollout_encode", horizon)) return rc;
-    if (n_steps < 0 || n_steps > (1 << 30)) return fail(OC_EINVAL, "oc_rollout_encode: n_steps must be in 0..2^30");
-    if (options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_KERNEL))
-        return fail(OC_EINVAL, "oc_rollout_encode: options other than OC_OPT_AUTO_RESET / OC_OPT_ONE_KERNEL");
-    if (d_actions && (!d_rewards || !d_flags)) return fail(OC_EINVAL, "oc_rollout_encode: caller actions need the rewards and flags arrays");
-    if (start && start->env_offset != env_offset)  // (both paths below: the one-step fallback would refuse it, the single kernel must too)
-        return fail(OC_EINVAL, "oc_rollout_encode: start.env_offset differs from env_offset");
-    if (b->n_envs == 0 || n_steps == 0) return OC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    // one layout, u8 observations, at most two pots: the whole trajectory in one launch (k_rollout_encode).  The LDS of
-    // a workgroup holds the cell words of its 256 envs, the template, the headers and one image per wavefront.
-    const int cells = b->width * b->height;
-    const size_t env_bytes = (size_t)2 * cells * OC_NUM_LAYERS * (obs_dtype == OC_OBS_U8 ? 1 : 4);
-    // It keeps 256 envs per CU on chip and is bound by what one CU's four wavefronts can encode per step (~27 us for
-    // 9x5), so it pays once every CU has a workgroup: 30 us vs 37 us per step at 65 536 envs, but 27 us vs 18 us at 16 384
-    // (a single step is a wash against the two one-step kernels — 36.4 vs 37.2 us on 9x5, 25.1 vs 24.4 us on 5x4 — and
-    // stays with them unless OC_OPT_ONE_KERNEL asks)
-    const bool fills_gpu = b->n_envs >= (simd_count() / 4) * 192 && n_steps >= 2;
-    const uint32_t step_options = options & (uint32_t)OC_OPT_AUTO_RESET;
-    if ((fills_gpu || (options & OC_OPT_ONE_KERNEL)) && b->n_layouts == 1 && b->max_pots >= 1 && b->max_pots <= 2 && n_obj <= 3) {
-        const int unit = envs_per_template(env_bytes);
-        const size_t cell_bytes = (size_t)n_obj * 16 * BLOCK * sizeof(uint16_t);
-        const size_t fixed = cell_bytes + env_bytes * unit + (size_t)BLOCK * 16 + RE_LIST_BYTES;
-        const bool fast = (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0 && cells <= 64;
-        // what a workgroup may ask for on top of the kernel's static LDS (160 KiB per CU)
-        auto dynamic_lds = [](const void* kernel) {
-            hipFuncAttributes fa;
-            if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) { (void)hipGetLastError(); return (size_t)(144 * 1024); }
-            return (size_t)160 * 1024 - (size_t)fa.sharedSizeBytes - 64;  // (the eight-wavefront instances keep 32 bytes more)
-        };
-        const size_t budget = obs_dtype == OC_OBS_U8
-            ? (fast ? dynamic_lds((const void*)k_rollout_encode<2, 3, uint8_t, 4>) : dynamic_lds((const void*)k_rollout_encode<2, 0, uint8_t, 4>))
-            : (fast ? dynamic_lds((const void*)k_rollout_encode<2, 3, float, 4>) : dynamic_lds((const void*)k_rollout_encode<2, 0, float, 4>));
-        // eight wavefronts (four of them helpers that only encode) when eight images of at least 8 envs fit: small grids,
-        // where four wavefronts cannot encode 256 envs in the time HBM takes them (5x4 u8: 14.4 vs 17.4 us per step); 9x5
-        // is at the write ceiling either way (30.1 vs 30.4 us), f32 loses with one-env images (128 vs 117 us)
-        static const int forced_nw = tuning_int("OC_ROLLOUT_ENCODE_WAVES", 0);
-        // round 6: u8 observations take eight wavefronts down to 4-env images — a wavefront that is issuing its image's stores into a
-        // busy store path is not building the next one, and eight of them leave the path idle less often (65 536 envs, us per step,
-        // four vs eight: 9x5 29.2 -> 27.6-28.3, 8x5 26.1 -> 24.2, 5x5 16.1 -> 15.4; profiles/r06_rollout_encode_ablation.txt)
-        const int min_g8 = obs_dtype == OC_OBS_U8 ? 4 : 8;
-        int nw = 8;
-        int gmax = fixed < budget ? (int)((budget - fixed) / (nw * env_bytes)) : 0;
-        if (((gmax < min_g8 || gmax < unit) && forced_nw != 8) || forced_nw == 4) {
-            nw = 4;
-            gmax = fixed < budget ? (int)((budget - fixed) / (nw * env_bytes)) : 0;
-        }
-        if (gmax > 64) gmax = 64;
-        if (gmax >= unit) {
-            const int span = nw == 8 ? 32 : 64;                  // envs one wavefront encodes per step
-            const int parts = (span + gmax - 1) / gmax;          // its sub-groups, as even as the budget allows
-            int g = (span + parts - 1) / parts;
-            g = (g + unit - 1) / unit * unit;
-            if (g > gmax) g = gmax / unit * unit;
-            static const int forced_reg = tuning_int("OC_ROLLOUT_ENCODE_G", 0);
-            if (forced_reg > 0 && forced_reg <= g && forced_reg % unit == 0) g = forced_reg;
-            const size_t smem = fixed + (size_t)nw * g * env_bytes;
-            const dim3 grid(grid_for(b->n_envs));
-#define GORE(FAST, T, NW)                                                                                              \
-    do {                                                                                                               \
-        if (!want_lds(k_rollout_encode<2, FAST, T, NW>, smem)) break;                                                  \
-        hipLaunchKernelGGL((k_rollout_encode<2, FAST, T, NW>), grid, dim3(NW * 64), smem, s, b->d_layouts,             \
-                           (uint4*)d_state, d_actions, (float4*)d_rewards, d_flags, (float4*)d_ep_returns,             \
-                           (uint8_t*)d_obs, obs_step_stride, b->n_envs, b->width, b->height, n_obj, horizon,           \
-                           step_options, (uint32_t)seed, (uint32_t)(seed >> 32), env_offset, t0, n_steps, unit, g, sa); \
-    } while (0)
-#define GORE_T(FAST, NW)                                                                                               \
-    do {                                                                                                               \
-        if (obs_dtype == OC_OBS_U8) GORE(FAST, uint8_t, NW); else GORE(FAST, float, NW);                               \
-    } while (0)
-            if (nw == 8) { if (fast) GORE_T(3, 8); else GORE_T(0, 8); }
-            else { if (fast) GORE_T(3, 4); else GORE_T(0, 4); }
-#undef GORE_T
-#undef GORE
-            return check_launch("oc_rollout_encode");
-        }
+    const RolloutEncodeArrays have = {d_state != nullptr, d_actions != nullptr, d_rewards != nullptr, d_flags != nullptr, d_obs != nullptr,
+                                      aligned16(d_obs) && obs_step_stride >= 0 && (obs_step_stride & 15) == 0};
+    const RolloutEncodePlan p = plan_rollout_encode(b, have, obs_dtype, horizon, options, env_offset, n_steps, start, rollout_encode_lds(b, obs_dtype));
+    if (p.rc != OC_OK || p.path == RolloutEncodePlan::NOTHING) return p.rc;
+    const RolloutEncodeCall c = {b, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_obs, obs_dtype, obs_step_stride, horizon,
+                                 options & (uint32_t)OC_OPT_AUTO_RESET, seed, env_offset, t0, n_steps, start, (hipStream_t)stream};
+    if (p.path == RolloutEncodePlan::ONE_KERNEL) return launch_rollout_encode(p, c);
+    return rollout_encode_step_by_step(c);
+}
+
+int oc_observation_plan(const OcBatch* b, int obs_dtype, int horizon, uint32_t options, int n_steps, int with_actions, int with_outputs,
+                        const OcStartSpec* start, char* out, size_t out_size) {
+    if (!out || out_size == 0) return fail(OC_EINVAL, "oc_observation_plan: no output buffer");
+    out[0] = 0;
+    if (n_steps == 0) {  // oc_encode_lossless of the batch: a state and an aligned observation array
+        const EncodePlan p = plan_encode(b, obs_dtype, true, true, true);
+        if (p.rc == OC_OK) describe_encode_plan(p, out, out_size);
+        return p.rc;
     }
-    // every other table: the same result from the one-step kernels, step by step
-    for (int k = 0; k < n_steps; ++k) {
-        const int64_t off = (int64_t)k * b->n_envs;
-        OcStartSpec sk;
-        if (start) { sk = *start; sk.epoch = start->epoch + (uint32_t)k; }  // a restart at step k draws from epoch + k
-        const OcStartSpec* spk = start ? &sk : nullptr;
-        int rc;
-        if (d_actions)
-            rc = oc_step(b, d_state, d_state, d_actions + 2 * off, d_rewards + 4 * off, d_flags + off, d_ep_returns, nullptr,
-                         horizon, step_options, spk, nullptr, stream);
-        else
-            rc = oc_rollout_random(b, d_state, d_rewards ? d_rewards + 4 * off : nullptr, d_flags ? d_flags + off : nullptr,
-                                   d_ep_returns, horizon, step_options, seed, env_offset, t0 + k, 1, spk, nullptr, stream);
-        if (rc) return rc;
-        if ((rc = oc_encode_lossless(b, d_state, (uint8_t*)d_obs + (int64_t)k * obs_step_stride, obs_dtype, horizon, stream))) return rc;
+    // the call oc_rollout_encode would get: a state, an aligned trajectory buffer, the named arrays, the env offset of the start spec
+    const RolloutEncodeArrays have = {true, with_actions != 0, with_outputs != 0, with_outputs != 0, true, true};
+    const RolloutEncodePlan p = plan_rollout_encode(b, have, obs_dtype, horizon, options, start ? start->env_offset : 0, n_steps, start,
+                                                    rollout_encode_lds(b, obs_dtype));
+    if (p.rc != OC_OK) return p.rc;
+    EncodePlan one_step;
+    if (p.path == RolloutEncodePlan::STEP_BY_STEP) {
+        one_step = plan_encode(b, obs_dtype, true, true, true);
+        if (one_step.rc != OC_OK) return one_step.rc;
     }
+    describe_rollout_encode_plan(p, have.actions, one_step, out, out_size);
     return OC_OK;
 }
 

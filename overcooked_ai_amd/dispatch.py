@@ -1,8 +1,9 @@
-"""Which rollout kernel instance serves which batch, and which path and kernel instance a training step takes: the host side of
-oc_rollout_plan and oc_multi_agent_plan (include/oc_amd.h, ABI 6).
+"""Which rollout kernel instance serves which batch, which path and kernel instance a training step takes, and which kernel
+instance writes an observation: the host side of oc_rollout_plan, oc_multi_agent_plan and oc_observation_plan (include/oc_amd.h,
+ABI 6).
 
-The answers are the plan oc_rollout_random makes of a call before it launches anything, put into words (the planner holds no
-launch and no device pointer), so this works on a host without a GPU.  `table()` is what tools/gen_dispatch_table.py writes to docs/DISPATCH.md and
+The answers are the plans oc_rollout_random, oc_multi_agent_step, oc_encode_lossless and oc_rollout_encode make of a call before
+they launch anything, put into words (the planners hold no launch and no device pointer), so this works on a host without a GPU.  `table()` is what tools/gen_dispatch_table.py writes to docs/DISPATCH.md and
 what tests/test_dispatch_table.py compares that file with."""
 import ctypes
 
@@ -44,6 +45,21 @@ def multi_agent_plan(table, n_envs, horizon=400, obs_dtype=_lib.OBS_F32, with_ob
     rc = L.oc_multi_agent_plan(ctypes.byref(b), int(horizon), int(bool(with_obs)), int(obs_dtype), int(bool(use_phi)), int(event_sink),
                                ctypes.byref(start) if start is not None else None, out, len(out))
     _lib.check(rc, "oc_multi_agent_plan")
+    return out.value.decode()
+
+
+def observation_plan(table, n_envs, n_steps=0, obs_dtype=_lib.OBS_U8, horizon=400, options=_lib.OPT_AUTO_RESET, with_actions=False,
+                     with_outputs=True, start=None):
+    """The kernel instance `oc_encode_lossless` (n_steps == 0) or `oc_rollout_encode` (n_steps >= 1) launches for this table and
+    batch size, or "step by step: ..." with the one-step entry point and the encode instance of every step (text; up to and
+    including '>' the instance's name), or the library's refusal (OcAmdError).  obs_dtype: _lib.OBS_U8 / OBS_F32; options:
+    OPT_AUTO_RESET, OPT_ONE_KERNEL."""
+    L = _lib.load()
+    b = batch_for(table, n_envs)
+    out = ctypes.create_string_buffer(320)
+    rc = L.oc_observation_plan(ctypes.byref(b), int(obs_dtype), int(horizon), int(options), int(n_steps), int(bool(with_actions)),
+                               int(bool(with_outputs)), ctypes.byref(start) if start is not None else None, out, len(out))
+    _lib.check(rc, "oc_observation_plan")
     return out.value.decode()
 
 

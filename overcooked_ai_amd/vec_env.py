@@ -261,8 +261,9 @@ class VecOvercookedEnv:
 
     def step_encode(self, actions, dtype=torch.uint8, out=None):
         """step(actions) followed by encode_lossless of the resulting states, as one C call (oc_step_encode: one kernel
-        for a single layout with at most two pots, u8 observations and a batch that fills the GPU — or `one_kernel` —
-        else the two kernels back to back).  Returns (rewards, flags, obs)."""
+        for a single layout with at most two pots and 48 cells, u8 or f32 observations, no drawn start states and
+        `one_kernel` — a single step does not pick it by batch size — else the two kernels back to back;
+        `plan_observation(1, dtype, actions=True, step_encode=True)` says which).  Returns (rewards, flags, obs)."""
         code = {torch.uint8: _lib.OBS_U8, torch.float32: _lib.OBS_F32}[dtype]
         if out is None:
             out = torch.empty((self.n_envs, 2, self.width, self.height, 26), dtype=dtype, device=self.device)
@@ -391,7 +392,8 @@ class VecOvercookedEnv:
 
     def rollout_encode(self, n_steps, obs_out, rewards_out=None, flags_out=None, actions=None, dtype=torch.uint8):
         """n_steps transitions with the lossless observation after every step, one C call (oc_rollout_encode; a single
-        kernel for one layout / u8 / at most two pots).  actions: None = the random policy of rollout_random (same Philox
+        kernel for one layout / at most two pots / at most 48 cells, u8 or f32 observations, once the batch gives every CU a
+        workgroup and n_steps >= 2 — or `one_kernel` —, else the one-step kernels step by step; `plan_observation` says which).  actions: None = the random policy of rollout_random (same Philox
         stream), or uint8 [n_steps, n_envs, 2].  obs_out: [n_steps, n_envs, 2, W, H, 26] (the whole trajectory) or
         [n_envs, 2, W, H, 26] (every step overwrites it: only the last observation survives).  rewards_out float32
         [n_steps, n_envs, 4] / flags_out uint8 [n_steps, n_envs] (required with caller actions).  With track_events the
@@ -440,6 +442,29 @@ class VecOvercookedEnv:
             self.t_global += K
         self._advance(K)
         return obs_out, rewards_out, flags_out
+
+    def plan_observation(self, n_steps=0, dtype=torch.uint8, actions=False, outputs=True, single_buffer=False, step_encode=False):
+        """The kernel instance the next observation call launches, in oc_observation_plan's words (up to and including '>' the
+        instance's name; "step by step: <one-step entry point> + <encode instance>" where every step is two calls).  n_steps = 0:
+        encode_lossless(dtype).  n_steps >= 1: rollout_encode(n_steps, obs_out, ..., dtype=dtype) — actions: caller actions are
+        given; outputs: rewards_out and flags_out are; single_buffer: obs_out holds one step, not the trajectory —, or, with
+        step_encode, step_encode(actions, dtype).  The arguments are the ones those calls pass; `one_kernel` is honoured."""
+        code = {torch.uint8: _lib.OBS_U8, torch.float32: _lib.OBS_F32}[dtype]
+        K = int(n_steps)
+        one_step = "oc_step" if actions or step_encode else "oc_rollout_random"
+        options, start = (_lib.OPT_AUTO_RESET if self.auto_reset else 0), self._start_spec() if self.auto_reset else None
+        if step_encode:  # oc_step_encode's own route: the options of step(), and oc_step + oc_encode_lossless with a start spec or any option but auto-reset
+            K, actions, outputs, options = 1, True, True, self.options
+            if start is not None or options & ~_lib.OPT_AUTO_RESET:
+                return "step by step: %s + %s" % (one_step, self.plan_observation(0, dtype))
+        row_bytes = self.n_envs * 2 * self.width * self.height * 26 * (1 if dtype == torch.uint8 else 4)
+        if K >= 1 and (self.event_counts is not None or (not step_encode and not single_buffer and row_bytes % 16 != 0)):
+            return "step by step: %s + %s" % (one_step, self.plan_observation(0, dtype))  # (this class's own loop over the one-step calls)
+        out = ctypes.create_string_buffer(320)
+        rc = self.lib.oc_observation_plan(self._bref, code, self.horizon, options | (_lib.OPT_ONE_KERNEL if self.one_kernel and K >= 1 else 0),
+                                          K, int(bool(actions)), int(bool(outputs)), start, out, len(out))
+        _lib.check(rc, "oc_observation_plan")
+        return out.value.decode()
 
     def encode_lossless(self, dtype=torch.uint8, out=None, state=None):
         """[n_envs, 2, W, H, 26] observation (mdp.py:2385); out[:, i] is the encoding for player i."""

@@ -57,6 +57,7 @@ def test_config2_asymmetric_advantages_step_plus_encoding(gpu):
     st[0, :, 6] = 380 & 0xFF
     st[0, :, 7] = 380 >> 8
     env.set_packed_state(st)
+    assert env.plan_observation(0, torch.uint8) == "k_encode_uniform<T=u8> unit=4, upg=4, grid=768, 47824 B LDS"
     for it in range(40):
         env.rollout_random(1, rew, fl)
         env.encode_lossless(torch.uint8, out=obs)
@@ -85,6 +86,9 @@ def test_config2_one_kernel_trajectory(gpu):
     rew = torch.zeros((K, N, 4), dtype=torch.float32, device=gpu)
     fl = torch.zeros((K, N), dtype=torch.uint8, device=gpu)
     obs = torch.empty((K, N, 2, env.width, env.height, 26), dtype=torch.uint8, device=gpu)
+    # (65 536 envs give every CU a workgroup: the single kernel without being asked; 9x5 u8: eight wavefronts, images of one 4-env template)
+    plan = env.plan_observation(K)
+    assert plan.startswith("k_rollout_encode<MAXP=2, FAST=3, T=u8, NW=8> unit=4, G=4, 120336 B LDS, budget ") and plan.endswith(" B (queried)"), plan
     env.rollout_encode(K, obs, rew, fl)
     rew_h, fl_h = rew.cpu().numpy(), fl.cpu().numpy()
     for it in range(K):

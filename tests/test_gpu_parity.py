@@ -87,6 +87,8 @@ def test_golden_lossless_encoding(name, manifest, gpu):
     for n in (st.shape[1], 1, 5, 63):  # ragged tails of the encode kernel's env groups
         env = make_env(spec, n, gpu, horizon=int(d["enc_horizon"]))
         env.set_packed_state(st[:, :n])
+        assert env.plan_observation(0, torch.uint8).startswith("k_encode_uniform<T=u8>"), (name, n)
+        assert env.plan_observation(0, torch.float32).startswith("k_encode<T=f32, LAY_LDS=true>"), (name, n)
         a = u8(env.encode_lossless(torch.uint8))
         b = u8(env.encode_lossless(torch.float32))
         assert a.shape == (n, 2, spec.width, spec.height, 26)
@@ -337,6 +339,7 @@ def test_large_layout_table_global_path(gpu):
     env.step(torch.from_numpy(acts).to(gpu))
     st_o2, _, _ = orc.step(st_o, acts, horizon=100, options=1, layout_id=lid)
     assert np.array_equal(env.get_packed_state(), st_o2)
+    assert env.plan_observation(0, torch.float32).startswith("k_encode<T=f32, LAY_LDS=false>")
     enc = u8(env.encode_lossless(torch.float32))
     assert np.array_equal(enc, orc.encode_lossless(st_o2, horizon=100, layout_id=lid).astype(np.float32))
 
@@ -416,6 +419,9 @@ def test_full_size_encoding_properties(gpu):
     st = random_packed_states(spec, 4096, rng)
     env.set_packed_state(np.tile(st, (1, n // 4096, 1)))
     env.rollout_random(37)
+    # (9x5 u8: templates of 4 envs, 4 per group, three groups resident per CU; f32: 4 envs per workgroup)
+    assert env.plan_observation(0, torch.uint8) == "k_encode_uniform<T=u8> unit=4, upg=4, grid=768, 47824 B LDS"
+    assert env.plan_observation(0, torch.float32) == "k_encode<T=f32, LAY_LDS=true> epb=4, grid=16384, 37696 B LDS"
     a = env.encode_lossless(torch.uint8)
     b = env.encode_lossless(torch.float32)
     assert torch.equal(a.float(), b)
@@ -1124,11 +1130,20 @@ def test_fused_step_encode_equals_step_then_encode(layout, gpu):
             st = st[:, order]
         a.set_packed_state(st)
         b.set_packed_state(st)
+        # the single kernel serves one layout with at most two pots, u8 and f32, and no start spec; every other call is oc_step,
+        # then the observation kernel of the table
+        one_kernel = layout in ("cramped_room", "asymmetric_advantages", "counter_circuit") and not random_starts
+        rest = {"mixed": ("k_encode<T=u8, LAY_LDS=true>", "k_encode<T=f32, LAY_LDS=true>")}.get(
+            layout, ("k_encode_uniform<T=u8>", "k_encode<T=f32, LAY_LDS=true>"))
         for t in range(2 * horizon + 3):
             acts = rng.integers(0, 6, size=(n, 2)).astype(np.uint8)
             acts[rng.integers(0, n, size=4), rng.integers(0, 2, size=4)] = 7  # illegal: env untouched, flagged
             ta = torch.from_numpy(acts).to(gpu)
             dt = torch.uint8 if t % 2 == 0 else torch.float32
+            if t < 2:
+                want = ("k_rollout_encode<MAXP=2, FAST=3, T=%s, NW=%d>" % (("u8", 8), ("f32", 4))[t]) if one_kernel \
+                    else "step by step: oc_step + " + rest[t]
+                assert a.plan_observation(1, dt, step_encode=True).startswith(want), (layout, random_starts, dt)
             r1, f1, obs1 = a.step_encode(ta, dt)
             r2, f2 = b.step(ta)
             obs2 = b.encode_lossless(dt)
@@ -1170,7 +1185,7 @@ def test_timestep_saturates_at_the_packing_limit(gpu):
                                     "cramped_room_old_dynamics", "mixed", "seven_pots"])
 def test_rollout_with_observations_equals_the_one_step_kernels(layout, gpu):
     """oc_rollout_encode (BASELINE configs[2]: K transitions and the lossless observation after every step in one call;
-    one kernel for single-layout / u8 / <= 2-pot batches, the one-step kernels step by step otherwise) == K x
+    one kernel for single-layout / <= 2-pot / <= 48-cell batches, the one-step kernels step by step otherwise) == K x
     (oc_rollout_random or oc_step, then oc_encode_lossless), bit for bit: per-step rewards, flags and observations, the
     final state and episode returns — random policy and caller actions with illegal entries, across two horizons with
     auto-reset, ragged batch (partly filled last wavefront, empty wavefronts), trajectory buffer and single buffer; the
@@ -1196,10 +1211,15 @@ def test_rollout_with_observations_equals_the_one_step_kernels(layout, gpu):
         order = np.argsort(np.argsort(lid, kind="stable"), kind="stable")
         st = st[:, order]
     W, H = table.width, table.height
+    encode = {"mixed": "k_encode<T=u8, LAY_LDS=true>", "seven_pots": "k_encode_uniform<T=u8>"}.get(layout)  # (of the step-by-step tables)
     for mode in ("random", "actions", "single_buffer"):
         a = make_env(table, n, gpu, horizon=horizon, auto_reset=True, seed=21, layout_id=lid)
         b = make_env(table, n, gpu, horizon=horizon, auto_reset=True, seed=21, layout_id=lid)
+        assert a.plan_observation(K, actions=mode == "actions").startswith("step by step: ")
         a.one_kernel = True  # the batch is far too small to pick k_rollout_encode by itself
+        want = "step by step: %s + %s" % ("oc_step" if mode == "actions" else "oc_rollout_random", encode) if encode \
+            else "k_rollout_encode<MAXP=2, FAST=3, T=u8, NW=8>"
+        assert a.plan_observation(K, actions=mode == "actions", single_buffer=mode == "single_buffer").startswith(want), (layout, mode)
         a.set_packed_state(st)
         b.set_packed_state(st)
         acts = None
@@ -1250,6 +1270,8 @@ def test_rollout_with_observations_edge_sizes(gpu):
     rng = np.random.default_rng(13)
     for layout, n in (("cramped_room", 1), ("cramped_room", 63), ("asymmetric_advantages", 68), ("cramped_room", 257),
                       ("coordination_ring", 260), ("coordination_ring", 257)):  # (257 x 1300 B rows: the step-by-step path)
+        want = "step by step: oc_rollout_random + k_encode_uniform<T=u8>" if n == 257 and layout == "coordination_ring" \
+            else "k_rollout_encode<MAXP=2, FAST=3, T=u8, NW=8>"
         table = LayoutTable([spec_from_name(layout)])
         st = random_packed_states(table.specs[0], n, rng, timestep_max=9)
         W, H, K = table.width, table.height, 14
@@ -1265,6 +1287,7 @@ def test_rollout_with_observations_edge_sizes(gpu):
             fl_a = torch.zeros((K, n), dtype=torch.uint8, device=gpu) if outputs else None
             rew_b = torch.zeros((K, n, 4), dtype=torch.float32, device=gpu)
             fl_b = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
+            assert a.plan_observation(K, outputs=outputs).startswith(want), (layout, n, auto_reset, outputs)
             a.rollout_encode(K, obs_a, rew_a, fl_a)
             for k in range(K):
                 b.rollout_random(1, rew_b[k:k + 1], fl_b[k:k + 1])
@@ -1417,6 +1440,11 @@ def test_rollout_with_observations_crowded_grids(dtype, gpu):
         rew_a = torch.zeros((K, n, 4), dtype=torch.float32, device=gpu)
         fl_a = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
         rew_b, fl_b = torch.zeros_like(rew_a), torch.zeros_like(fl_a)
+        # (130 or 70 u8 rows of 2340 bytes are no multiple of 16: the trajectories of the two 9x5 layouts are written step by step;
+        # f32 rows always are: the crowded sub-groups of k_rollout_encode run under f32 only)
+        want = "step by step: oc_rollout_random + k_encode_uniform<T=u8>" if layout != "cramped_room" and dtype == "u8" \
+            else "k_rollout_encode<MAXP=2, FAST=3, T=%s, NW=%d>" % (("u8", 8) if dtype == "u8" else ("f32", 4))
+        assert a.plan_observation(K, tdt).startswith(want), (layout, dtype, a.plan_observation(K, tdt))
         a.rollout_encode(K, obs_a, rew_a, fl_a, dtype=tdt)
         for k in range(K):
             b.rollout_random(1, rew_b[k:k + 1], fl_b[k:k + 1])
@@ -1444,6 +1472,7 @@ def test_rollout_with_float32_observations(layout, gpu):
     obs_a = torch.full((K, n, 2, W, H, 26), -7.0, dtype=torch.float32, device=gpu)
     rew_a = torch.zeros((K, n, 4), dtype=torch.float32, device=gpu)
     fl_a = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
+    assert a.plan_observation(K, torch.float32).startswith("k_rollout_encode<MAXP=2, FAST=3, T=f32, NW=4>"), a.plan_observation(K, torch.float32)
     a.rollout_encode(K, obs_a, rew_a, fl_a, dtype=torch.float32)
     rew_b, fl_b = torch.zeros_like(rew_a), torch.zeros_like(fl_a)
     for k in range(K):
@@ -1479,6 +1508,9 @@ def test_rollout_with_observations_and_drawn_start_states(layout, gpu):
         obs_a = torch.full((K, n, 2, W, H, 26), 0xAB, dtype=torch.uint8, device=gpu)
         rew_a = torch.zeros((K, n, 4), dtype=torch.float32, device=gpu)
         fl_a = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
+        want = "step by step: %s + k_encode<T=u8, LAY_LDS=true>" % ("oc_step" if with_actions else "oc_rollout_random") if layout == "mixed" \
+            else "k_rollout_encode<MAXP=2, FAST=3, T=u8, NW=8>"
+        assert a.plan_observation(K, actions=with_actions).startswith(want), (layout, with_actions)
         a.rollout_encode(K, obs_a, rew_a, fl_a, actions=acts)
         rew_b, fl_b = torch.zeros_like(rew_a), torch.zeros_like(fl_a)
         for k in range(K):
@@ -1491,6 +1523,50 @@ def test_rollout_with_observations_and_drawn_start_states(layout, gpu):
             assert torch.equal(obs_a[k], b.encode_lossless(torch.uint8)), (layout, with_actions, k)
         assert torch.equal(rew_a, rew_b) and torch.equal(fl_a, fl_b) and torch.equal(a.state, b.state), (layout, with_actions)
         assert (u8(fl_a) & 4).sum() >= 3 * n, "several restarts per env inside the launch"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["u8", "f32"])
+@pytest.mark.parametrize("layout", ["cramped_room", "asymmetric_advantages"])
+def test_rollout_with_observations_against_the_oracle(layout, dtype, gpu):
+    """k_rollout_encode against the C oracle alone, at zero tolerance: 260 envs (one full workgroup and a ragged one of 4 envs),
+    12 steps over a horizon of 10 (every env restarts inside the launch), a launch that does not begin at step 0, u8 and f32 — the
+    rewards, flags and observation of every step, the final state and the episode returns.  The plan must name the single kernel:
+    a call that fell back to the one-step kernels would pass the comparison without running it."""
+    from overcooked_ai_amd.layouts import LayoutTable, spec_from_name
+
+    n, horizon, K, seed, t_first = 260, 10, 12, 21, 3
+    table = LayoutTable([spec_from_name(layout)])
+    tdt = torch.uint8 if dtype == "u8" else torch.float32
+    # 5x4 u8: three sub-groups of 11 envs per wavefront; 9x5 u8: images of one 4-env template (tests/test_host_observation_plan.py
+    # derives both); f32 images hold what the device's LDS budget leaves: the instance is fixed, G is not
+    want = {("cramped_room", "u8"): "k_rollout_encode<MAXP=2, FAST=3, T=u8, NW=8> unit=1, G=11, 120464 B LDS",
+            ("asymmetric_advantages", "u8"): "k_rollout_encode<MAXP=2, FAST=3, T=u8, NW=8> unit=4, G=4, 120336 B LDS",
+            ("cramped_room", "f32"): "k_rollout_encode<MAXP=2, FAST=3, T=f32, NW=4> unit=1, G=",
+            ("asymmetric_advantages", "f32"): "k_rollout_encode<MAXP=2, FAST=3, T=f32, NW=4> unit=1, G="}[layout, dtype]
+    orc = oracle_for(table.specs)
+    st = random_packed_states(table.specs[0], n, np.random.default_rng(31), timestep_max=horizon - 1)
+    env = make_env(table, n, gpu, horizon=horizon, auto_reset=True, seed=seed)
+    env.one_kernel = True
+    env.set_packed_state(st)
+    env.rollout_random(t_first)
+    ep_o = np.zeros((n, 4), np.float32)
+    orc.rollout_random(st, t_first, horizon=horizon, options=1, seed=seed, t0=0, ep_returns=ep_o, want_outputs=False)
+    assert np.array_equal(env.get_packed_state(), st) and np.array_equal(u8(env.ep_returns), ep_o)
+    plan = env.plan_observation(K, tdt)
+    assert plan.startswith(want) and plan.endswith(" B (queried)"), plan
+    obs = torch.full((K, n, 2, table.width, table.height, 26), 7, dtype=tdt, device=gpu)
+    rew = torch.full((K, n, 4), -1.0, dtype=torch.float32, device=gpu)
+    fl = torch.full((K, n), 0xEE, dtype=torch.uint8, device=gpu)
+    env.rollout_encode(K, obs, rew, fl, dtype=tdt)
+    obs_h, rew_h, fl_h = u8(obs), u8(rew), u8(fl)
+    for k in range(K):
+        rew_o, fl_o = orc.rollout_random(st, 1, horizon=horizon, options=1, seed=seed, t0=t_first + k, ep_returns=ep_o)
+        assert np.array_equal(rew_h[k], rew_o[0]) and np.array_equal(fl_h[k], fl_o[0]), (layout, dtype, k)
+        assert np.array_equal(obs_h[k].astype(np.int32), orc.encode_lossless(st, horizon=horizon)), (layout, dtype, k)
+    assert np.array_equal(env.get_packed_state(), st) and np.array_equal(u8(env.ep_returns), ep_o)
+    assert ((fl_h & 4) != 0).sum(axis=0).min() >= 1, "an env that never restarted inside the launch"
+    assert env.t_global == t_first + K
 
 
 @pytest.mark.gpu
