@@ -30,7 +30,7 @@ def as_layout_table(layouts, pad_to=None):
 class VecOvercookedEnv:
     def __init__(self, layouts, n_envs, horizon=400, device="cuda", layout_id=None, auto_reset=False, seed=0,
                  env_offset=0, pad_to=None, track_returns=True, random_start_pos=False, rnd_obj_prob_thresh=0.0,
-                 track_events=False, regen_layout=False):
+                 track_events=False, regen_layout=False, *, batch_flags_mask=0xFFFFFFFF):
         self.lib = _lib.load()
         self.table = as_layout_table(layouts, pad_to)
         self.n_envs = int(n_envs)
@@ -103,6 +103,9 @@ class VecOvercookedEnv:
         host_table = np.ascontiguousarray(self.table.records)
         _lib.check(self.lib.oc_batch_hints(host_table.ctypes.data, len(self.table), self._bref), "oc_batch_hints")
         assert self._batch.max_pots == self.table.max_pots
+        # batch_flags_mask: the OC_BATCH_* hints the library is given (default: all the table earns).  A hint withheld is always
+        # safe (include/oc_amd.h) and selects the general kernel variants, e.g. ~_lib.BATCH_TWO_PLAYERS: k_rollout_encode<FAST=0>
+        self._batch.batch_flags &= int(batch_flags_mask) & 0xFFFFFFFF
         self._plans = {}
         self._phi_tables = {}
         self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()

@@ -1441,7 +1441,9 @@ def test_rollout_with_observations_crowded_grids(dtype, gpu):
         fl_a = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
         rew_b, fl_b = torch.zeros_like(rew_a), torch.zeros_like(fl_a)
         # (130 or 70 u8 rows of 2340 bytes are no multiple of 16: the trajectories of the two 9x5 layouts are written step by step;
-        # f32 rows always are: the crowded sub-groups of k_rollout_encode run under f32 only)
+        # f32 rows always are: here the crowded sub-groups of k_rollout_encode run under f32 only.  Under u8 they run, against the
+        # oracle, in tests/test_gpu_observation_instances.py: obs_cases' rollout_u8_unit4_crowded — 132 envs, rows that are —,
+        # rollout_u8_40_cells_crowded and rollout_u8_dword8)
         want = "step by step: oc_rollout_random + k_encode_uniform<T=u8>" if layout != "cramped_room" and dtype == "u8" \
             else "k_rollout_encode<MAXP=2, FAST=3, T=%s, NW=%d>" % (("u8", 8) if dtype == "u8" else ("f32", 4))
         assert a.plan_observation(K, tdt).startswith(want), (layout, dtype, a.plan_observation(K, tdt))
