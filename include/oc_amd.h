@@ -674,6 +674,35 @@ int oc_multi_agent_plan(const OcBatch* batch, int horizon, int with_obs, int obs
 int oc_observation_plan(const OcBatch* batch, int obs_dtype, int horizon, uint32_t options, int n_steps, int with_actions,
                         int with_outputs, const OcStartSpec* start, char* out, size_t out_size);
 
+/*
+ * oc_step_plan (ABI 6: an entry point added beside the others, as oc_multi_agent_plan was) — which kernel instance oc_step
+ * (entry 0), oc_step_many (entry 1) or oc_step_server_open (entry 2) would launch for this batch, as text; up to and including
+ * '>' the text is the instance's name and stable:
+ *   "k_step1<UNIFORM=true, MAXP=1, LAY_LDS=true, EVENTS=false> grid=10, 8192 B LDS"    one step on a grid of at most 64 cells, in
+ *                                                                       place or out of place, with or without an event sink
+ *   "k_step3<UNIFORM=false, MAXP=2, LAY_LDS=true, FAST=false, EVENTS=true> grid=..."   oc_step_many's K steps in one launch, and
+ *                                                                       one step on 65..128 cells
+ *   "k_step<UNIFORM=true, MAXP=2, LAY_LDS=true, EVENTS=false> grid=..."                OC_OPT_PREDICATE_INTERACT
+ *   "k_step_server<UNIFORM=false, MAXP=8, LAY_LDS=false> grid=..."                     the resident step
+ *   "step by step: oc_step + k_step<...> ..."                           oc_step_many with OC_OPT_PREDICATE_INTERACT: n_steps calls
+ *   "nothing to launch (no envs)" / "nothing to launch (no steps)"
+ * The three entry points plan a call before they launch anything (their argument checks, then the choice of the instance, the grid
+ * and the dynamic LDS bytes) and launch from that plan; this is the same plan put into words: every check applies (a refusal
+ * returns its code, with the entry point's own name in front of the message in oc_last_error), the code that answers is told which
+ * arrays a call has, not where they are, and holds no launch — so it also runs on a host without a GPU.  One check is not made:
+ * whether the GPU keeps every workgroup of the resident kernel resident at once is asked of the runtime when
+ * oc_step_server_open launches, and refused there.  idle_ms and life_s are not part of the plan either.
+ * The call described has every required array, and
+ *   horizon, options   as the entry point takes them
+ *   n_steps            oc_step_many's; not read for entries 0 and 2
+ *   with_masks         1: per-step event masks are asked for (oc_step's d_events or OcEventSink.d_events); 0: not
+ *   with_counts        1: per-episode counters (OcEventSink.d_counts); 0: not.  Neither is read for entry 2 (no event sink)
+ *   start              NULL or the start-state description the call would carry
+ *   out, out_size      caller's text buffer (>= 256 bytes holds every answer)
+ */
+int oc_step_plan(const OcBatch* batch, int entry, int horizon, uint32_t options, int n_steps, int with_masks, int with_counts,
+                 const OcStartSpec* start, char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

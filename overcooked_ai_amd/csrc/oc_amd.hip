@@ -20,9 +20,9 @@
 //   stores_only.hpp     the output stores of a rollout and nothing else: k_output_stores_only (oc_output_stores_only)
 //   observation_plan.hpp  host only: the observation geometry and the plans of oc_encode_lossless / oc_rollout_encode
 //   this file           launch dispatch and the extern "C" entry points declared in include/oc_amd.h: oc_rollout_random,
-//                       oc_multi_agent_step, oc_encode_lossless and oc_rollout_encode plan a call (checks, then choices; no
-//                       launch, no device address), then launch from the plan; oc_rollout_plan, oc_multi_agent_plan and
-//                       oc_observation_plan put the plans into words
+//                       oc_multi_agent_step, oc_encode_lossless, oc_rollout_encode, oc_step, oc_step_many and oc_step_server_open plan
+//                       a call (checks, then choices; no launch, no device address), then launch from the plan; oc_rollout_plan,
+//                       oc_multi_agent_plan, oc_observation_plan and oc_step_plan put the plans into words
 //
 // Execution model: one lane per env, 64-lane wavefronts, 256-lane workgroups.  This is integer /
 // indexing work (no MFMA).  Per-env state arrives as coalesced 16-byte planes (1 KiB per wavefront
@@ -183,70 +183,201 @@ inline bool ev_on(const EvArgs& ea) { return ea.events || ea.counts; }
         default: { constexpr int NOBJ = 8; __VA_ARGS__; } break;        \
     }
 
+// ---- the caller-actions family (oc_step, oc_step_many, oc_step_server_*): the call is planned first (every check, every choice; no
+//      launch, no device address), then launched from the plan — or, by oc_step_plan, described
 // kernel variant selection: UNIFORM (one layout for the whole batch -> layout constants in SGPRs),
 // MAXP (pot slots kept in registers: 1 for single-pot batches of one layout such as cramped_room, 2 covers every
 // canonical layout, 8 is the format's maximum),
-// LAY_LDS (layout table staged in LDS vs read from HBM/L2 for tables of more than 32 layouts)
-template <bool EVENTS>
-void launch_step_as(const OcBatch* b, int n_obj, const void* d_state_in, void* d_state_out, const uint8_t* d_actions,
-                    float* d_rewards, uint8_t* d_flags, float* d_ep_returns, int horizon, uint32_t options, hipStream_t s,
-                    const StartArgs& sa, const EvArgs& ea, int n_steps) {
+// LAY_LDS (layout table staged in LDS vs read from HBM/L2 for tables of more than 32 layouts),
+// FAST (k_step3: two players everywhere and at most 64 cells, the 64-bit floor mask), EVENTS (an event sink is there)
+struct StepChoice {
+    enum Family { NOTHING, STEP1, STEP3, PREDICATE, SERVER } family = NOTHING;  // no envs or steps / k_step1 / k_step3 / k_step / k_step_server
+    bool uniform = false;
+    int maxp = 0;
+    bool lay_lds = false, fast = false, events = false;
+    unsigned grid = 0;
+    size_t lds = 0;  // dynamic LDS bytes of the launch
+};
+enum StepEntry { ENTRY_STEP = 0, ENTRY_STEP_MANY = 1, ENTRY_SERVER = 2 };
+
+// Which kernel instance serves a call of the family: the one place that reads the batch and the call for it.  launch_step_from and
+// sv_launch launch what it returns.
+StepChoice choose_step(const OcBatch* b, int n_obj, uint32_t options, int n_steps, bool events, bool server) {
     const bool uniform = b->n_layouts == 1;
     const bool lds = b->n_layouts <= LDS_LAYOUT_MAX;
     const bool small = b->max_pots >= 1 && b->max_pots <= 2;
     const bool fast = (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0 && b->width * b->height <= 64;
-    const size_t smem = (size_t)n_obj * 8 * BLOCK * sizeof(uint32_t);
-    const dim3 grid(grid_for(b->n_envs)), block(BLOCK);
-    if (!(options & OC_OPT_PREDICATE_INTERACT)) {
-        // one step on a grid of at most 64 cells: the transition on the wire format itself (step_one.hpp) — in place or out of
-        // place, with or without event logging
-        if (n_steps == 1 && n_obj <= STEP1_MAX_PLANES && !step_no_lean()) {
-            const size_t smem1 = (size_t)n_obj * BLOCK * sizeof(uint4);
+    StepChoice c;
+    c.grid = grid_for(b->n_envs);
+    c.lds = (size_t)n_obj * 8 * BLOCK * sizeof(uint32_t);  // the cell words of a workgroup's envs (k_step1: see below)
+    c.events = events && !server;
+    const auto as = [&c](StepChoice::Family f, bool u, int mp, bool ll, bool fa = false) {
+        c.family = f; c.uniform = u; c.maxp = mp; c.lay_lds = ll; c.fast = fa;
+        return c;
+    };
+    if (server) {  // the resident step: no event logging
+        if (uniform && small) return as(StepChoice::SERVER, true, 2, true);
+        if (lds && small) return as(StepChoice::SERVER, false, 2, true);
+        return as(StepChoice::SERVER, false, 8, false);
+    }
+    if (options & OC_OPT_PREDICATE_INTERACT) {  // the predicate network is the independent second implementation: three instances cover every table
+        if (uniform) return small ? as(StepChoice::PREDICATE, true, 2, true) : as(StepChoice::PREDICATE, true, 8, true);
+        return as(StepChoice::PREDICATE, false, 8, false);
+    }
+    // one step on a grid of at most 64 cells: the transition on the wire format itself (step_one.hpp) — in place or out of place,
+    // with or without event logging
+    if (n_steps == 1 && n_obj <= STEP1_MAX_PLANES && !step_no_lean()) {
+        c.lds = (size_t)n_obj * BLOCK * sizeof(uint4);  // the object planes as they are, one 16-byte row per lane and plane
+        if (uniform) return b->max_pots == 1 ? as(StepChoice::STEP1, true, 1, true) : small ? as(StepChoice::STEP1, true, 2, true) : as(StepChoice::STEP1, true, 8, true);
+        if (lds && small) return as(StepChoice::STEP1, false, 2, true);
+        if (small) return as(StepChoice::STEP1, false, 2, false);
+        return as(StepChoice::STEP1, false, 8, false);  // (more than two pots on a mixed table: the general instance reads the table through L2)
+    }
+    // what is left for k_step3: oc_step_many's K transitions per launch and grids above 64 cells
+    if (uniform && fast && b->max_pots == 1) return as(StepChoice::STEP3, true, 1, true, true);
+    if (uniform && fast && small) return as(StepChoice::STEP3, true, 2, true, true);
+    if (lds && small) return as(StepChoice::STEP3, false, 2, true, false);
+    return as(StepChoice::STEP3, false, 8, false, false);
+}
+
+// an instance's template arguments as one switch label
+#define STEP_KEY(U, MP, LL, F) (((U) ? 1 : 0) | ((LL) ? 2 : 0) | ((F) ? 4 : 0) | ((MP) << 3))
+inline int step_key(const StepChoice& c) { return STEP_KEY(c.uniform, c.maxp, c.lay_lds, c.fast); }
+const char* const NO_STEP_INSTANCE = "no kernel instance for the planned step (internal error)";
+
+// launch what choose_step chose (EVENTS: the event-logging instances)
+template <bool EVENTS>
+int launch_step_as(const StepChoice& ch, const OcBatch* b, int n_obj, const void* d_state_in, void* d_state_out, const uint8_t* d_actions,
+                   float* d_rewards, uint8_t* d_flags, float* d_ep_returns, int horizon, uint32_t options, hipStream_t s,
+                   const StartArgs& sa, const EvArgs& ea, int n_steps) {
+    const size_t smem = ch.lds;
+    const dim3 grid(ch.grid), block(BLOCK);
+    if (ch.family == StepChoice::STEP1) {
 #define GO1(U, MP, LL)                                                                                                \
-    hipLaunchKernelGGL((k_step1<U, MP, LL, EVENTS>), grid, block, smem1, s, b->d_layouts, b->n_layouts, b->d_layout_id, \
-                       (uint4*)d_state_in, (uint4*)d_state_out, d_actions, (float4*)d_rewards, d_flags,               \
-                       (float4*)d_ep_returns, b->n_envs, b->width, n_obj, horizon, options, sa, ea)
-            if (uniform) { if (b->max_pots == 1) GO1(true, 1, true); else if (small) GO1(true, 2, true); else GO1(true, 8, true); }
-            else if (lds && small) GO1(false, 2, true);
-            else if (small) GO1(false, 2, false);
-            else GO1(false, 8, false);  // (more than two pots on a mixed table: the general instance reads the table through L2)
-#undef GO1
-            return;
+    case STEP_KEY(U, MP, LL, false):                                                                                  \
+        hipLaunchKernelGGL((k_step1<U, MP, LL, EVENTS>), grid, block, smem, s, b->d_layouts, b->n_layouts, b->d_layout_id, \
+                           (uint4*)d_state_in, (uint4*)d_state_out, d_actions, (float4*)d_rewards, d_flags,           \
+                           (float4*)d_ep_returns, b->n_envs, b->width, n_obj, horizon, options, sa, ea);              \
+        return OC_OK
+        switch (step_key(ch)) {
+            GO1(true, 1, true);
+            GO1(true, 2, true);
+            GO1(true, 8, true);
+            GO1(false, 2, true);
+            GO1(false, 2, false);
+            GO1(false, 8, false);
         }
+#undef GO1
+    } else if (ch.family == StepChoice::STEP3) {
 #define GO3(U, MP, LL, F)                                                                                            \
-    do {                                                                                                             \
-        if (!want_lds(k_step3<U, MP, LL, F, EVENTS>, smem)) break;                                                   \
+    case STEP_KEY(U, MP, LL, F):                                                                                     \
+        if (!want_lds(k_step3<U, MP, LL, F, EVENTS>, smem)) return OC_OK;                                            \
         hipLaunchKernelGGL((k_step3<U, MP, LL, F, EVENTS>), grid, block, smem, s, b->d_layouts, b->n_layouts, b->d_layout_id,   \
                            (const uint4*)d_state_in, (uint4*)d_state_out, d_actions, (float4*)d_rewards, d_flags,    \
                            (float4*)d_ep_returns, b->n_envs, b->width, n_obj, horizon, options, n_steps, sa, ea);    \
-    } while (0)
-        // (what is left for k_step3: oc_step_many's K transitions per launch and grids above 64 cells)
-        if (uniform && fast && b->max_pots == 1) GO3(true, 1, true, true);
-        else if (uniform && fast && small) GO3(true, 2, true, true);
-        else if (lds && small) GO3(false, 2, true, false);
-        else GO3(false, 8, false, false);
+        return OC_OK
+        switch (step_key(ch)) {
+            GO3(true, 1, true, true);
+            GO3(true, 2, true, true);
+            GO3(false, 2, true, false);
+            GO3(false, 8, false, false);
+        }
 #undef GO3
-        return;
-    }
+    } else if (ch.family == StepChoice::PREDICATE) {
 #define GO(U, MP, LL)                                                                                       \
-    do {                                                                                                    \
-        if (!want_lds(k_step<U, MP, LL, EVENTS>, smem)) break;                                              \
+    case STEP_KEY(U, MP, LL, false):                                                                        \
+        if (!want_lds(k_step<U, MP, LL, EVENTS>, smem)) return OC_OK;                                       \
         hipLaunchKernelGGL((k_step<U, MP, LL, EVENTS>), grid, block, smem, s, b->d_layouts, b->n_layouts,   \
                            b->d_layout_id, (const uint4*)d_state_in, (uint4*)d_state_out, d_actions,        \
                            (float4*)d_rewards, d_flags, (float4*)d_ep_returns, ea.events, b->n_envs,        \
                            b->width, n_obj, horizon, options);                                              \
-    } while (0)
-    // (the predicate network is the independent second implementation: three instances cover every table)
-    if (uniform) { if (small) GO(true, 2, true); else GO(true, 8, true); }
-    else GO(false, 8, false);
+        return OC_OK
+        switch (step_key(ch)) {
+            GO(true, 2, true);
+            GO(true, 8, true);
+            GO(false, 8, false);
+        }
 #undef GO
+    }
+    return fail(OC_ELAUNCH, NO_STEP_INSTANCE);  // (a missing kernel is an error, never another kernel)
 }
-// ... with the event-logging instances when ea names a sink
+// (a refused LDS request returns OC_OK above: check_launch reports it, as it reports a failed launch)
+int launch_step_from(const StepChoice& ch, const OcBatch* b, int n_obj, const void* d_state_in, void* d_state_out, const uint8_t* d_actions,
+                     float* d_rewards, uint8_t* d_flags, float* d_ep_returns, int horizon, uint32_t options, hipStream_t s,
+                     const StartArgs& sa, const EvArgs& ea, int n_steps) {
+    const auto go = ch.events ? launch_step_as<true> : launch_step_as<false>;
+    return go(ch, b, n_obj, d_state_in, d_state_out, d_actions, d_rewards, d_flags, d_ep_returns, horizon, options, s, sa, ea, n_steps);
+}
+// one step of a batch that another entry point has checked (the training step's sequence)
 void launch_step(const OcBatch* b, int n_obj, const void* d_state_in, void* d_state_out, const uint8_t* d_actions,
                  float* d_rewards, uint8_t* d_flags, float* d_ep_returns, int horizon, uint32_t options, hipStream_t s,
-                 const StartArgs& sa, const EvArgs& ea, int n_steps = 1) {
-    const auto go = ev_on(ea) ? launch_step_as<true> : launch_step_as<false>;
-    go(b, n_obj, d_state_in, d_state_out, d_actions, d_rewards, d_flags, d_ep_returns, horizon, options, s, sa, ea, n_steps);
+                 const StartArgs& sa, const EvArgs& ea) {
+    (void)launch_step_from(choose_step(b, n_obj, options, 1, ev_on(ea), false), b, n_obj, d_state_in, d_state_out, d_actions, d_rewards,
+                           d_flags, d_ep_returns, horizon, options, s, sa, ea, 1);
+}
+
+// What a plan needs to know of a call's arrays: which ones are there, never where (oc_step_plan has no more than that to give)
+struct StepArrays {
+    bool required;             // the state(s), actions, rewards and flags of the entry point (the server: the state)
+    bool ev_masks, ev_counts;  // per-step event masks (oc_step's d_events or the sink's) / per-episode counters
+};
+struct StepPlan {
+    int rc = OC_OK;  // the call is refused with this code (the message: oc_last_error)
+    int n_obj = 0;
+    StartArgs sa = {};
+    StepChoice ch;                  // NOTHING: no envs or no steps (`nothing` says which)
+    bool step_by_step = false;      // oc_step_many with OC_OPT_PREDICATE_INTERACT: n_steps calls of oc_step, each ch
+    const char* nothing = nullptr;
+};
+const char* const STEP_ENTRY_NAME[3] = {"oc_step", "oc_step_many", "oc_step_server_open"};
+
+// every check of the entry point, in its order and under its name, then the choice
+StepPlan plan_step(const OcBatch* b, int entry, const StepArrays& have, int horizon, uint32_t options, int n_steps, const OcStartSpec* start) {
+    const char* const who = STEP_ENTRY_NAME[entry];
+    StepPlan p;
+    const auto refused = [&p](int rc) { p.rc = rc; return p; };
+    const bool predicate = (options & OC_OPT_PREDICATE_INTERACT) != 0, ev = have.ev_masks || have.ev_counts;
+    if (entry == ENTRY_STEP_MANY) {
+        if (n_steps < 0) return refused(refuse(who, "n_steps < 0"));
+        if (int rc = check_start(who, start, &p.sa, b)) return refused(rc);
+        if ((start || ev) && predicate) return refused(refuse(who, "drawn start states / event logging need the table-driven kernel"));
+        if (int rc = check_batch(b, &p.n_obj)) return refused(rc);
+    } else {
+        if (int rc = check_batch(b, &p.n_obj)) return refused(rc);
+        if (int rc = check_start(who, start, &p.sa, b)) return refused(rc);
+    }
+    if (entry == ENTRY_STEP && predicate) {
+        if (start) return refused(refuse(who, "drawn start states need the table-driven kernel (no PREDICATE_INTERACT)"));
+        if (have.ev_counts) return refused(refuse(who, "event counters need the table-driven kernel (no PREDICATE_INTERACT)"));
+    }
+    if (!have.required) return refused(refuse(who, entry == ENTRY_SERVER ? "NULL state pointer" : "NULL state/actions/rewards/flags pointer"));
+    if (int rc = check_horizon(who, horizon)) return refused(rc);
+    if (entry == ENTRY_SERVER) {
+        if (options & ~(uint32_t)OC_OPT_AUTO_RESET) return refused(refuse(who, "the only option is OC_OPT_AUTO_RESET"));
+        if (b->n_envs < 1) return refused(refuse(who, "no envs"));
+        p.ch = choose_step(b, p.n_obj, options, 1, false, true);
+        return p;
+    }
+    if (b->n_envs == 0) { p.nothing = "no envs"; return p; }
+    if (entry == ENTRY_STEP_MANY && n_steps == 0) { p.nothing = "no steps"; return p; }
+    p.step_by_step = entry == ENTRY_STEP_MANY && predicate;
+    p.ch = choose_step(b, p.n_obj, options, entry == ENTRY_STEP || p.step_by_step ? 1 : n_steps, ev, false);
+    return p;
+}
+
+// A choice in words (oc_step_plan): up to and including '>' the kernel instance, as tests match it
+void describe_step(const StepChoice& c, char* out, size_t out_size) {
+    const char* const tf[2] = {"false", "true"};
+    char name[160];
+    if (c.family == StepChoice::STEP3)
+        snprintf(name, sizeof(name), "k_step3<UNIFORM=%s, MAXP=%d, LAY_LDS=%s, FAST=%s, EVENTS=%s>", tf[c.uniform], c.maxp, tf[c.lay_lds],
+                 tf[c.fast], tf[c.events]);
+    else if (c.family == StepChoice::SERVER)
+        snprintf(name, sizeof(name), "k_step_server<UNIFORM=%s, MAXP=%d, LAY_LDS=%s>", tf[c.uniform], c.maxp, tf[c.lay_lds]);
+    else
+        snprintf(name, sizeof(name), "%s<UNIFORM=%s, MAXP=%d, LAY_LDS=%s, EVENTS=%s>", c.family == StepChoice::STEP1 ? "k_step1" : "k_step",
+                 tf[c.uniform], c.maxp, tf[c.lay_lds], tf[c.events]);
+    snprintf(out, out_size, "%s grid=%u, %zu B LDS", name, c.grid, c.lds);
 }
 
 // Which kernel serves a call of oc_rollout_random (without OC_OPT_LANE_PAIR / OC_OPT_PREDICATE_INTERACT) or of oc_rollout_record /
@@ -576,40 +707,27 @@ int oc_batch_hints(const OcLayout* h_layouts, int n_layouts, OcBatch* batch) {
 int oc_step(const OcBatch* b, const void* d_state_in, void* d_state_out, const uint8_t* d_actions, float* d_rewards,
             uint8_t* d_flags, float* d_ep_returns, uint64_t* d_events, int horizon, uint32_t options,
             const OcStartSpec* start, const OcEventSink* events, void* stream) {
-    int n_obj = 0;
-    if (int rc = check_batch(b, &n_obj)) return rc;
-    StartArgs sa;
-    if (int rc = check_start("oc_step", start, &sa, b)) return rc;
     const EvArgs ea = ev_args(events, d_events);
-    if (options & OC_OPT_PREDICATE_INTERACT) {
-        if (start) return fail(OC_EINVAL, "oc_step: drawn start states need the table-driven kernel (no PREDICATE_INTERACT)");
-        if (ea.counts) return fail(OC_EINVAL, "oc_step: event counters need the table-driven kernel (no PREDICATE_INTERACT)");
-    }
-    if (!d_state_in || !d_state_out || !d_actions || !d_rewards || !d_flags)
-        return fail(OC_EINVAL, "oc_step: NULL state/actions/rewards/flags pointer");
-    if (int rc = check_horizon("oc_step", horizon)) return rc;
-    if (b->n_envs == 0) return OC_OK;
-    launch_step(b, n_obj, d_state_in, d_state_out, d_actions, d_rewards, d_flags, d_ep_returns, horizon, options, (hipStream_t)stream, sa, ea);
+    const StepArrays have = {d_state_in && d_state_out && d_actions && d_rewards && d_flags, ea.events != nullptr, ea.counts != nullptr};
+    const StepPlan p = plan_step(b, ENTRY_STEP, have, horizon, options, 1, start);
+    if (p.rc != OC_OK || p.ch.family == StepChoice::NOTHING) return p.rc;
+    if (int rc = launch_step_from(p.ch, b, p.n_obj, d_state_in, d_state_out, d_actions, d_rewards, d_flags, d_ep_returns, horizon, options,
+                                  (hipStream_t)stream, p.sa, ea, 1))
+        return rc;
     return check_launch("oc_step");
 }
 
 int oc_step_many(const OcBatch* b, void* d_state, const uint8_t* d_actions, float* d_rewards, uint8_t* d_flags,
                  float* d_ep_returns, int n_steps, int horizon, uint32_t options, const OcStartSpec* start,
                  const OcEventSink* events, void* stream) {
-    if (n_steps < 0) return fail(OC_EINVAL, "oc_step_many: n_steps < 0");
-    StartArgs sa;
-    if (int rc = check_start("oc_step_many", start, &sa, b)) return rc;
     const EvArgs ea = ev_args(events, nullptr);
-    if ((start || ev_on(ea)) && (options & OC_OPT_PREDICATE_INTERACT))
-        return fail(OC_EINVAL, "oc_step_many: drawn start states / event logging need the table-driven kernel");
-    int n_obj = 0;
-    if (int rc = check_batch(b, &n_obj)) return rc;
-    if (!d_state || !d_actions || !d_rewards || !d_flags)
-        return fail(OC_EINVAL, "oc_step_many: NULL state/actions/rewards/flags pointer");
-    if (int rc = check_horizon("oc_step_many", horizon)) return rc;
-    if (b->n_envs == 0 || n_steps == 0) return OC_OK;
-    if (!(options & OC_OPT_PREDICATE_INTERACT)) {  // all K transitions in one launch, the envs stay on chip in between
-        launch_step(b, n_obj, d_state, d_state, d_actions, d_rewards, d_flags, d_ep_returns, horizon, options, (hipStream_t)stream, sa, ea, n_steps);
+    const StepArrays have = {d_state && d_actions && d_rewards && d_flags, ea.events != nullptr, ea.counts != nullptr};
+    const StepPlan p = plan_step(b, ENTRY_STEP_MANY, have, horizon, options, n_steps, start);
+    if (p.rc != OC_OK || p.ch.family == StepChoice::NOTHING) return p.rc;
+    if (!p.step_by_step) {  // all K transitions in one launch, the envs stay on chip in between
+        if (int rc = launch_step_from(p.ch, b, p.n_obj, d_state, d_state, d_actions, d_rewards, d_flags, d_ep_returns, horizon, options,
+                                      (hipStream_t)stream, p.sa, ea, n_steps))
+            return rc;
         return check_launch("oc_step_many");
     }
     for (int k = 0; k < n_steps; ++k) {
@@ -618,6 +736,26 @@ int oc_step_many(const OcBatch* b, void* d_state, const uint8_t* d_actions, floa
                              nullptr, horizon, options, nullptr, nullptr, stream))
             return rc;
     }
+    return OC_OK;
+}
+
+int oc_step_plan(const OcBatch* b, int entry, int horizon, uint32_t options, int n_steps, int with_masks, int with_counts,
+                 const OcStartSpec* start, char* out, size_t out_size) {
+    if (!out || out_size == 0) return fail(OC_EINVAL, "oc_step_plan: no output buffer");
+    out[0] = 0;
+    if (entry < ENTRY_STEP || entry > ENTRY_SERVER) return fail(OC_EINVAL, "oc_step_plan: entry must be 0 (oc_step), 1 (oc_step_many) or 2 (oc_step_server_open)");
+    // the call the entry point would get: every required array, the named event arrays (the server takes no event sink)
+    const StepArrays have = {true, entry != ENTRY_SERVER && with_masks != 0, entry != ENTRY_SERVER && with_counts != 0};
+    const StepPlan p = plan_step(b, entry, have, horizon, options, n_steps, start);
+    if (p.rc != OC_OK) return p.rc;
+    char buf[256];
+    if (p.ch.family == StepChoice::NOTHING) {
+        snprintf(buf, sizeof(buf), "nothing to launch (%s)", p.nothing);
+    } else {
+        const int used = p.step_by_step ? snprintf(buf, sizeof(buf), "step by step: oc_step + ") : 0;
+        describe_step(p.ch, buf + used, sizeof(buf) - (size_t)used);
+    }
+    snprintf(out, out_size, "%s", buf);
     return OC_OK;
 }
 
@@ -1350,13 +1488,13 @@ int sv_stop(OcStepServer* m) {
 // (re)launch the resident kernel; the requests first lose any stale STOP (a no-op request: the tag already served)
 int sv_launch(OcStepServer* m) {
     const OcBatch* b = &m->b;
-    const size_t smem = (size_t)m->n_obj * 8 * BLOCK * sizeof(uint32_t);
-    const bool uniform = b->n_layouts == 1, lds = b->n_layouts <= LDS_LAYOUT_MAX, small = b->max_pots >= 1 && b->max_pots <= 2;
+    const StepChoice ch = choose_step(b, m->n_obj, m->options, 1, false, true);
+    const size_t smem = ch.lds;
     sv_mark(m, 0u);  // (every serving wavefront reports in by itself)
     hipLaunchKernelGGL(k_step_server_post, dim3(m->grid), dim3(BLOCK), 0, m->stream, m->d_req, b->n_envs, 0u, m->d_rsp, 0u);
     (void)hipMemsetAsync(m->d_claims, 0, 16 * sizeof(uint32_t), m->stream);
 #define GOSV(U, MP, LL)                                                                                              \
-    do {                                                                                                             \
+    case STEP_KEY(U, MP, LL, false):                                                                                 \
         if (!want_lds(k_step_server<U, MP, LL>, smem)) break;                                                        \
         if (!sv_fits(k_step_server<U, MP, LL>, m, smem)) {                                                           \
             sv_mark(m, 0u);                                                                                          \
@@ -1365,10 +1503,13 @@ int sv_launch(OcStepServer* m) {
         hipLaunchKernelGGL((k_step_server<U, MP, LL>), dim3(m->grid), dim3(BLOCK), smem, m->stream, b->d_layouts, b->n_layouts, \
                            b->d_layout_id, (uint4*)m->d_state, (float4*)m->d_ep_returns, m->d_req, m->d_rsp, m->d_ctl, m->d_claims, b->n_envs, \
                            b->width, m->n_obj, m->horizon, m->options, m->sa, m->idle_ticks, m->life_ticks, sv_knobs("OC_SV_SERVER", 0x0100u)); \
-    } while (0)
-    if (uniform && small) GOSV(true, 2, true);
-    else if (lds && small) GOSV(false, 2, true);
-    else GOSV(false, 8, false);
+        break
+    switch (step_key(ch)) {
+        GOSV(true, 2, true);
+        GOSV(false, 2, true);
+        GOSV(false, 8, false);
+        default: sv_mark(m, 0u); return fail(OC_ELAUNCH, NO_STEP_INSTANCE);
+    }
 #undef GOSV
     const int rc = check_launch("oc_step_server");
     if (rc) { sv_mark(m, 0u); return rc; }
@@ -1416,16 +1557,12 @@ extern "C" {
 
 int oc_step_server_open(const OcBatch* b, void* d_state, float* d_ep_returns, int horizon, uint32_t options,
                         const OcStartSpec* start, double idle_ms, double life_s, OcStepServer** out) {
-    int n_obj = 0;
     if (!out) return fail(OC_EINVAL, "oc_step_server_open: NULL result pointer");
     *out = nullptr;
-    if (int rc = check_batch(b, &n_obj)) return rc;
-    StartArgs sa;
-    if (int rc = check_start("oc_step_server_open", start, &sa, b)) return rc;
-    if (!d_state) return fail(OC_EINVAL, "oc_step_server_open: NULL state pointer");
-    if (int rc = check_horizon("oc_step_server_open", horizon)) return rc;
-    if (options & ~(uint32_t)OC_OPT_AUTO_RESET) return fail(OC_EINVAL, "oc_step_server_open: the only option is OC_OPT_AUTO_RESET");
-    if (b->n_envs < 1) return fail(OC_EINVAL, "oc_step_server_open: no envs");
+    const StepPlan p = plan_step(b, ENTRY_SERVER, StepArrays{d_state != nullptr, false, false}, horizon, options, 1, start);
+    if (p.rc != OC_OK) return p.rc;
+    const int n_obj = p.n_obj;
+    const StartArgs& sa = p.sa;
     if (!(idle_ms >= 0.0 && idle_ms <= 10000.0) || !(life_s >= 0.0 && life_s <= 86400.0))
         return fail(OC_EINVAL, "oc_step_server_open: idle_ms in 0..10 000 (0: 20 ms), life_s in 0..86 400 (0: 600 s)");
     OcStepServer* m = new OcStepServer();

@@ -1,4 +1,4 @@
-// step_one.hpp — k_step1: ONE transition per launch, computed on the wire format itself (oc_step's in-place path)
+// step_one.hpp — k_step1: ONE transition per launch, computed on the wire format itself (oc_step on grids of at most 64 cells)
 // Part of liboc_amd.so: included by oc_amd.hip inside its anonymous namespace after step_table.hpp (interact3 and the
 // 8-byte LUT, step3_env, regen_layout) and reset.hpp (draw_start).
 #pragma once
@@ -18,8 +18,10 @@
 //     env restarts.
 // Same transition as env_step3 (get_state_transition, mdp.py:1375-1430): interact3 + the 8-byte LUT for
 // resolve_interacts, the replay of player 1 when player 0 touched its cell or pot, resolve_movement on the layout's
-// terrain bytes, step3_env.  In place only (state_out == state_in), no event logging, grids of at most 64 cells:
-// oc_step falls back to k_step3 otherwise.
+// terrain bytes, step3_env.  In place or out of place (st_out != st: every plane of the new state is written from the
+// lane's LDS rows, one_store), with or without event logging (EVENTS: per-step masks and / or per-episode counters), on grids
+// of at most 64 cells (STEP1_MAX_PLANES object planes): choose_step (oc_amd.hip) sends every single step of such a grid here,
+// and single steps on 65..128 cells to k_step3.
 // ==========================================================================================
 constexpr int STEP1_MAX_PLANES = 4;
 

@@ -468,8 +468,8 @@ __device__ __forceinline__ const uint8_t* stage_lut(uint2* s_lut, uint32_t old_d
 }
 
 // k_step3: transitions with caller-supplied actions (one per launch for oc_step, K for oc_step_many), table-driven
-// interact (no event logging;
-// oc_step with d_events != NULL uses k_step, whose predicate-network interact produces the event bits)
+// interact.  EVENTS: the instances that log events (per-step masks and / or per-episode counters, EvArgs).  oc_step reaches it
+// only on grids of 65..128 cells (k_step1 serves the others); k_step runs for OC_OPT_PREDICATE_INTERACT alone.
 template <bool UNIFORM, int MAXP, bool LAY_LDS, bool FAST = false, bool EVENTS = false>
 __global__ __launch_bounds__(BLOCK) void k_step3(const OcLayout* __restrict__ g_layouts, int n_layouts,
                                                  const uint16_t* layout_id, const uint4* st_in,

@@ -1,8 +1,9 @@
 """Which rollout kernel instance serves which batch, which path and kernel instance a training step takes, and which kernel
-instance writes an observation: the host side of oc_rollout_plan, oc_multi_agent_plan and oc_observation_plan (include/oc_amd.h,
-ABI 6).
+instance writes an observation, and which kernel instance steps a batch with the caller's actions: the host side of
+oc_rollout_plan, oc_multi_agent_plan, oc_observation_plan and oc_step_plan (include/oc_amd.h, ABI 6).
 
-The answers are the plans oc_rollout_random, oc_multi_agent_step, oc_encode_lossless and oc_rollout_encode make of a call before
+The answers are the plans oc_rollout_random, oc_multi_agent_step, oc_encode_lossless, oc_rollout_encode, oc_step, oc_step_many
+and oc_step_server_open make of a call before
 they launch anything, put into words (the planners hold no launch and no device pointer), so this works on a host without a GPU.  `table()` is what tools/gen_dispatch_table.py writes to docs/DISPATCH.md and
 what tests/test_dispatch_table.py compares that file with."""
 import ctypes
@@ -60,6 +61,24 @@ def observation_plan(table, n_envs, n_steps=0, obs_dtype=_lib.OBS_U8, horizon=40
     rc = L.oc_observation_plan(ctypes.byref(b), int(obs_dtype), int(horizon), int(options), int(n_steps), int(bool(with_actions)),
                                int(bool(with_outputs)), ctypes.byref(start) if start is not None else None, out, len(out))
     _lib.check(rc, "oc_observation_plan")
+    return out.value.decode()
+
+
+STEP_ENTRIES = {"step": 0, "step_many": 1, "server": 2}  # oc_step_plan's `entry`
+
+
+def step_plan(table, n_envs, entry="step", n_steps=1, horizon=400, options=_lib.OPT_AUTO_RESET, with_masks=False, with_counts=False,
+              start=None, batch=None):
+    """The kernel instance `oc_step` (entry "step"), `oc_step_many` ("step_many") or `oc_step_server_open` ("server") launches for
+    this table and batch size (text; up to and including '>' the instance's name), "step by step: oc_step + ..." for oc_step_many
+    with OPT_PREDICATE_INTERACT, or the library's refusal (OcAmdError).  with_masks / with_counts: per-step event masks / per-episode
+    counters are asked for; batch: an OcBatch to plan for instead of batch_for(table, n_envs) (hints withheld, say)."""
+    L = _lib.load()
+    b = batch_for(table, n_envs) if batch is None else batch
+    out = ctypes.create_string_buffer(320)
+    rc = L.oc_step_plan(ctypes.byref(b), STEP_ENTRIES[entry], int(horizon), int(options), int(n_steps), int(bool(with_masks)),
+                        int(bool(with_counts)), ctypes.byref(start) if start is not None else None, out, len(out))
+    _lib.check(rc, "oc_step_plan")
     return out.value.decode()
 
 

@@ -30,7 +30,7 @@ def as_layout_table(layouts, pad_to=None):
 class VecOvercookedEnv:
     def __init__(self, layouts, n_envs, horizon=400, device="cuda", layout_id=None, auto_reset=False, seed=0,
                  env_offset=0, pad_to=None, track_returns=True, random_start_pos=False, rnd_obj_prob_thresh=0.0,
-                 track_events=False, regen_layout=False, *, batch_flags_mask=0xFFFFFFFF):
+                 track_events=False, regen_layout=False, *, batch_flags_mask=0xFFFFFFFF, withhold_hints=False):
         self.lib = _lib.load()
         self.table = as_layout_table(layouts, pad_to)
         self.n_envs = int(n_envs)
@@ -106,6 +106,10 @@ class VecOvercookedEnv:
         # batch_flags_mask: the OC_BATCH_* hints the library is given (default: all the table earns).  A hint withheld is always
         # safe (include/oc_amd.h) and selects the general kernel variants, e.g. ~_lib.BATCH_TWO_PLAYERS: k_rollout_encode<FAST=0>
         self._batch.batch_flags &= int(batch_flags_mask) & 0xFFFFFFFF
+        # withhold_hints: none of the three hints is given (max_pots, batch_flags, max_free_cells all 0: "always safe", the general
+        # kernel variants everywhere)
+        if withhold_hints:
+            self._batch.max_pots = self._batch.batch_flags = self._batch.max_free_cells = 0
         self._plans = {}
         self._phi_tables = {}
         self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
@@ -301,6 +305,20 @@ class VecOvercookedEnv:
         _lib.check(rc, "oc_step_many")
         self._advance(int(K))
         return rewards_out, flags_out
+
+    def plan_step(self, entry="step", n_steps=1, state_out=False, events_out=False):
+        """The kernel instance the next caller-actions call launches, in oc_step_plan's words (up to and including '>' the instance's
+        name).  entry: "step" — step(actions, state_out, events_out) —, "step_many" — step_many(actions of n_steps steps, ...,
+        events_out) — or "server" — step_server().  events_out: a per-step mask buffer is given; state_out changes no choice (the
+        same instance steps in place and out of place).  This env's batch, options, start spec and event counters are the call's."""
+        del state_out
+        code = {"step": 0, "step_many": 1, "server": 2}[entry]
+        options = (_lib.OPT_AUTO_RESET if self.auto_reset else 0) if entry == "server" else self.options
+        out = ctypes.create_string_buffer(320)
+        rc = self.lib.oc_step_plan(self._bref, code, self.horizon, options, int(n_steps), int(bool(events_out)),
+                                   int(self.event_counts is not None), self._start_spec() if self.auto_reset else None, out, len(out))
+        _lib.check(rc, "oc_step_plan")
+        return out.value.decode()
 
     def step_server(self, idle_ms=0.0, life_s=0.0):
         """A StepServer for this env: the resident batched step (no launch per step; include/oc_amd.h oc_step_server_*).  Event

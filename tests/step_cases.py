@@ -1,0 +1,318 @@
+"""One list of caller-actions calls (oc_step, oc_step_many, oc_step_server_*), each there for ONE kernel instance, and the C oracle's
+run of such a call.
+
+The family launches 29 kernel instances (csrc/oc_amd.hip: launch_step_as, sv_launch): k_step1<UNIFORM, MAXP, LAY_LDS, EVENTS> (12:
+one step on a grid of at most four object planes), k_step3<UNIFORM, MAXP, LAY_LDS, FAST, EVENTS> (8: oc_step_many, and single steps
+on 65..128 cells), k_step<UNIFORM, MAXP, LAY_LDS, EVENTS> (6: OC_OPT_PREDICATE_INTERACT) and k_step_server<UNIFORM, MAXP, LAY_LDS>
+(3: the resident step).  choose_step (csrc/oc_amd.hip) picks one from the table's hints, the grid, the option bits, the number of
+steps and the event sink.  Every case below names the instance it is there for (`expect`: the words of oc_step_plan up to and
+including `>`); tests/test_host_step_instances.py holds the list to the planner's answers and to the instances the sources
+instantiate, without a GPU, and tests/test_gpu_step_instances.py runs every case against the oracle at zero tolerance.
+
+The default batch is 2 307 envs = 9 * 256 + 3: ten workgroups (no multiple of the 8 XCDs, for k_step3's xcd_block), the last
+wavefront of 3 envs.  The states a call starts from are helpers.random_packed_states with timesteps over the whole horizon; the
+default run is 20 steps at horizon 11, so roughly every env restarts inside the run and many restart twice, at different steps
+within every wavefront.  Unless a case says "standard", a restart draws its start state (rollout_cases.DRAWN); "regen" also
+re-draws the env's layout from the whole table.  N_BAD envs per step get an illegal action (6, 89, 172), no env twice, and the
+batch's last env one more at step 1."""
+import functools
+import os
+from collections import namedtuple
+
+import numpy as np
+
+from helpers import random_packed_states
+from rollout_cases import DRAWN
+from train_cases import table_of as _train_table_of
+
+N_ENVS = 2307   # 9 * 256 + 3
+N_BAD = 3       # illegal actions per step
+FOUR_BY_FOUR = "XPXX\nO12X\nX  S\nXDXX"  # 16 cells: one object plane, one pot
+# 64 cells: four object planes (STEP1_MAX_PLANES), two pots; k_step3<FAST>'s 64-bit floor mask is full
+EIGHT_BY_EIGHT = "XXPXXPXX\nO      X\nX 1    X\nX      O\nX    2 X\nX      X\nX      X\nXDXXSXXX"
+ENTRIES = ("step", "step_out_of_place", "step_many", "server")
+SERVER_SPLIT = 10  # a server case plays its first 10 steps in one play(), syncs, and plays the others as single step() calls
+
+
+def _tf(v):
+    return "true" if v else "false"
+
+
+def step1(UNIFORM, MAXP, LAY_LDS, EVENTS=False):
+    """A k_step1 instance in oc_step_plan's words."""
+    return "k_step1<UNIFORM=%s, MAXP=%d, LAY_LDS=%s, EVENTS=%s>" % (_tf(UNIFORM), MAXP, _tf(LAY_LDS), _tf(EVENTS))
+
+
+def step3(UNIFORM, MAXP, LAY_LDS, FAST, EVENTS=False):
+    return "k_step3<UNIFORM=%s, MAXP=%d, LAY_LDS=%s, FAST=%s, EVENTS=%s>" % (_tf(UNIFORM), MAXP, _tf(LAY_LDS), _tf(FAST), _tf(EVENTS))
+
+
+def pred(UNIFORM, MAXP, LAY_LDS, EVENTS=False):
+    return "k_step<UNIFORM=%s, MAXP=%d, LAY_LDS=%s, EVENTS=%s>" % (_tf(UNIFORM), MAXP, _tf(LAY_LDS), _tf(EVENTS))
+
+
+def server(UNIFORM, MAXP, LAY_LDS):
+    return "k_step_server<UNIFORM=%s, MAXP=%d, LAY_LDS=%s>" % (_tf(UNIFORM), MAXP, _tf(LAY_LDS))
+
+
+STEP1_ROWS = ((True, 1, True), (True, 2, True), (True, 8, True), (False, 2, True), (False, 2, False), (False, 8, False))
+STEP3_ROWS = ((True, 1, True, True), (True, 2, True, True), (False, 2, True, False), (False, 8, False, False))
+PRED_ROWS = ((True, 2, True), (True, 8, True), (False, 8, False))
+SERVER_ROWS = ((True, 2, True), (False, 2, True), (False, 8, False))
+# Every kernel instance csrc/oc_amd.hip instantiates for the caller-actions family
+INSTANCES = tuple([step1(*r, EVENTS=ev) for r in STEP1_ROWS for ev in (False, True)] + [step3(*r, EVENTS=ev) for r in STEP3_ROWS for ev in (False, True)]
+                  + [pred(*r, EVENTS=ev) for r in PRED_ROWS for ev in (False, True)] + [server(*r) for r in SERVER_ROWS])
+# Instances no call reaches without a tuning knob, each with its reason: none — every instance has a case
+UNREACHABLE = {}
+
+Case = namedtuple("Case", "id table n_envs entry expect n_steps horizon start events predicate hints returns seed env_offset")
+
+
+def case(id, table, entry, expect, n_envs=N_ENVS, n_steps=20, horizon=11, start="drawn", events="none", predicate=False, hints=True,
+         returns=True, seed=None, env_offset=None):
+    """entry: one of ENTRIES ("step" / "step_out_of_place": n_steps calls of one step; "step_many": one call; "server": see
+    SERVER_SPLIT); start: what a restart inside the call gives, "standard", "drawn" (DRAWN) or "regen" (drawn, on a layout drawn from
+    the whole table); events: "none", "masks" (per-step masks only), "counts" (per-episode counters only) or "both"; predicate:
+    OC_OPT_PREDICATE_INTERACT; hints: False withholds max_pots, batch_flags and max_free_cells; returns: False = no episode-return
+    array; seed: named where the default's run misses an event type the table can produce (possible_events)."""
+    assert entry in ENTRIES and start in ("standard", "drawn", "regen") and events in ("none", "masks", "counts", "both")
+    k = len(CASES)
+    c = Case(id, table, n_envs, entry, expect, n_steps, horizon, start, events, predicate, hints, returns, 71 + k if seed is None else seed,
+             3 * n_envs + 64 * k + 37 if env_offset is None else env_offset)
+    CASES.append(c)
+    return c
+
+
+CASES = []
+# ---- k_step1<UNIFORM, MAXP, LAY_LDS, EVENTS>: one step, in place, each row with and without an event sink
+case("step1_one_pot", "cramped_room", "step", step1(True, 1, True))
+case("step1_one_pot_events", "cramped_room", "step", step1(True, 1, True, True), events="both")
+case("step1_two_pots_standard_start", "asymmetric_advantages", "step", step1(True, 2, True), start="standard")
+case("step1_two_pots_counters_only", "asymmetric_advantages", "step", step1(True, 2, True, True), events="counts")
+case("step1_seven_pots", "seven_pots", "step", step1(True, 8, True))
+case("step1_seven_pots_masks_only", "seven_pots", "step", step1(True, 8, True, True), events="masks", seed=200)
+case("step1_table_in_lds_regen", "mix5", "step", step1(False, 2, True), start="regen")
+case("step1_table_in_lds_events_regen", "mix5", "step", step1(False, 2, True, True), start="regen", events="both", seed=206)
+case("step1_table_through_l2_no_returns", "canonical_5_x8", "step", step1(False, 2, False), returns=False)
+case("step1_table_through_l2_counters_only", "canonical_5_x8", "step", step1(False, 2, False, True), events="counts", seed=202)
+# (four layouts of one, two and seven pots: a table LDS would hold, read through L2; a re-draw switches L and C in mid-kernel)
+case("step1_general_through_l2_regen", "seven_and_scenario2_s", "step", step1(False, 8, False), start="regen")
+case("step1_general_through_l2_events_regen", "seven_and_scenario2_s", "step", step1(False, 8, False, True), start="regen", events="both")
+# ---- k_step1 out of place: every plane of the new state is written from the lane's LDS rows
+case("step1_out_of_place_drawn", "cramped_room", "step_out_of_place", step1(True, 1, True))
+case("step1_out_of_place_events_regen", "mix5", "step_out_of_place", step1(False, 2, True, True), start="regen", events="both", seed=215)
+case("step1_out_of_place_four_planes", "eight_by_eight", "step_out_of_place", step1(True, 2, True))
+case("step1_out_of_place_seven_pots_standard_start", "seven_pots", "step_out_of_place", step1(True, 8, True), start="standard")
+# ---- k_step1's grid edges: one object plane (16 cells) and STEP1_MAX_PLANES of them (64 cells)
+case("step1_one_plane", "four_by_four", "step", step1(True, 1, True))
+case("step1_four_planes_events", "eight_by_eight", "step", step1(True, 2, True, True), events="both", seed=206)
+# ---- one player: player 1 absent in k_step1<true, 1, true>; no OC_BATCH_TWO_PLAYERS -> k_step3<UNIFORM=false> without layout ids
+case("step1_one_player", "cramped_room_single", "step", step1(True, 1, True))
+case("step3_one_player_many_events", "cramped_room_single", "step_many", step3(False, 2, True, False, True), events="both", seed=208)
+# ---- withheld hints (max_pots = 0, batch_flags = 0, max_free_cells = 0: "always safe"): the MAXP=8 / non-FAST instances
+case("step1_hints_withheld", "cramped_room", "step", step1(True, 8, True), hints=False)
+case("step3_hints_withheld_many", "cramped_room", "step_many", step3(False, 8, False, False), hints=False)
+case("server_hints_withheld", "cramped_room", "server", server(False, 8, False), n_steps=21, hints=False)
+# ---- k_step3<UNIFORM, MAXP, LAY_LDS, FAST, EVENTS>: oc_step_many, each row with and without an event sink
+case("step3_fast_one_pot_many", "cramped_room", "step_many", step3(True, 1, True, True))
+case("step3_fast_one_pot_many_masks_only", "cramped_room", "step_many", step3(True, 1, True, True, True), events="masks")
+case("step3_fast_two_pots_many", "asymmetric_advantages", "step_many", step3(True, 2, True, True), start="standard")
+case("step3_fast_two_pots_many_counters_only", "asymmetric_advantages", "step_many", step3(True, 2, True, True, True), events="counts")
+case("step3_fast_full_floor_mask_many", "eight_by_eight", "step_many", step3(True, 2, True, True))
+case("step3_table_in_lds_many_regen", "mix5", "step_many", step3(False, 2, True, False), start="regen")
+case("step3_table_in_lds_many_events_regen", "mix5", "step_many", step3(False, 2, True, False, True), start="regen", events="both", seed=204)
+case("step3_general_seven_pots_many_no_returns", "seven_pots", "step_many", step3(False, 8, False, False), returns=False)
+case("step3_general_through_l2_many_events", "canonical_5_x8", "step_many", step3(False, 8, False, False, True), events="both", seed=206)
+case("step3_general_many_regen", "seven_and_scenario2_s", "step_many", step3(False, 8, False, False), start="regen")
+# ---- k_step3, single steps on 65..128 cells
+case("step3_65_cells_table", "big_4", "step", step3(False, 2, True, False))
+case("step3_65_cells_one_layout_events", "small_corridor", "step", step3(False, 2, True, False, True), events="both", seed=203)
+case("step3_126_cells_one_layout", "corridor", "step", step3(False, 2, True, False), n_envs=515)  # (two workgroups and 3 envs)
+# ---- k_step3's 8-step action queue, loaded with (k + j < n_steps): its fill edges, on a FAST and on a general instance
+for _k in (7, 8, 9, 17):
+    case("step3_fast_%d_steps" % _k, "cramped_room", "step_many", step3(True, 1, True, True), n_steps=_k, horizon=5)
+    case("step3_table_in_lds_%d_steps" % _k, "mix5", "step_many", step3(False, 2, True, False), n_steps=_k, horizon=5)
+# ---- k_step<UNIFORM, MAXP, LAY_LDS, EVENTS>: OC_OPT_PREDICATE_INTERACT (standard starts, per-step masks only: the entry point
+#      refuses start specs and counters), each row with and without events; oc_step_many runs it step by step
+case("predicate_two_pots", "asymmetric_advantages", "step", pred(True, 2, True), start="standard", predicate=True)
+case("predicate_two_pots_masks", "asymmetric_advantages", "step", pred(True, 2, True, True), start="standard", predicate=True, events="masks", seed=200)
+case("predicate_seven_pots", "seven_pots", "step", pred(True, 8, True), start="standard", predicate=True)
+case("predicate_seven_pots_masks", "seven_pots", "step_out_of_place", pred(True, 8, True, True), start="standard", predicate=True, events="masks", seed=200)
+case("predicate_table", "mix5", "step", pred(False, 8, False), start="standard", predicate=True)
+case("predicate_table_masks", "mix5", "step", pred(False, 8, False, True), start="standard", predicate=True, events="masks", seed=255)
+case("predicate_many_step_by_step", "mix5", "step_many", "step by step: oc_step + " + pred(False, 8, False), start="standard", predicate=True)
+# ---- k_step_server<UNIFORM, MAXP, LAY_LDS>: 21 steps = 10 in one play, a sync, 11 single steps (a resume)
+case("server_one_layout_drawn", "cramped_room", "server", server(True, 2, True), n_steps=21)
+case("server_table_in_lds", "mix5", "server", server(False, 2, True), n_steps=21, start="standard")
+case("server_general_seven_pots_no_returns", "seven_pots", "server", server(False, 8, False), n_steps=21, start="standard", returns=False)
+CASES = tuple(CASES)
+assert len({c.id for c in CASES}) == len(CASES)
+
+
+@functools.lru_cache(maxsize=None)
+def table_of(name):
+    """The LayoutTable a case names: train_cases' and rollout_cases' tables, and two of this list's own."""
+    from overcooked_ai_amd.layouts import LayoutSpec, LayoutTable, spec_from_name
+
+    own = {"four_by_four": FOUR_BY_FOUR, "eight_by_eight": EIGHT_BY_EIGHT}
+    if name in own:
+        return LayoutTable([LayoutSpec(dict(spec_from_name("cramped_room").to_layout_dict(), layout_name=name, grid=own[name]))])
+    return _train_table_of(name)
+
+
+def instance_of(c):
+    """The instance the case is there for: the words of its plan up to and including the last '>'."""
+    return c.expect[:c.expect.rindex(">") + 1].split(" + ")[-1]
+
+
+def with_masks(c):
+    return c.events in ("masks", "both")
+
+
+def with_counts(c):
+    return c.events in ("counts", "both")
+
+
+def possible_events(table):
+    """The names (overcooked_ai_amd.mdp.EVENT_TYPES) of the events a run on `table` can hold at all, from the reference's rules: the
+    pick-ups, drops, pottings, deliveries always (the random states hold every kind of object); the useful_* ones only with two
+    players (they ask what the other player holds); optimal / viable / catastrophic / useless potting of an ingredient where some
+    pot content of at most two items gives it on some layout (is_potting_*, mdp.py:2256-2308: on a layout whose orders hold no
+    tomato, potting a tomato is never viable and potting an onion never catastrophic)."""
+    from overcooked_ai_amd.mdp import EVENT_TYPES
+
+    names = set(EVENT_TYPES[:17])
+    if any(s.num_players != 2 for s in table.specs):
+        names -= {n for n in EVENT_TYPES if n.startswith("useful_")}
+    for s in table.specs:
+        for o in range(3):
+            for t in range(3 - o):
+                for ing in ("onion", "tomato"):
+                    bits = s.potting_class((o, t), ing)
+                    names |= {"%s_%s_potting" % (k, ing) for b, k in enumerate(("optimal", "viable", "catastrophic", "useless")) if bits >> b & 1}
+    return names
+
+
+def layout_ids(c):
+    """Global env e starts on layout e % K; None for a table of one layout."""
+    K = len(table_of(c.table))
+    return None if K == 1 else ((np.arange(c.n_envs) + c.env_offset) % K).astype(np.uint16)
+
+
+@functools.lru_cache(maxsize=None)
+def _states(cid):
+    c = next(x for x in CASES if x.id == cid)
+    table, lid = table_of(c.table), layout_ids(c)
+    rng = np.random.default_rng(c.seed)
+    if lid is None:
+        st = random_packed_states(table.specs[0], c.n_envs, rng, timestep_max=c.horizon - 1)
+    else:
+        st = np.zeros((table.n_planes, c.n_envs, 16), np.uint8)
+        for l in range(len(table)):
+            idx = np.nonzero(lid == l)[0]
+            st[:, idx] = random_packed_states(table.specs[l], len(idx), rng, timestep_max=c.horizon - 1)
+    st.setflags(write=False)
+    return st
+
+
+def states_of(c):
+    """uint8 [n_planes, n_envs, 16], read-only: the states the call starts from (computed once per case)."""
+    return _states(c.id)
+
+
+@functools.lru_cache(maxsize=None)
+def _actions(cid):
+    c = next(x for x in CASES if x.id == cid)
+    rng = np.random.default_rng(1000 + c.seed)
+    a = rng.integers(0, 6, size=(c.n_steps, c.n_envs, 2)).astype(np.uint8)
+    for k in range(c.n_steps):  # N_BAD envs per step, no env twice in a run, once the batch's last env
+        for j in range(N_BAD):
+            a[k, (N_BAD * k + j) * ((c.n_envs - 2) // (N_BAD * c.n_steps)), (k + j) & 1] = 6 + 83 * j
+    a[1, c.n_envs - 1, 0] = 9
+    a.setflags(write=False)
+    return a
+
+
+def actions_of(c):
+    """uint8 [n_steps, n_envs, 2], read-only: the caller's actions, N_BAD illegal entries (6, 89, 172) per step and one more at step 1."""
+    return _actions(c.id)
+
+
+def n_illegal(c):
+    return N_BAD * c.n_steps + 1
+
+
+def start_spec_of(c, epoch=1):
+    """The _lib.OcStartSpec the env hands to the library at `epoch`; None for the standard start."""
+    from overcooked_ai_amd import _lib
+
+    if c.start == "standard":
+        return None
+    count = len(table_of(c.table)) if c.start == "regen" else 0
+    return _lib.OcStartSpec(c.seed, c.env_offset, epoch, int(DRAWN["random_start_pos"]), float(DRAWN["rnd_obj_prob_thresh"]), 0, count)
+
+
+def plan_of_case(c):
+    """oc_step_plan's answer for the call the case makes (stand-in pointers; where the hints are withheld, the batch of
+    dispatch.batch_for with max_pots, batch_flags and max_free_cells cleared)."""
+    from overcooked_ai_amd import _lib, dispatch
+
+    table = table_of(c.table)
+    b = dispatch.batch_for(table, c.n_envs)
+    if not c.hints:
+        b.max_pots = b.batch_flags = b.max_free_cells = 0
+    options = _lib.OPT_AUTO_RESET | (_lib.OPT_PREDICATE_INTERACT if c.predicate else 0)
+    entry = "step" if c.entry == "step_out_of_place" else c.entry
+    return dispatch.step_plan(table, c.n_envs, entry, n_steps=c.n_steps if entry == "step_many" else 1, horizon=c.horizon, options=options,
+                              with_masks=with_masks(c), with_counts=with_counts(c), start=start_spec_of(c), batch=b)
+
+
+def env_kwargs(c):
+    """Keyword arguments of the VecOvercookedEnv the case runs on (layouts, n_envs and device aside; `predicate_interact` is an
+    attribute the caller sets)."""
+    kw = dict(horizon=c.horizon, layout_id=layout_ids(c), auto_reset=True, seed=c.seed, env_offset=c.env_offset, track_returns=c.returns,
+              track_events=with_counts(c), withhold_hints=not c.hints)
+    if c.start != "standard":
+        kw.update(DRAWN)
+    if c.start == "regen":
+        kw["regen_layout"] = True
+    return kw
+
+
+class OracleRun:
+    """The C oracle's run of one case on a fresh VecOvercookedEnv holding states_of(c).  step(k) plays step k with actions_of(c)[k]
+    and returns (rewards [n, 4], flags [n], event masks [n] u64); a restart at step k draws from epoch 1 + k, as the env's k-th step
+    after its construction does.  `state`, `ep_returns`, `layout_id` and the event counters (from the oracle's masks: [env][event]
+    [player] of the running episode, and of each env's last finished one) follow the run in place; `prev_state` is the state step k
+    acted on."""
+
+    def __init__(self, c):
+        from oracle import oracle as O
+
+        O.set_threads(min(16, len(os.sched_getaffinity(0))))
+        table = table_of(c.table)
+        self.c, self.O = c, O
+        self.orc = O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in table.specs])
+        self.layout_id = layout_ids(c)
+        self.state = self.prev_state = states_of(c).copy()
+        self.ep_returns = np.zeros((c.n_envs, 4), np.float32)
+        self.actions = actions_of(c)
+        self.counts = np.zeros((c.n_envs, 25, 2), np.int64)
+        self.counts_done = np.zeros((c.n_envs, 25, 2), np.int64)
+
+    def step(self, k):
+        c = self.c
+        start = None
+        if c.start != "standard":
+            start = self.O.start_spec(seed=c.seed, env_offset=c.env_offset, epoch=1 + k,
+                                      regen=(0, len(table_of(c.table))) if c.start == "regen" else None, **DRAWN)
+        self.prev_state = self.state
+        self.state, rew, fl = self.orc.step(self.state, self.actions[k], horizon=c.horizon, options=1, layout_id=self.layout_id,
+                                            ep_returns=self.ep_returns, start=start)
+        masks = self.orc.last_events
+        bits = ((masks[:, None] >> np.arange(50, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.int64)
+        self.counts += bits.reshape(c.n_envs, 25, 2)
+        fin = (fl & 1) != 0
+        self.counts_done[fin] = self.counts[fin]
+        self.counts[(fl & 4) != 0] = 0
+        return rew, fl, masks

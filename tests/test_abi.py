@@ -139,6 +139,10 @@ def test_argument_validation_without_gpu():
         # (... and the plan of a training step is oc_multi_agent_step's)
         assert L.oc_multi_agent_plan(er, horizon, 1, 0, 0, 0, None, text, len(text)) == -1
         assert L.oc_last_error().decode() == "oc_multi_agent_step: horizon must be in 1..65535"
+        # (... and the plan of a caller-actions call is its entry point's: oc_step, oc_step_many, oc_step_server_open)
+        for entry, name in enumerate(("oc_step", "oc_step_many", "oc_step_server_open")):
+            assert L.oc_step_plan(er, entry, horizon, 1, 3, 0, 0, None, text, len(text)) == -1, (name, horizon)
+            assert L.oc_last_error().decode() == name + ": horizon must be in 1..65535", (name, horizon)
         # ... and the general sequence of oc_multi_agent_step (a table of more than two pots) checks it too
         e.max_pots = 3
         assert calls["oc_multi_agent_step"]() == -1 and L.oc_last_error().decode() == "oc_multi_agent_step: horizon must be in 1..65535"
@@ -150,6 +154,17 @@ def test_argument_validation_without_gpu():
     assert L.oc_multi_agent_plan(er, 400, 1, 0, 0, 0, ctypes.byref(bad_start), text, len(text)) == -1
     assert L.oc_last_error().decode().startswith("oc_multi_agent_step: ")
     assert L.oc_multi_agent_plan(er, 400, 1, 0, 1, 0, None, text, len(text)) == 0 and text.value == b"nothing to launch (no envs)"
+    # oc_step_plan: its own buffer and entry, then every check of the entry point that its arguments can fail, under that name
+    assert L.oc_step_plan(er, 0, 400, 1, 1, 0, 0, None, None, 0) == -1 and b"oc_step_plan: no output buffer" in L.oc_last_error()
+    assert L.oc_step_plan(er, 0, 400, 1, 1, 0, 0, None, text, 0) == -1 and b"oc_step_plan: no output buffer" in L.oc_last_error()
+    assert L.oc_step_plan(er, 5, 400, 1, 1, 0, 0, None, text, len(text)) == -1 and b"oc_step_plan: entry must be" in L.oc_last_error()
+    for entry in (0, 1, 2):
+        assert L.oc_step_plan(None, entry, 400, 1, 1, 0, 0, None, text, len(text)) == -1 and b"batch is NULL" in L.oc_last_error()
+        assert text.value == b""
+    assert L.oc_step_plan(er, 1, 400, 1, 1, 0, 0, ctypes.byref(bad_start), text, len(text)) == -1
+    assert L.oc_last_error().decode().startswith("oc_step_many: start.rnd_obj_prob_thresh")
+    assert L.oc_step_plan(er, 0, 400, 1, 1, 0, 0, None, text, len(text)) == 0 and text.value == b"nothing to launch (no envs)"
+    assert L.oc_step_plan(er, 2, 400, 1, 1, 0, 0, None, text, len(text)) == -1 and L.oc_last_error() == b"oc_step_server_open: no envs"
     # the measurement aid: argument checks before the launch, nothing to do for an empty job
     assert L.oc_output_stores_only(64, 8, None, None, 0, None) == -1 and b"no rewards array" in L.oc_last_error()
     assert L.oc_output_stores_only(64, 8, 4100, None, 0, None) == -1 and b"16-byte aligned" in L.oc_last_error()

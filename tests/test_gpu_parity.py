@@ -53,7 +53,8 @@ def u8(t):
 @pytest.mark.parametrize("name", TRANSITION_CONFIGS)
 def test_golden_transitions(name, interact, manifest, gpu):
     """8 400 (state, joint action) -> (next state, rewards, event_infos) transitions of the reference per configuration,
-    through oc_step with event logging: the table-driven kernel (k_step3) and the predicate-network one (k_step)."""
+    through oc_step with event logging: the table-driven kernel (k_step1<EVENTS> on these grids of at most 64 cells; k_step3 above
+    that) and the predicate-network one (k_step)."""
     from overcooked_ai_amd.layouts import LayoutSpec
 
     cfg = manifest["configs"][name]["transitions"]
@@ -223,7 +224,7 @@ def test_step_vs_oracle_random_states(n_envs, gpu):
         assert np.array_equal(u8(env.ep_returns), ep_o)
         assert (fl_o & 2).any() or n_envs == 1
         # the same step in place without event logging = k_step1 (the transition on the wire format itself), and through
-        # OC_STEP's out-of-place form = k_step3
+        # OC_STEP's out-of-place form = k_step1 again (its planes written from LDS rows; k_step3 above 64 cells)
         lean = make_env(spec, n_envs, gpu, horizon=horizon, auto_reset=True)
         lean.set_packed_state(st)
         lean.ep_returns.copy_(torch.from_numpy(ep0))
@@ -935,7 +936,7 @@ def test_step_many_equals_single_steps_with_illegal_actions_and_resets(gpu):
 def test_random_starts_inside_the_fused_auto_reset(layouts, gpu):
     """start_state_fn = get_random_start_state_fn(random_start_pos, rnd_obj_prob_thresh) (mdp.py:1307-1369) as
     OvercookedEnv.reset uses it (env.py:288-319): every restart at the horizon, inside the step kernels, draws a new
-    start state (OcStartSpec) — rollout (k_rollout4), step and step_many (k_step3) against the oracle's restatement,
+    start state (OcStartSpec) — rollout (k_rollout4), step (k_step1) and step_many (k_step3) against the oracle's restatement,
     across several episode boundaries, with staggered timesteps so that envs restart at different steps."""
     from oracle import oracle as O
     from overcooked_ai_amd.layouts import LayoutTable, spec_from_name
@@ -999,7 +1000,7 @@ def test_random_starts_inside_the_fused_auto_reset(layouts, gpu):
 
 @pytest.mark.parametrize("layouts", ["cramped_room", "counter_circuit", "mixed"])
 def test_event_masks_and_episode_counters_on_the_fast_paths(layouts, gpu):
-    """event_infos / game_stats without the slow kernel: k_rollout4 and k_step3 emit the per-step event
+    """event_infos / game_stats without the slow kernel: k_rollout4, k_step1 (single steps) and k_step3 (step_many) emit the per-step event
     masks and keep per-env, per-episode counters (OcEventSink) — masks equal the oracle's event_infos of every step,
     the counters equal the popcount sums per episode, are published when the episode ends and restart from zero."""
     from oracle import oracle as O
