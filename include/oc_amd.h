@@ -703,6 +703,29 @@ int oc_observation_plan(const OcBatch* batch, int obs_dtype, int horizon, uint32
 int oc_step_plan(const OcBatch* batch, int entry, int horizon, uint32_t options, int n_steps, int with_masks, int with_counts,
                  const OcStartSpec* start, char* out, size_t out_size);
 
+/*
+ * oc_potential_plan, oc_featurize_plan (ABI 6: entry points added beside the others, as oc_multi_agent_plan was) — which kernel
+ * instance oc_potential / oc_featurize would launch for this batch (and this num_pots), as text; up to and including the
+ * instance's name ('>' for k_featurize) the text is stable:
+ *   "k_potential2 grid=10"                              every layout of the table has one or two pots (batch.max_pots 1 or 2)
+ *   "k_potential grid=10"                               any other table, and withheld hints (batch.max_pots == 0: unknown)
+ *   "k_featurize<LAY_LDS=true> grid=19, 78848 B LDS"    a table of at most 32 layouts, staged in LDS
+ *   "k_featurize<LAY_LDS=false> grid=..."               a larger table, read through L2
+ *   "nothing to launch (no envs)"
+ * grid: oc_potential runs one lane per env, 256 envs per workgroup: ceil(n_envs / 256); oc_featurize two lanes per env, 128 envs
+ * per workgroup: ceil(n_envs / 128), with 128 * (16 * state planes + 4 * (2 * (num_pots * 10 + 26) + 6)) bytes of dynamic LDS
+ * (the envs' states and their int16 feature rows; oc_potential asks for none).
+ * Both entry points plan a call before they launch anything (their argument checks, then the choice of the instance, the grid and
+ * the dynamic LDS bytes) and launch from that plan; this is the same plan put into words: every check applies (num_pots in 0..4,
+ * two-player layouts for oc_featurize, the batch; a refusal returns its code, with the entry point's own message in
+ * oc_last_error), the code that answers is told which arrays a call has, not where they are, and holds no launch — so it also runs
+ * on a host without a GPU.  Whether the device grants the dynamic LDS is asked when oc_featurize launches, and refused there.
+ * The call described has every required array, aligned.
+ *   out, out_size caller's text buffer (>= 256 bytes holds every answer)
+ */
+int oc_potential_plan(const OcBatch* batch, char* out, size_t out_size);
+int oc_featurize_plan(const OcBatch* batch, int num_pots, char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -296,16 +296,17 @@ def encode_lossless_u8(orc, state, horizon=400, layout_id=None):
 
 def featurize(orc, state, counter_goals="none", num_pots=2, layout_id=None):
     """featurize_state of every env: float32 [n_envs, 2, 2*(num_pots*10+26)+4]. counter_goals: "none" (the reference's
-    NO_COUNTERS_PARAMS) or "all" (every counter is a motion goal)."""
+    NO_COUNTERS_PARAMS), "all" (every counter is a motion goal) or a list of (x, y) counters."""
     n = state.shape[1]
     lid = orc._lid(layout_id, n)
     mask = None
-    if counter_goals == "all":
+    if counter_goals != "none":
+        listed = None if counter_goals == "all" else {tuple(g) for g in counter_goals}
         mask = np.zeros((orc.n, MAX_CELLS), dtype=np.int32)
         for l in range(orc.n):
-            t = orc.arr[l].terrain
-            for c in range(orc.arr[l].width * orc.arr[l].height):
-                mask[l, c] = 1 if t[c:c + 1] == b"X" else 0
+            t, w = orc.arr[l].terrain, orc.arr[l].width
+            for c in range(w * orc.arr[l].height):
+                mask[l, c] = 1 if t[c:c + 1] == b"X" and (listed is None or (c % w, c // w) in listed) else 0
     out = np.zeros((n, 2, 2 * (num_pots * 10 + 26) + 4), dtype=np.float32)
     rc = lib().oracle_featurize(orc.arr, orc.n, _ptr(lid, ctypes.c_uint16), _ptr(mask, ctypes.c_int32),
                                 _ptr(np.ascontiguousarray(state), ctypes.c_uint8), _ptr(out, ctypes.c_float),

@@ -24,7 +24,7 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_rollout_random", "oc_rollout_record", "oc_rollout_record_ex", "oc_encode_lossless", "oc_step_encode", "oc_rollout_encode", "oc_featurize", "oc_potential",
            "oc_phi_table_size", "oc_reset", "oc_reset_random", "oc_regen_layouts", "oc_shape_rewards", "oc_multi_agent_step",
            "oc_mailbox_open", "oc_mailbox_buffer", "oc_mailbox_step", "oc_mailbox_close", "oc_output_stores_only", "oc_rollout_plan", "oc_multi_agent_plan",
-           "oc_observation_plan", "oc_step_plan",
+           "oc_observation_plan", "oc_step_plan", "oc_potential_plan", "oc_featurize_plan",
            "oc_step_server_open", "oc_step_server_requests", "oc_step_server_responses", "oc_step_server_resume",
            "oc_step_server_play", "oc_step_server_sync", "oc_step_server_steps", "oc_step_server_close")
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
@@ -164,6 +164,10 @@ def load():
     L.oc_observation_plan.argtypes = [bp, i32, i32, u32, i32, i32, i32, sp, ctypes.c_char_p, ctypes.c_size_t]
     L.oc_step_plan.restype = i32
     L.oc_step_plan.argtypes = [bp, i32, i32, u32, i32, i32, i32, sp, ctypes.c_char_p, ctypes.c_size_t]
+    L.oc_potential_plan.restype = i32
+    L.oc_potential_plan.argtypes = [bp, ctypes.c_char_p, ctypes.c_size_t]
+    L.oc_featurize_plan.restype = i32
+    L.oc_featurize_plan.argtypes = [bp, i32, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

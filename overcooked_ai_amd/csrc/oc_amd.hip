@@ -22,7 +22,7 @@
 //   this file           launch dispatch and the extern "C" entry points declared in include/oc_amd.h: oc_rollout_random,
 //                       oc_multi_agent_step, oc_encode_lossless, oc_rollout_encode, oc_step, oc_step_many and oc_step_server_open plan
 //                       a call (checks, then choices; no launch, no device address), then launch from the plan; oc_rollout_plan,
-//                       oc_multi_agent_plan, oc_observation_plan and oc_step_plan put the plans into words
+//                       oc_multi_agent_plan, oc_observation_plan, oc_step_plan, oc_potential_plan and oc_featurize_plan put the plans into words
 //
 // Execution model: one lane per env, 64-lane wavefronts, 256-lane workgroups.  This is integer /
 // indexing work (no MFMA).  Per-env state arrives as coalesced 16-byte planes (1 KiB per wavefront
@@ -658,6 +658,63 @@ void launch_rollout_predicate(const oc_detail::Rollout4Call& c) {
 #undef GO
 }
 
+// ---- oc_featurize / oc_potential: plan a call (the argument checks, the kernel instance, the grid, the dynamic LDS bytes; no
+//      launch, no device address), then launch from the plan — or, by oc_featurize_plan / oc_potential_plan, describe it
+struct FeaturizePlan {
+    int rc = OC_OK;
+    bool nothing = false;  // no envs
+    bool lay_lds = false;  // the layout table fits LDS: k_featurize<true>
+    int n_planes = 0;
+    unsigned grid = 0;
+    size_t smem = 0;
+};
+
+// have: every required pointer is there; aligned: d_features is 16-byte aligned
+FeaturizePlan plan_featurize(const OcBatch* b, bool have, bool aligned, int num_pots) {
+    FeaturizePlan p;
+    int n_obj = 0;
+    if ((p.rc = check_batch(b, &n_obj)) != OC_OK) return p;
+    if (!have) { p.rc = fail(OC_EINVAL, "oc_featurize: NULL pointer"); return p; }
+    if (num_pots < 0 || num_pots > 4) { p.rc = fail(OC_EINVAL, "oc_featurize: num_pots must be in 0..4"); return p; }
+    if (!(b->batch_flags & OC_BATCH_TWO_PLAYERS)) { p.rc = fail(OC_EINVAL, "oc_featurize: needs 2-player layouts"); return p; }
+    if (!aligned) { p.rc = fail(OC_EINVAL, "oc_featurize: d_features must be 16-byte aligned"); return p; }
+    if (b->n_envs == 0) { p.nothing = true; return p; }
+    p.n_planes = 1 + n_obj;
+    const int total = 2 * (num_pots * 10 + 26) + 4;
+    p.smem = (size_t)FEAT_ENVS * p.n_planes * 16 + (size_t)FEAT_ENVS * 2 * (total + 2) * sizeof(int16_t);
+    p.grid = (unsigned)((b->n_envs + FEAT_ENVS - 1) / FEAT_ENVS);
+    p.lay_lds = b->n_layouts <= LDS_LAYOUT_MAX;
+    return p;
+}
+
+template <bool LAY_LDS>
+void launch_featurize(const FeaturizePlan& p, const OcBatch* b, const uint8_t* d_plan_blob, const uint32_t* d_plan_off,
+                      const void* d_state, float* d_features, int num_pots, hipStream_t s) {
+    if (!want_lds(k_featurize<LAY_LDS>, p.smem)) return;
+    hipLaunchKernelGGL((k_featurize<LAY_LDS>), dim3(p.grid), dim3(BLOCK), p.smem, s, b->d_layouts, b->n_layouts, b->d_layout_id,
+                       d_plan_blob, d_plan_off, (const uint4*)d_state, d_features, b->n_envs, b->width, b->height, p.n_planes, num_pots);
+}
+
+struct PotentialPlan {
+    int rc = OC_OK;
+    bool nothing = false;   // no envs
+    bool two_pots = false;  // the table's hint promises one or two pots everywhere: k_potential2
+    unsigned grid = 0;
+};
+
+// have: every required pointer is there; aligned: d_phi_tables and d_phi are 8-byte aligned
+PotentialPlan plan_potential(const OcBatch* b, bool have, bool aligned) {
+    PotentialPlan p;
+    int n_obj = 0;
+    if ((p.rc = check_batch(b, &n_obj)) != OC_OK) return p;
+    if (!have) { p.rc = fail(OC_EINVAL, "oc_potential: NULL pointer"); return p; }
+    if (!aligned) { p.rc = fail(OC_EINVAL, "oc_potential: d_phi_tables / d_phi must be 8-byte aligned"); return p; }
+    if (b->n_envs == 0) { p.nothing = true; return p; }
+    p.two_pots = b->max_pots >= 1 && b->max_pots <= 2;  // (0 = unknown: the general kernel)
+    p.grid = (unsigned)grid_for(b->n_envs);
+    return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -820,28 +877,21 @@ int oc_rollout_plan(const OcBatch* b, int horizon, uint32_t options, int64_t t0,
 
 int oc_featurize(const OcBatch* b, const uint8_t* d_plan_blob, const uint32_t* d_plan_off, const void* d_state,
                  float* d_features, int num_pots, void* stream) {
-    int n_obj = 0;
-    if (int rc = check_batch(b, &n_obj)) return rc;
-    if (!d_plan_blob || !d_plan_off || !d_state || !d_features) return fail(OC_EINVAL, "oc_featurize: NULL pointer");
-    if (num_pots < 0 || num_pots > 4) return fail(OC_EINVAL, "oc_featurize: num_pots must be in 0..4");
-    if (!(b->batch_flags & OC_BATCH_TWO_PLAYERS)) return fail(OC_EINVAL, "oc_featurize: needs 2-player layouts");
-    if (((uintptr_t)d_features & 15u) != 0) return fail(OC_EINVAL, "oc_featurize: d_features must be 16-byte aligned");
-    if (b->n_envs == 0) return OC_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const int n_planes = 1 + n_obj;
-    const int total = 2 * (num_pots * 10 + 26) + 4;
-    const size_t smem = (size_t)FEAT_ENVS * n_planes * 16 + (size_t)FEAT_ENVS * 2 * (total + 2) * sizeof(int16_t);
-    const dim3 grid((unsigned)((b->n_envs + FEAT_ENVS - 1) / FEAT_ENVS)), block(BLOCK);
-    if (b->n_layouts <= LDS_LAYOUT_MAX) {
-        if (!want_lds(k_featurize<true>, smem)) return check_launch("oc_featurize");
-        hipLaunchKernelGGL((k_featurize<true>), grid, block, smem, s, b->d_layouts, b->n_layouts, b->d_layout_id, d_plan_blob,
-                           d_plan_off, (const uint4*)d_state, d_features, b->n_envs, b->width, b->height, n_planes, num_pots);
-    } else {
-        if (!want_lds(k_featurize<false>, smem)) return check_launch("oc_featurize");
-        hipLaunchKernelGGL((k_featurize<false>), grid, block, smem, s, b->d_layouts, b->n_layouts, b->d_layout_id, d_plan_blob,
-                           d_plan_off, (const uint4*)d_state, d_features, b->n_envs, b->width, b->height, n_planes, num_pots);
-    }
+    const FeaturizePlan p = plan_featurize(b, d_plan_blob && d_plan_off && d_state && d_features, ((uintptr_t)d_features & 15u) == 0, num_pots);
+    if (p.rc != OC_OK || p.nothing) return p.rc;
+    if (p.lay_lds) launch_featurize<true>(p, b, d_plan_blob, d_plan_off, d_state, d_features, num_pots, (hipStream_t)stream);
+    else launch_featurize<false>(p, b, d_plan_blob, d_plan_off, d_state, d_features, num_pots, (hipStream_t)stream);
     return check_launch("oc_featurize");
+}
+
+int oc_featurize_plan(const OcBatch* b, int num_pots, char* out, size_t out_size) {
+    if (!out || out_size == 0) return fail(OC_EINVAL, "oc_featurize_plan: no output buffer");
+    out[0] = 0;
+    const FeaturizePlan p = plan_featurize(b, true, true, num_pots);
+    if (p.rc != OC_OK) return p.rc;
+    if (p.nothing) snprintf(out, out_size, "nothing to launch (no envs)");
+    else snprintf(out, out_size, "k_featurize<LAY_LDS=%s> grid=%u, %zu B LDS", p.lay_lds ? "true" : "false", p.grid, p.smem);
+    return OC_OK;
 }
 
 int oc_phi_table_size(void) { return PHI_BYTES; }
@@ -862,21 +912,26 @@ int oc_shape_rewards(const OcBatch* b, const float* d_rewards, const uint8_t* d_
 
 int oc_potential(const OcBatch* b, const uint8_t* d_plan_blob, const uint32_t* d_plan_off, const uint8_t* d_phi_tables,
                  const void* d_state, double* d_phi, void* stream) {
-    int n_obj = 0;
-    if (int rc = check_batch(b, &n_obj)) return rc;
-    if (!d_plan_blob || !d_plan_off || !d_phi_tables || !d_state || !d_phi) return fail(OC_EINVAL, "oc_potential: NULL pointer");
-    if (((uintptr_t)d_phi_tables & 7u) != 0 || ((uintptr_t)d_phi & 7u) != 0)
-        return fail(OC_EINVAL, "oc_potential: d_phi_tables / d_phi must be 8-byte aligned");
-    if (b->n_envs == 0) return OC_OK;
-    if (b->max_pots >= 1 && b->max_pots <= 2)
-        hipLaunchKernelGGL(k_potential2, dim3(grid_for(b->n_envs)), dim3(BLOCK), 0, (hipStream_t)stream, b->d_layouts,
-                           b->d_layout_id, d_plan_blob, d_plan_off, d_phi_tables, (const uint4*)d_state, d_phi, b->n_envs,
-                           b->width, b->height);
+    const PotentialPlan p = plan_potential(b, d_plan_blob && d_plan_off && d_phi_tables && d_state && d_phi,
+                                           ((uintptr_t)d_phi_tables & 7u) == 0 && ((uintptr_t)d_phi & 7u) == 0);
+    if (p.rc != OC_OK || p.nothing) return p.rc;
+    if (p.two_pots)
+        hipLaunchKernelGGL(k_potential2, dim3(p.grid), dim3(BLOCK), 0, (hipStream_t)stream, b->d_layouts, b->d_layout_id, d_plan_blob,
+                           d_plan_off, d_phi_tables, (const uint4*)d_state, d_phi, b->n_envs, b->width, b->height);
     else
-        hipLaunchKernelGGL(k_potential, dim3(grid_for(b->n_envs)), dim3(BLOCK), 0, (hipStream_t)stream, b->d_layouts,
-                           b->d_layout_id, d_plan_blob, d_plan_off, d_phi_tables, (const uint4*)d_state, d_phi, b->n_envs,
-                           b->width, b->height);
+        hipLaunchKernelGGL(k_potential, dim3(p.grid), dim3(BLOCK), 0, (hipStream_t)stream, b->d_layouts, b->d_layout_id, d_plan_blob,
+                           d_plan_off, d_phi_tables, (const uint4*)d_state, d_phi, b->n_envs, b->width, b->height);
     return check_launch("oc_potential");
+}
+
+int oc_potential_plan(const OcBatch* b, char* out, size_t out_size) {
+    if (!out || out_size == 0) return fail(OC_EINVAL, "oc_potential_plan: no output buffer");
+    out[0] = 0;
+    const PotentialPlan p = plan_potential(b, true, true);
+    if (p.rc != OC_OK) return p.rc;
+    if (p.nothing) snprintf(out, out_size, "nothing to launch (no envs)");
+    else snprintf(out, out_size, "%s grid=%u", p.two_pots ? "k_potential2" : "k_potential", p.grid);
+    return OC_OK;
 }
 
 int oc_reset(const OcBatch* b, void* d_state, const uint8_t* d_mask, float* d_ep_returns, void* stream) {

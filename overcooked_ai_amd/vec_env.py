@@ -516,6 +516,13 @@ class VecOvercookedEnv:
         _lib.check(rc, "oc_featurize")
         return out
 
+    def featurize_plan(self, num_pots=2):
+        """The kernel instance the next featurize(num_pots) launches, in oc_featurize_plan's words (up to and including '>' the
+        instance's name), with its grid and dynamic LDS bytes; counter_goals changes no choice."""
+        out = ctypes.create_string_buffer(320)
+        _lib.check(self.lib.oc_featurize_plan(self._bref, int(num_pots), out, len(out)), "oc_featurize_plan")
+        return out.value.decode()
+
     def _plan(self, counter_goals):
         key = counter_goals if isinstance(counter_goals, str) else tuple(sorted(map(tuple, counter_goals)))
         if key not in self._plans:
@@ -541,6 +548,13 @@ class VecOvercookedEnv:
                           self._phi_tables[gamma].data_ptr(), st.data_ptr(), out.data_ptr())
         _lib.check(rc, "oc_potential")
         return out
+
+    def potential_plan(self):
+        """The kernel instance the next potential() launches, in oc_potential_plan's words: "k_potential2 grid=..." or
+        "k_potential grid=..."; gamma changes no choice."""
+        out = ctypes.create_string_buffer(320)
+        _lib.check(self.lib.oc_potential_plan(self._bref, out, len(out)), "oc_potential_plan")
+        return out.value.decode()
 
     # ------------------------------------------------------------------ host <-> device state
     def set_packed_state(self, packed):

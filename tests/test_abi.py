@@ -165,6 +165,29 @@ def test_argument_validation_without_gpu():
     assert L.oc_last_error().decode().startswith("oc_step_many: start.rnd_obj_prob_thresh")
     assert L.oc_step_plan(er, 0, 400, 1, 1, 0, 0, None, text, len(text)) == 0 and text.value == b"nothing to launch (no envs)"
     assert L.oc_step_plan(er, 2, 400, 1, 1, 0, 0, None, text, len(text)) == -1 and L.oc_last_error() == b"oc_step_server_open: no envs"
+    # oc_potential_plan / oc_featurize_plan: their own buffer, then every check of the entry point that their arguments can fail
+    for plan in (lambda b_, out, size: L.oc_potential_plan(b_, out, size), lambda b_, out, size: L.oc_featurize_plan(b_, 2, out, size)):
+        assert plan(er, None, 0) == -1 and b"_plan: no output buffer" in L.oc_last_error()
+        assert plan(er, text, 0) == -1 and b"_plan: no output buffer" in L.oc_last_error()
+        assert plan(None, text, len(text)) == -1 and b"batch is NULL" in L.oc_last_error() and text.value == b""
+        assert plan(er, text, len(text)) == 0 and text.value == b"nothing to launch (no envs)"
+    wide = _lib.OcBatch(d_layouts=4096, d_layout_id=None, n_envs=4, n_layouts=1, width=40, height=40, max_pots=1, batch_flags=1)
+    assert L.oc_potential_plan(ctypes.byref(wide), text, len(text)) == -1 and b"grid shape" in L.oc_last_error()
+    assert L.oc_featurize_plan(ctypes.byref(wide), 2, text, len(text)) == -1 and b"grid shape" in L.oc_last_error()
+    for num_pots in (-1, 5):  # (refused before the empty-batch exit, as oc_featurize does, with its message)
+        assert L.oc_featurize_plan(er, num_pots, text, len(text)) == -1
+        assert L.oc_last_error() == b"oc_featurize: num_pots must be in 0..4"
+        assert L.oc_featurize(er, P, P, P, P, num_pots, None) == -1 and L.oc_last_error() == b"oc_featurize: num_pots must be in 0..4"
+    e.batch_flags = _lib.BATCH_NEW_DYNAMICS  # one player somewhere
+    assert L.oc_featurize_plan(er, 2, text, len(text)) == -1 and L.oc_last_error() == b"oc_featurize: needs 2-player layouts"
+    assert L.oc_featurize(er, P, P, P, P, 2, None) == -1 and L.oc_last_error() == b"oc_featurize: needs 2-player layouts"
+    assert L.oc_potential_plan(er, text, len(text)) == 0  # (phi is defined for one player)
+    e.batch_flags = _lib.BATCH_TWO_PLAYERS | _lib.BATCH_NEW_DYNAMICS
+    assert L.oc_featurize(er, P, P, P, None, 2, None) == -1 and L.oc_last_error() == b"oc_featurize: NULL pointer"
+    assert L.oc_featurize(er, P, P, P, P + 4, 2, None) == -1 and b"16-byte aligned" in L.oc_last_error()
+    assert L.oc_potential(er, P, P, P, P, None, None) == -1 and L.oc_last_error() == b"oc_potential: NULL pointer"
+    assert L.oc_potential(er, P, P, P, P, P + 4, None) == -1 and b"8-byte aligned" in L.oc_last_error()
+    assert L.oc_featurize(er, P, P, P, P, 2, None) == 0 and L.oc_potential(er, P, P, P, P, P, None) == 0  # no envs: nothing launched
     # the measurement aid: argument checks before the launch, nothing to do for an empty job
     assert L.oc_output_stores_only(64, 8, None, None, 0, None) == -1 and b"no rewards array" in L.oc_last_error()
     assert L.oc_output_stores_only(64, 8, 4100, None, 0, None) == -1 and b"16-byte aligned" in L.oc_last_error()
