@@ -58,13 +58,14 @@ and of the features (featurize_state, mdp.py:2579-2898; csrc/featurize.hpp), `pN
   counter_unreachable    an object on a counter that is no goal of, or out of reach for, some player (cost 255)
 """
 import functools
-import os
 from collections import namedtuple
 
 import numpy as np
 
+import train_cases  # noqa: F401 (its tables and rollout_cases': the import registers them)
+from case_support import env_layout_ids, layout_ids, new_oracle, register_grid, register_table, table_of
 from helpers import random_packed_states
-from train_cases import table_of as _train_table_of
+from rollout_cases import SEVEN
 
 N_ENVS = 2307  # 9 * 256 + 3 = 18 * 128 + 3
 GAMMAS = (0.99, 0.9)
@@ -163,11 +164,8 @@ CASES = tuple(CASES)
 assert len({c.id for c in CASES}) == len(CASES)
 
 
-@functools.lru_cache(maxsize=None)
-def table_of(name):
-    """The LayoutTable a case names: train_cases' and rollout_cases' tables, and four of this list's own."""
+def _table(name):
     from overcooked_ai_amd.layouts import LayoutSpec, LayoutTable, spec_from_name
-    from rollout_cases import SEVEN
 
     if name == "three_pots":
         oot = {"ingredients": ["onion", "onion", "tomato"]}
@@ -175,17 +173,14 @@ def table_of(name):
                                             start_all_orders=[{"ingredients": ["onion"] * 3}, oot, {"ingredients": ["tomato"] * 3}]))])
     if name == "eight_pots_serve_ring":
         return LayoutTable([LayoutSpec(dict(SEVEN, grid=EIGHT_POTS_SERVE_RING, layout_name=name))])
-    if name == "one_player_two_pots":
-        return LayoutTable([LayoutSpec(dict(spec_from_name("cramped_room").to_layout_dict(), layout_name=name, grid=ONE_PLAYER_TWO_POTS))])
-    if name == "mdp_test_tomato":  # the registry's mdp_test under the name the second set of POTENTIAL_CONSTANTS is keyed by
-        return LayoutTable([LayoutSpec(dict(spec_from_name("mdp_test").to_layout_dict(), layout_name=name))])
-    return _train_table_of(name)
+    assert name == "mdp_test_tomato"  # the registry's mdp_test under the name the second set of POTENTIAL_CONSTANTS is keyed by
+    return LayoutTable([LayoutSpec(dict(spec_from_name("mdp_test").to_layout_dict(), layout_name=name))])
 
 
-def layout_ids(c):
-    """Global env e is on layout e % K; None for a table of one layout."""
-    K = len(table_of(c.table))
-    return None if K == 1 else ((np.arange(c.n_envs) + c.env_offset) % K).astype(np.uint16)
+# this list's own tables
+for _name in ("three_pots", "eight_pots_serve_ring", "mdp_test_tomato"):
+    register_table(_name, functools.partial(_table, _name))
+register_grid("one_player_two_pots", ONE_PLAYER_TWO_POTS)
 
 
 def counter_goals_of(c):
@@ -596,7 +591,7 @@ def directed_states(spec, n, rng, kind="potential", counter_goals="none", first=
 def _states(table_name, n_envs, seed, env_offset, kind, goals):
     table = table_of(table_name)
     K = len(table)
-    lid = None if K == 1 else ((np.arange(n_envs) + env_offset) % K).astype(np.uint16)
+    lid = env_layout_ids(n_envs, env_offset, K)
     rng = np.random.default_rng(seed)
     goals = goals if isinstance(goals, str) else list(goals)
     if lid is None:
@@ -782,10 +777,7 @@ def env_kwargs(c):
 
 @functools.lru_cache(maxsize=None)
 def _oracle(table_name):
-    from oracle import oracle as O
-
-    O.set_threads(min(16, len(os.sched_getaffinity(0))))
-    return O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in table_of(table_name).specs])
+    return new_oracle(table_of(table_name).specs)
 
 
 @functools.lru_cache(maxsize=None)

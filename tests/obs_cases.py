@@ -22,15 +22,13 @@ of the envs outside their last 40 steps (the urgency layer is mixed inside every
 them inside the launch.  Rollout cases set `one_kernel`; their restarts draw the start state (rollout_cases.DRAWN) unless the case
 says "standard".  14 steps x 258 or 260 envs keep every row of a u8 trajectory a multiple of 16 bytes."""
 import ctypes
-import functools
-import os
 from collections import namedtuple
 
 import numpy as np
 
-from helpers import random_packed_states
-from rollout_cases import DRAWN
-from train_cases import table_of as _train_table_of
+import train_cases  # noqa: F401 (its tables and rollout_cases': the import registers them)
+from case_support import (DRAWN, caller_actions, instance_of, layout_ids, new_oracle, register_grid, seeded_states, start_spec_of,  # noqa: F401
+                          table_of)
 
 THIRDS = (0.95, 0.5, 0.05)  # counter fill of env e: THIRDS[e % 3] — crowded, half full and sparse envs side by side
 LIST_CAP = 14               # RE_LIST_CAP (csrc/rollout_encode.hpp): an env with more objects sends its sub-group through the dword loop
@@ -162,20 +160,10 @@ assert len({c.id for c in CASES}) == len(CASES)
 STREAMED = next(c for c in CASES if c.id == "encode_f32_epb1_streamed")
 
 
-@functools.lru_cache(maxsize=None)
-def table_of(name):
-    """The LayoutTable a case names: train_cases' and rollout_cases' tables, and three of this list's own."""
-    from overcooked_ai_amd.layouts import LayoutSpec, LayoutTable, spec_from_name
-
-    own = {"six_by_five": SIX_BY_FIVE, "eight_by_four": EIGHT_BY_FOUR, "seven_by_three": SEVEN_BY_THREE}
-    if name in own:
-        return LayoutTable([LayoutSpec(dict(spec_from_name("cramped_room").to_layout_dict(), layout_name=name, grid=own[name]))])
-    return _train_table_of(name)
-
-
-def instance_of(c):
-    """The instance the case is there for: the words of its plan up to and including the last '>'."""
-    return c.expect[:c.expect.rindex(">") + 1].split(" + ")[-1]
+# this list's own tables
+register_grid("six_by_five", SIX_BY_FIVE)
+register_grid("eight_by_four", EIGHT_BY_FOUR)
+register_grid("seven_by_three", SEVEN_BY_THREE)
 
 
 def env_bytes(c):
@@ -183,51 +171,15 @@ def env_bytes(c):
     return 2 * t.width * t.height * 26 * (1 if c.dtype == "u8" else 4)
 
 
-def layout_ids(c):
-    """Global env e is on layout e % K; None for a table of one layout."""
-    K = len(table_of(c.table))
-    return None if K == 1 else ((np.arange(c.n_envs) + c.env_offset) % K).astype(np.uint16)
-
-
-@functools.lru_cache(maxsize=None)
-def _states(cid):
-    c = next(x for x in CASES if x.id == cid)
-    table, lid = table_of(c.table), layout_ids(c)
-    rng = np.random.default_rng(c.seed)
-    fill = None if c.fill is None else (lambda e: c.fill[e % 3])
-    if lid is None:
-        st = random_packed_states(table.specs[0], c.n_envs, rng, timestep_max=c.horizon - 1, counter_fill=fill)
-    else:
-        st = np.zeros((table.n_planes, c.n_envs, 16), np.uint8)
-        for l in range(len(table)):
-            idx = np.nonzero(lid == l)[0]
-            st[:, idx] = random_packed_states(table.specs[l], len(idx), rng, timestep_max=c.horizon - 1, counter_fill=fill)
-    st.setflags(write=False)
-    return st
-
-
 def states_of(c):
     """uint8 [n_planes, n_envs, 16], read-only: the states the call starts from (computed once per case)."""
-    return _states(c.id)
-
-
-@functools.lru_cache(maxsize=None)
-def _actions(cid):
-    c = next(x for x in CASES if x.id == cid)
-    rng = np.random.default_rng(1000 + c.seed)
-    a = rng.integers(0, 6, size=(c.n_steps, c.n_envs, 2)).astype(np.uint8)
-    for k in range(c.n_steps):  # N_BAD envs per step, no env twice in a run, once the batch's last env
-        for j in range(N_BAD):
-            a[k, (N_BAD * k + j) * ((c.n_envs - 2) // (N_BAD * c.n_steps)), (k + j) & 1] = 6 + 83 * j
-    a[1, c.n_envs - 1, 0] = 9
-    a.setflags(write=False)
-    return a
+    return seeded_states(c, counter_fill=c.fill)
 
 
 def actions_of(c):
     """uint8 [n_steps, n_envs, 2], read-only: the caller's actions, N_BAD illegal entries (6, 89, 172) per step and one more at step
     1; None for the random policy."""
-    return _actions(c.id) if c.call in ("rollout_actions", "step_encode") else None
+    return caller_actions(c.n_steps, c.n_envs, N_BAD, c.seed) if c.call in ("rollout_actions", "step_encode") else None
 
 
 def n_illegal(c):
@@ -242,9 +194,7 @@ def plan_of_case(c):
     code = _lib.OBS_U8 if c.dtype == "u8" else _lib.OBS_F32
     if c.call == "encode":
         return dispatch.observation_plan(table_of(c.table), c.n_envs, 0, code, horizon=c.horizon)
-    start = None
-    if c.start == "drawn":
-        start = _lib.OcStartSpec(c.seed, c.env_offset, 1, int(DRAWN["random_start_pos"]), float(DRAWN["rnd_obj_prob_thresh"]), 0, 0)
+    start = start_spec_of(c)
     K = 1 if c.call == "step_encode" else c.n_steps
     options = _lib.OPT_AUTO_RESET | _lib.OPT_ONE_KERNEL
     b = dispatch.batch_for(table_of(c.table), c.n_envs)
@@ -288,10 +238,8 @@ class OracleRun:
     def __init__(self, c):
         from oracle import oracle as O
 
-        O.set_threads(min(16, len(os.sched_getaffinity(0))))
-        table = table_of(c.table)
         self.c, self.O = c, O
-        self.orc = O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in table.specs])
+        self.orc = new_oracle(table_of(c.table).specs)
         self.layout_id = layout_ids(c)
         self.state = states_of(c).copy()
         self.ep_returns = np.zeros((c.n_envs, 4), np.float32)

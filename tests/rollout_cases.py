@@ -10,24 +10,19 @@ Unless a case is there for the standard start it has a nonzero env_offset, drawn
 rnd_obj_prob_thresh 0.35: pots that arrive full, players that arrive holding soups) and at least two restarts per env inside
 the launch (horizon < n_steps / 2)."""
 import functools
-import os
 from collections import namedtuple
 
 import numpy as np
 
+from case_support import DRAWN, EventCounts, layout_ids, new_oracle, register_table, table_of, tf as _tf  # noqa: F401 (DRAWN, table_of, layout_ids: for the tests)
 from helpers import CANONICAL_5
 
 PIPE_MAX = 98304       # envs up to which the one-wavefront instances read a step ahead (1.5 wavefronts per SIMD, 1 024 SIMDs)
 N_LEAN = 131072 + 64   # above it, and not whole 256-env workgroups: the lean one-wavefront instances
 N_RAGGED = 5000        # below it, not whole workgroups: the pipelined one-wavefront instances
 N_WHOLE = 4096         # whole workgroups, one round: the mover / interact kernel
-DRAWN = {"random_start_pos": True, "rnd_obj_prob_thresh": 0.35}
 SEVEN = {"grid": "XPPPPPX\nO 1 2 O\nX     X\nXDPSPTX", "onion_time": 3, "tomato_time": 5, "onion_value": 7, "tomato_value": 4}
 BIG_4 = ("marshmallow_experiment", "inverse_marshmallow_experiment", "marshmallow_experiment_coordination", "small_corridor")
-
-
-def _tf(v):
-    return "true" if v else "false"
 
 
 def r4(UNIFORM=False, MAXP=8, LAY_LDS=False, MODE=0, OUT=False, OLD=True, EV=False, PIPE=True, RU=False, CW=2, NOCONF=False,
@@ -148,9 +143,8 @@ CASES = tuple(CASES)
 assert len({c.id for c in CASES}) == len(CASES)
 
 
-@functools.lru_cache(maxsize=None)
-def table_of(name):
-    """The LayoutTable a case names."""
+def _composed(name):
+    """The tables the cases name beside single registry layouts (case_support.table_of: those, and `<layout>_old`)."""
     from overcooked_ai_amd.layout_gen import reference_generated_layouts
     from overcooked_ai_amd.layouts import LayoutSpec, LayoutTable, spec_from_name
 
@@ -169,17 +163,12 @@ def table_of(name):
         return LayoutTable([spec_from_name(nm) for nm in BIG_4] * 9)
     if name == "generated_4096":
         return LayoutTable(reference_generated_layouts(4096))
-    if name == "seven_pots":
-        return LayoutTable([LayoutSpec(SEVEN)])
-    if name.endswith("_old"):
-        return LayoutTable([spec_from_name(name[:-4], old_dynamics=True)])
-    return LayoutTable([spec_from_name(name)])
+    assert name == "seven_pots"
+    return LayoutTable([LayoutSpec(SEVEN)])
 
 
-def layout_ids(c):
-    """Global env e starts on layout e % K; None for a table of one layout."""
-    K = len(table_of(c.table))
-    return None if K == 1 else ((np.arange(c.n_envs) + c.env_offset) % K).astype(np.uint16)
+for _name in ("mix5", "canonical_5_x8", "canonical_4_old", "canonical_4_old_x9", "big_4", "big_4_x9", "generated_4096", "seven_pots"):
+    register_table(_name, functools.partial(_composed, _name))
 
 
 def plan_of(table, n_envs, n_steps, t0, horizon, tiled=False, one_wavefront=False, outputs=True, events=0, start=None, regen=None,
@@ -213,8 +202,7 @@ class OracleLaunch:
     def __init__(self, specs, n, layout_id=None, seed=0, env_offset=0, horizon=400, start=None, regen=None, events=False):
         from oracle import oracle as O
 
-        O.set_threads(min(16, len(os.sched_getaffinity(0))))  # the envs are independent
-        self.O, self.orc = O, O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in specs])
+        self.O, self.orc = O, new_oracle(specs)
         self.n, self.seed, self.env_offset, self.horizon = n, seed, env_offset, horizon
         self.start, self.regen, self.events = dict(start or {}), regen, events
         self.layout_id = None if layout_id is None else np.ascontiguousarray(layout_id, dtype=np.uint16).copy()
@@ -223,8 +211,8 @@ class OracleLaunch:
             self.state = self.orc.reset_random(self.state, seed=seed, env_offset=env_offset, epoch=0, layout_id=self.layout_id,
                                                **self.start)
         self.ep_returns = np.zeros((n, 4), np.float32)
-        self.counts = np.zeros((n, 25, 2), np.int64)       # [env][event][player] of the running episode
-        self.counts_done = np.zeros((n, 25, 2), np.int64)  # ... of each env's last finished episode
+        self.event_counts = EventCounts(n)
+        self.counts, self.counts_done = self.event_counts.running, self.event_counts.published
 
     def _spec(self, epoch):
         if not self.start and self.regen is None:
@@ -248,11 +236,7 @@ class OracleLaunch:
                 acts = self.O.random_actions(self.seed, self.env_offset, t0 + c0 + j, self.n)
                 self.state, rew[j], fl[j] = self.orc.step(self.state, acts, start=self._spec(epoch + c0 + j), **kw)
                 masks[j] = self.orc.last_events
-                bits = ((masks[j][:, None] >> np.arange(50, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.int64)
-                self.counts += bits.reshape(self.n, 25, 2)
-                fin = (fl[j] & 1) != 0
-                self.counts_done[fin] = self.counts[fin]
-                self.counts[(fl[j] & 4) != 0] = 0
+                self.event_counts.update(masks[j], finished=(fl[j] & 1) != 0, cleared=(fl[j] & 4) != 0)  # (cleared at the restart)
             yield c0, rew, fl, masks
 
 

@@ -15,15 +15,13 @@ default run is 20 steps at horizon 11, so roughly every env restarts inside the 
 within every wavefront.  Unless a case says "standard", a restart draws its start state (rollout_cases.DRAWN); "regen" also
 re-draws the env's layout from the whole table.  N_BAD envs per step get an illegal action (6, 89, 172), no env twice, and the
 batch's last env one more at step 1."""
-import functools
-import os
 from collections import namedtuple
 
 import numpy as np
 
-from helpers import random_packed_states
-from rollout_cases import DRAWN
-from train_cases import table_of as _train_table_of
+import train_cases  # noqa: F401 (its tables and rollout_cases': the import registers them)
+from case_support import (DRAWN, EventCounts, caller_actions, instance_of, layout_ids, new_oracle, register_grid, seeded_states,  # noqa: F401
+                          start_spec_of, table_of, tf as _tf)
 
 N_ENVS = 2307   # 9 * 256 + 3
 N_BAD = 3       # illegal actions per step
@@ -32,10 +30,6 @@ FOUR_BY_FOUR = "XPXX\nO12X\nX  S\nXDXX"  # 16 cells: one object plane, one pot
 EIGHT_BY_EIGHT = "XXPXXPXX\nO      X\nX 1    X\nX      O\nX    2 X\nX      X\nX      X\nXDXXSXXX"
 ENTRIES = ("step", "step_out_of_place", "step_many", "server")
 SERVER_SPLIT = 10  # a server case plays its first 10 steps in one play(), syncs, and plays the others as single step() calls
-
-
-def _tf(v):
-    return "true" if v else "false"
 
 
 def step1(UNIFORM, MAXP, LAY_LDS, EVENTS=False):
@@ -149,20 +143,9 @@ CASES = tuple(CASES)
 assert len({c.id for c in CASES}) == len(CASES)
 
 
-@functools.lru_cache(maxsize=None)
-def table_of(name):
-    """The LayoutTable a case names: train_cases' and rollout_cases' tables, and two of this list's own."""
-    from overcooked_ai_amd.layouts import LayoutSpec, LayoutTable, spec_from_name
-
-    own = {"four_by_four": FOUR_BY_FOUR, "eight_by_eight": EIGHT_BY_EIGHT}
-    if name in own:
-        return LayoutTable([LayoutSpec(dict(spec_from_name("cramped_room").to_layout_dict(), layout_name=name, grid=own[name]))])
-    return _train_table_of(name)
-
-
-def instance_of(c):
-    """The instance the case is there for: the words of its plan up to and including the last '>'."""
-    return c.expect[:c.expect.rindex(">") + 1].split(" + ")[-1]
+# this list's own tables
+register_grid("four_by_four", FOUR_BY_FOUR)
+register_grid("eight_by_eight", EIGHT_BY_EIGHT)
 
 
 def with_masks(c):
@@ -193,63 +176,18 @@ def possible_events(table):
     return names
 
 
-def layout_ids(c):
-    """Global env e starts on layout e % K; None for a table of one layout."""
-    K = len(table_of(c.table))
-    return None if K == 1 else ((np.arange(c.n_envs) + c.env_offset) % K).astype(np.uint16)
-
-
-@functools.lru_cache(maxsize=None)
-def _states(cid):
-    c = next(x for x in CASES if x.id == cid)
-    table, lid = table_of(c.table), layout_ids(c)
-    rng = np.random.default_rng(c.seed)
-    if lid is None:
-        st = random_packed_states(table.specs[0], c.n_envs, rng, timestep_max=c.horizon - 1)
-    else:
-        st = np.zeros((table.n_planes, c.n_envs, 16), np.uint8)
-        for l in range(len(table)):
-            idx = np.nonzero(lid == l)[0]
-            st[:, idx] = random_packed_states(table.specs[l], len(idx), rng, timestep_max=c.horizon - 1)
-    st.setflags(write=False)
-    return st
-
-
 def states_of(c):
     """uint8 [n_planes, n_envs, 16], read-only: the states the call starts from (computed once per case)."""
-    return _states(c.id)
-
-
-@functools.lru_cache(maxsize=None)
-def _actions(cid):
-    c = next(x for x in CASES if x.id == cid)
-    rng = np.random.default_rng(1000 + c.seed)
-    a = rng.integers(0, 6, size=(c.n_steps, c.n_envs, 2)).astype(np.uint8)
-    for k in range(c.n_steps):  # N_BAD envs per step, no env twice in a run, once the batch's last env
-        for j in range(N_BAD):
-            a[k, (N_BAD * k + j) * ((c.n_envs - 2) // (N_BAD * c.n_steps)), (k + j) & 1] = 6 + 83 * j
-    a[1, c.n_envs - 1, 0] = 9
-    a.setflags(write=False)
-    return a
+    return seeded_states(c)
 
 
 def actions_of(c):
     """uint8 [n_steps, n_envs, 2], read-only: the caller's actions, N_BAD illegal entries (6, 89, 172) per step and one more at step 1."""
-    return _actions(c.id)
+    return caller_actions(c.n_steps, c.n_envs, N_BAD, c.seed)
 
 
 def n_illegal(c):
     return N_BAD * c.n_steps + 1
-
-
-def start_spec_of(c, epoch=1):
-    """The _lib.OcStartSpec the env hands to the library at `epoch`; None for the standard start."""
-    from overcooked_ai_amd import _lib
-
-    if c.start == "standard":
-        return None
-    count = len(table_of(c.table)) if c.start == "regen" else 0
-    return _lib.OcStartSpec(c.seed, c.env_offset, epoch, int(DRAWN["random_start_pos"]), float(DRAWN["rnd_obj_prob_thresh"]), 0, count)
 
 
 def plan_of_case(c):
@@ -289,16 +227,14 @@ class OracleRun:
     def __init__(self, c):
         from oracle import oracle as O
 
-        O.set_threads(min(16, len(os.sched_getaffinity(0))))
-        table = table_of(c.table)
         self.c, self.O = c, O
-        self.orc = O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in table.specs])
+        self.orc = new_oracle(table_of(c.table).specs)
         self.layout_id = layout_ids(c)
         self.state = self.prev_state = states_of(c).copy()
         self.ep_returns = np.zeros((c.n_envs, 4), np.float32)
         self.actions = actions_of(c)
-        self.counts = np.zeros((c.n_envs, 25, 2), np.int64)
-        self.counts_done = np.zeros((c.n_envs, 25, 2), np.int64)
+        self.event_counts = EventCounts(c.n_envs)
+        self.counts, self.counts_done = self.event_counts.running, self.event_counts.published
 
     def step(self, k):
         c = self.c
@@ -310,9 +246,5 @@ class OracleRun:
         self.state, rew, fl = self.orc.step(self.state, self.actions[k], horizon=c.horizon, options=1, layout_id=self.layout_id,
                                             ep_returns=self.ep_returns, start=start)
         masks = self.orc.last_events
-        bits = ((masks[:, None] >> np.arange(50, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.int64)
-        self.counts += bits.reshape(c.n_envs, 25, 2)
-        fin = (fl & 1) != 0
-        self.counts_done[fin] = self.counts[fin]
-        self.counts[(fl & 4) != 0] = 0
+        self.event_counts.update(masks, finished=(fl & 1) != 0, cleared=(fl & 4) != 0)  # (cleared at the restart)
         return rew, fl, masks

@@ -5,8 +5,6 @@
                np.random.seed(0)), env e -> terrain e % 4096: per-env divergent terrain from a table in HBM
 Checked against the C oracle (pinned to the reference by tests/test_oracle_golden.py): packed state, rewards, flags
 and the u8 observation, bit for bit, across an episode boundary, for every rollout kernel family."""
-import os
-
 import numpy as np
 import pytest
 
@@ -15,25 +13,12 @@ from helpers import CANONICAL_5, select_kernel
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+
+from case_support import new_oracle as _oracle  # noqa: E402
+from gpu_support import gpu  # noqa: E402, F401
+
 N = 65536
 KERNELS = ["default", "lane_pair", "predicate_interact"]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test run without a GPU")
-    from overcooked_ai_amd import _lib
-
-    _lib.load()
-    return torch.device("cuda:0")
-
-
-def _oracle(specs):
-    from oracle import oracle as O
-
-    O.set_threads(min(16, len(os.sched_getaffinity(0))))  # the envs are independent
-    return O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in specs])
 
 
 def _env(layouts, gpu, **kw):

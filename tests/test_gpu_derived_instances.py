@@ -16,37 +16,18 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-GUARD = 3        # guard rows (envs) on either side of the output
+from case_support import compare  # noqa: E402
+from gpu_support import GUARD, gpu, guarded, guards_untouched  # noqa: E402, F401
+
 SENTINEL = -7.0  # the fill of the whole array; the guards are compared with it, the rows between them with the oracle
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test run without a GPU")
-    from overcooked_ai_amd import _lib
-
-    _lib.load()  # fail loudly if the HIP extension is missing
-    return torch.device("cuda:0")
-
-
-def _guarded(rows, row_shape, dtype, gpu):
-    """(rows [GUARD, GUARD + rows) of a new array of rows + 2 * GUARD, all of it SENTINEL; the guard rows before; those after).
-    GUARD feature rows are a multiple of 32 bytes and GUARD potentials of 8, so the slice keeps the alignment the entry points ask for."""
-    whole = torch.full((rows + 2 * GUARD,) + tuple(row_shape), SENTINEL, dtype=dtype, device=gpu)
-    out = whole[GUARD:GUARD + rows]
+def _output_between_guards(rows, row_shape, dtype, gpu):
+    """The output between GUARD rows on either side.  GUARD feature rows are a multiple of 32 bytes and GUARD potentials of 8, so the
+    slice keeps the alignment the entry points ask for."""
+    out, guards = guarded(rows, row_shape, dtype, SENTINEL, gpu, before=GUARD)
     assert out.is_contiguous() and out.data_ptr() % (16 if row_shape else 8) == 0
-    return out, whole[:GUARD], whole[GUARD + rows:]
-
-
-def _first_difference(case, what, got, want, layout_id):
-    bad = np.nonzero((got != want).reshape(len(got), -1).any(axis=1))[0]
-    e = int(bad[0])
-    g, w = got[e].ravel(), want[e].ravel()
-    at = np.nonzero(g != w)[0]
-    return "%s, %s: %d of %d envs differ, the first is env %d (layout %d, situations %s): %d values, the first at %d: got %r, reference %r" % (
-        case.id, what, len(bad), len(got), e, 0 if layout_id is None else int(layout_id[e]), sorted(_situations(case, e)), len(at), int(at[0]),
-        g[at[:6]].tolist(), w[at[:6]].tolist())
+    return out, guards
 
 
 def _situations(case, e):
@@ -71,6 +52,7 @@ def _new_env(case, gpu, hints=None):
 def test_every_derived_instance_against_the_oracle(case, gpu):
     n, lid = case.n_envs, DC.layout_ids(case)
     env = _new_env(case, gpu)
+    context = lambda e: ", situations %s" % sorted(_situations(case, e))  # noqa: E731
 
     # 1. the plan of the call, on this device: the instance the case is there for
     plan = env.potential_plan() if case.kind == "potential" else env.featurize_plan(case.num_pots)
@@ -82,12 +64,11 @@ def test_every_derived_instance_against_the_oracle(case, gpu):
         for gamma in DC.GAMMAS:
             want = DC.oracle_run(case, gamma)
             assert want.dtype == np.float64 and np.isfinite(want).all() and (want > 0).all()
-            out, before, after = _guarded(n, (), torch.float64, gpu)
+            out, guards = _output_between_guards(n, (), torch.float64, gpu)
             assert env.potential(gamma, out=out).data_ptr() == out.data_ptr()
             got = out.cpu().numpy()
-            if not np.array_equal(got, want):
-                pytest.fail(_first_difference(case, "phi at gamma %s" % gamma, got, want, lid))
-            assert bool((before == SENTINEL).all()) and bool((after == SENTINEL).all()), "%s: guard rows written" % case.id
+            compare(case, None, "phi at gamma %s" % gamma, got, want, lid, context=context)
+            guards_untouched(case, "potentials", guards, SENTINEL)
             if case.id == "potential_hints_withheld":  # ... and k_potential2 on the same states: the two kernels agree
                 env2 = _new_env(case, gpu, hints=True)
                 assert env2.potential_plan().startswith("k_potential2 grid=")
@@ -96,9 +77,7 @@ def test_every_derived_instance_against_the_oracle(case, gpu):
         total = 2 * (case.num_pots * 10 + 26) + 4
         want = DC.oracle_run(case)
         assert want.dtype == np.float32 and want.shape == (n, 2, total) and np.isfinite(want).all()
-        out, before, after = _guarded(n, (2, total), torch.float32, gpu)
+        out, guards = _output_between_guards(n, (2, total), torch.float32, gpu)
         assert env.featurize(case.num_pots, DC.counter_goals_of(case), out=out).data_ptr() == out.data_ptr()
-        got = out.cpu().numpy()
-        if not np.array_equal(got, want):
-            pytest.fail(_first_difference(case, "features", got, want, lid))
-        assert bool((before == SENTINEL).all()) and bool((after == SENTINEL).all()), "%s: guard rows written" % case.id
+        compare(case, None, "features", out.cpu().numpy(), want, lid, context=context)
+        guards_untouched(case, "features", guards, SENTINEL)

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from case_support import EventCounts
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -315,18 +316,15 @@ def test_vec_multi_agent_event_counters():
         assert env.plan() == expect
         orc = O.Oracle([O.mdp_from_layout_dict(spec.to_layout_dict())])
         st = orc.reset(orc.new_state(n))
-        counts = np.zeros((n, 25, 2), np.int64)
-        done_counts = np.zeros((n, 25, 2), np.int64)
+        events = EventCounts(n)
+        counts, done_counts = events.running, events.published
         gen = torch.Generator(device=dev).manual_seed(3)
         for t in range(75):
             acts = torch.randint(0, 6, (n, 2), dtype=torch.uint8, device=dev, generator=gen)
             env.step(acts)
             st, _, f = orc.step(st, acts.cpu().numpy(), horizon=horizon, options=0)
-            ev = orc.last_events
-            counts += ((ev[:, None] >> np.arange(50, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.int64).reshape(n, 25, 2)
             fin = (f & 1) != 0
-            done_counts[fin] = counts[fin]
-            counts[fin] = 0
+            events.update(orc.last_events, finished=fin, cleared=fin)  # (no auto-reset here: cleared where done)
             st = orc.reset(st, mask=fin.astype(np.uint8))
         assert np.array_equal(env.venv.get_packed_state(), st)
         got = env.venv.event_counts.cpu().numpy().astype(np.int64)

@@ -5,8 +5,6 @@ global env offset of an inner rank), and every instance `oc_rollout_random` can 
 the C oracle (pinned to the reference by
 tests/test_oracle_golden.py): every reward quad and flag byte of every env-step, the final packed states and the
 episode returns, bit for bit.  The oracle runs in 400-step chunks to bound host memory."""
-import os
-
 import numpy as np
 import pytest
 
@@ -16,40 +14,11 @@ from helpers import CANONICAL_5
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+
+from case_support import EventCounts, compare, new_oracle as _oracle  # noqa: E402
+from gpu_support import gpu, packed_counters  # noqa: E402, F401
+
 HORIZON, T = 400, 4000
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test run without a GPU")
-    from overcooked_ai_amd import _lib
-
-    _lib.load()
-    return torch.device("cuda:0")
-
-
-def _oracle(specs):
-    from oracle import oracle as O
-
-    O.set_threads(min(16, len(os.sched_getaffinity(0))))  # the envs are independent
-    return O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in specs])
-
-
-def _first_difference(got, want, lid, c0=0):
-    """'; first at (step, env, ...) on layout L: got x, oracle y' for two arrays [steps or planes][envs]..., for an assertion's message"""
-    bad = np.argwhere(np.asarray(got) != np.asarray(want))
-    if len(bad) == 0:
-        return ""
-    i = tuple(bad[0])
-    return "; %d values differ, first at (step or plane, env, ...) %s on layout %d: got %s, oracle %s" % (
-        len(bad), [int(i[0]) + c0] + [int(v) for v in i[1:]], 0 if lid is None else int(lid[i[1]]), got[i], want[i])
-
-
-def _packed_counters(t):
-    """[n_envs, 25] int32, player 0 in the low half-word -> [n_envs, 25, 2]"""
-    c = t.cpu().numpy().astype(np.int64)
-    return np.stack([c & 0xFFFF, (c >> 16) & 0xFFFF], -1)
 
 
 def _long_launch_against_oracle(gpu, table, n, lid=None, env_offset=0, seed=0, steps=T, horizon=HORIZON, start=None,
@@ -77,7 +46,8 @@ def _long_launch_against_oracle(gpu, table, n, lid=None, env_offset=0, seed=0, s
     rew = torch.zeros((steps, n, 4), dtype=torch.float32, device=gpu) if outputs else None
     fl = torch.zeros((steps // 8, n, 8) if flags_tiled8 else (steps, n), dtype=torch.uint8, device=gpu) if outputs else None
     ev = torch.zeros((steps, n), dtype=torch.int64, device=gpu) if events == 2 else None
-    assert np.array_equal(env.get_packed_state(), run.state), "first states differ"
+    what = "launch of %d envs x %d steps" % (n, steps)
+    compare(what, t0, "first states", env.get_packed_state(), run.state, lid, env_axis=1)
     epoch = env.reset_epoch
     env.rollout_random(steps, rew, fl, events_out=ev, flags_tiled8=flags_tiled8)  # ONE call
     if flags_tiled8:
@@ -86,25 +56,22 @@ def _long_launch_against_oracle(gpu, table, n, lid=None, env_offset=0, seed=0, s
     for c0, rew_o, fl_o, masks_o in run.chunks(steps, t0=t0, epoch=epoch):
         k = len(fl_o)
         if outputs:
-            got_fl, got_rew = fl[c0:c0 + k].cpu().numpy(), rew[c0:c0 + k].cpu().numpy()
-            assert np.array_equal(got_fl, fl_o), "flags differ in steps %d..%d%s" % (c0, c0 + k, _first_difference(got_fl, fl_o, lid, c0))
-            assert np.array_equal(got_rew, rew_o), "rewards differ in steps %d..%d%s" % (c0, c0 + k, _first_difference(got_rew, rew_o, lid, c0))
+            # ([step][env]...: the step a message names is the chunk's first, the index it gives starts with the step inside the chunk)
+            compare(what, c0, "flags of steps %d..%d" % (c0, c0 + k), fl[c0:c0 + k].cpu().numpy(), fl_o, lid, env_axis=1)
+            compare(what, c0, "rewards of steps %d..%d" % (c0, c0 + k), rew[c0:c0 + k].cpu().numpy(), rew_o, lid, env_axis=1)
         if ev is not None:
-            got_ev = ev[c0:c0 + k].cpu().numpy().view(np.uint64)
-            assert np.array_equal(got_ev, masks_o), "event masks differ in steps %d..%d%s" % (c0, c0 + k, _first_difference(got_ev, masks_o, lid, c0))
+            compare(what, c0, "event masks of steps %d..%d" % (c0, c0 + k), ev[c0:c0 + k].cpu().numpy().view(np.uint64), masks_o, lid, env_axis=1)
         restarts += int(((fl_o & 4) != 0).sum())
         sparse += float(rew_o[..., :2].sum())
         shaped += float(rew_o[..., 2:].sum())
+    last = t0 + steps - 1
     if env.regen is not None:
-        assert np.array_equal(env.layout_ids(), run.layout_id), "layout ids differ" + _first_difference(env.layout_ids()[None], run.layout_id[None], None)
-    got_st = env.get_packed_state()
-    assert np.array_equal(got_st, run.state), "final states differ" + _first_difference(got_st, run.state, lid)
-    got_ep = env.ep_returns.cpu().numpy()
-    assert np.array_equal(got_ep, run.ep_returns), "episode returns differ" + _first_difference(got_ep[None], run.ep_returns[None], lid)
+        compare(what, last, "layout ids", env.layout_ids(), run.layout_id, None)
+    compare(what, last, "final states", env.get_packed_state(), run.state, lid, env_axis=1)
+    compare(what, last, "episode returns", env.ep_returns.cpu().numpy(), run.ep_returns, lid)
     if events:
-        got_c, got_d = _packed_counters(env.event_counts), _packed_counters(env.event_counts_done)
-        assert np.array_equal(got_c, run.counts), "running event counters differ" + _first_difference(got_c[None], run.counts[None], lid)
-        assert np.array_equal(got_d, run.counts_done), "published event counters differ" + _first_difference(got_d[None], run.counts_done[None], lid)
+        compare(what, last, "running event counters", packed_counters(env.event_counts), run.counts, lid)
+        compare(what, last, "published event counters", packed_counters(env.event_counts_done), run.counts_done, lid)
         assert run.counts_done.sum() > 0
     assert restarts == n * (steps // horizon) and (shaped > 0 or not expect_shaped)
     return sparse, shaped
@@ -429,8 +396,8 @@ def test_mover_interact_event_log_against_oracle(layouts, gpu):
     env = VecOvercookedEnv(table, n, horizon=horizon, device=gpu, auto_reset=True, seed=seed, env_offset=off, layout_id=lid,
                            track_events=True, random_start_pos=True, rnd_obj_prob_thresh=0.5)
     st = env.get_packed_state().copy()
-    counts = np.zeros((n, 25, 2), np.int64)
-    done_counts = np.zeros((n, 25, 2), np.int64)
+    events = EventCounts(n)
+    counts, done_counts = events.running, events.published
     steps = 0
     for T_, tiled in ((64, False), (56, True)):
         rew = torch.zeros((T_, n, 4), dtype=torch.float32, device=gpu)
@@ -444,20 +411,14 @@ def test_mover_interact_event_log_against_oracle(layouts, gpu):
                                     start=O.start_spec(seed, off, 1 + steps, True, 0.5))
             steps += 1
             assert np.array_equal(fl_np[k], f_o) and np.array_equal(rew_np[k], r_o), steps
-            bits = ((orc.last_events[:, None] >> np.arange(50, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.int64)
-            counts += bits.reshape(n, 25, 2)
-            fin = (f_o & 1) != 0
-            done_counts[fin] = counts[fin]
-            counts[(f_o & 4) != 0] = 0
+            events.update(orc.last_events, finished=(f_o & 1) != 0, cleared=(f_o & 4) != 0)  # (cleared at the restart)
         assert np.array_equal(env.get_packed_state(), st)
-        got = env.event_counts.cpu().numpy().astype(np.int64)
-        got2 = np.stack([got & 0xFFFF, (got >> 16) & 0xFFFF], -1)
+        got2 = packed_counters(env.event_counts)
         bad = np.argwhere(got2 != counts)
         assert len(bad) == 0, "running counters after %d steps: %d differ, first (env, event, player) %s: %d vs %d; events that differ %s, layouts %s" % (
             steps, len(bad), bad[0].tolist(), got2[tuple(bad[0])], counts[tuple(bad[0])], sorted(set(bad[:, 1].tolist())),
             sorted(set((lid[bad[:, 0]] if lid is not None else np.zeros(1, int)).tolist())))
-        gd = env.event_counts_done.cpu().numpy().astype(np.int64)
-        assert np.array_equal(np.stack([gd & 0xFFFF, (gd >> 16) & 0xFFFF], -1), done_counts), "published counters after %d steps" % steps
+        assert np.array_equal(packed_counters(env.event_counts_done), done_counts), "published counters after %d steps" % steps
     assert done_counts.sum() > 0 and done_counts[:, 1].sum() + done_counts[:, 6].sum() > 0  # useful pick-ups were logged
 
 

@@ -13,15 +13,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test run without a GPU")
-    from overcooked_ai_amd import _lib
-
-    _lib.load()
-    return torch.device("cuda:0")
+from gpu_support import gpu  # noqa: E402, F401
 
 
 class Mailbox:

@@ -17,42 +17,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from case_support import compare  # noqa: E402
+from gpu_support import gpu, guarded, guards_untouched  # noqa: E402, F401
+
 OBS_CHUNK_BYTES = 70 << 20  # the oracle's int32 image of one comparison of the observation: at most ~70 MB
-GUARD = 3                   # guard rows (envs) behind every output array
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test run without a GPU")
-    from overcooked_ai_amd import _lib
-
-    _lib.load()  # fail loudly if the HIP extension is missing
-    return torch.device("cuda:0")
-
-
-def _first_difference(case, k, field, got, want, layout_id, env_axis=0, e0=0):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (case.id, k, field, got.shape, want.shape)
-    bad = np.nonzero(np.moveaxis(got != want, env_axis, 0).reshape(got.shape[env_axis], -1).any(axis=1))[0]
-    e = int(bad[0])
-    lay = 0 if layout_id is None else int(layout_id[e0 + e])
-    g, w = np.take(got, e, axis=env_axis).ravel(), np.take(want, e, axis=env_axis).ravel()
-    at = np.nonzero(g != w)[0]
-    return "%s: step %d, env %d (layout %d), %s: %d values differ, the first at %d: got %s, reference %s; %d envs differ" % (
-        case.id, k, e0 + e, lay, field, len(at), int(at[0]), g[at[:8]], w[at[:8]], len(bad))
-
-
-def _compare(case, k, field, got, want, layout_id, env_axis=0, e0=0):
-    """np.array_equal; a failure names the first differing (step, env, layout, field)."""
-    if not np.array_equal(np.asarray(got), np.asarray(want)):
-        pytest.fail(_first_difference(case, k, field, got, want, layout_id, env_axis, e0))
-
-
-def _guarded(rows, row_shape, dtype, fill, gpu):
-    """(the first `rows` rows of a new array of rows + GUARD, all of it filled with `fill`; the guard rows behind them)"""
-    whole = torch.full((rows + GUARD,) + tuple(row_shape), fill, dtype=dtype, device=gpu)
-    return whole[:rows], whole[rows:]
 
 
 def _compare_obs(case, k, obs, ref):
@@ -62,7 +30,7 @@ def _compare_obs(case, k, obs, ref):
     for a in range(0, case.n_envs, chunk):
         b = min(case.n_envs, a + chunk)
         want = ref.obs(a, b)
-        _compare(case, k, "observation", obs[a:b].cpu().numpy(), want.astype(np.float32) if case.dtype == "f32" else want.astype(np.uint8),
+        compare(case, k, "observation", obs[a:b].cpu().numpy(), want.astype(np.float32) if case.dtype == "f32" else want.astype(np.uint8),
                  ref.layout_id, e0=a)
         assert int(want.max()) <= 255
 
@@ -91,17 +59,17 @@ def test_every_observation_instance_against_the_oracle(case, gpu):
         assert plan.endswith(" B (queried)"), plan
 
     if case.call == "encode":
-        out, guard = _guarded(n, (2, W, H, 26), tdt, fill, gpu)
+        out, guard = guarded(n, (2, W, H, 26), tdt, fill, gpu)
         assert env.encode_lossless(tdt, out=out) is out
         _compare_obs(case, 0, out, ref)
-        assert bool((guard == fill).all()), "%s: guard rows behind the observation written" % case.id
-        _compare(case, 0, "state", env.get_packed_state(), ref.state, lid, env_axis=1)
+        guards_untouched(case, "observation", guard, fill)
+        compare(case, 0, "state", env.get_packed_state(), ref.state, lid, env_axis=1)
         return
 
     rows = 1 if case.call in ("rollout_single_buffer", "step_encode") else K
-    obs, g_obs = _guarded(rows * n, (2, W, H, 26), tdt, fill, gpu)
-    rew, g_rew = _guarded(K * n, (4,), torch.float32, -7.0, gpu)
-    fl, g_fl = _guarded(K * n, (), torch.uint8, 0xEE, gpu)
+    obs, g_obs = guarded(rows * n, (2, W, H, 26), tdt, fill, gpu)
+    rew, g_rew = guarded(K * n, (4,), torch.float32, -7.0, gpu)
+    fl, g_fl = guarded(K * n, (), torch.uint8, 0xEE, gpu)
     rew, fl = rew.view(K, n, 4), fl.view(K, n)
     d_acts = None if acts is None else torch.from_numpy(np.array(acts)).to(gpu)
     if case.call == "step_encode":
@@ -110,25 +78,25 @@ def test_every_observation_instance_against_the_oracle(case, gpu):
             r, f, o = env.step_encode(d_acts[k], tdt, out=obs)
             assert o is obs
             rew_o, fl_o = ref.step(k)
-            _compare(case, k, "rewards", r.cpu().numpy(), rew_o, lid)
-            _compare(case, k, "flags", f.cpu().numpy(), fl_o, lid)
+            compare(case, k, "rewards", r.cpu().numpy(), rew_o, lid)
+            compare(case, k, "flags", f.cpu().numpy(), fl_o, lid)
             _compare_obs(case, k, obs, ref)
-            _compare(case, k, "state", env.get_packed_state(), ref.state, lid, env_axis=1)
-            _compare(case, k, "episode returns", env.ep_returns.cpu().numpy(), ref.ep_returns, lid)
+            compare(case, k, "state", env.get_packed_state(), ref.state, lid, env_axis=1)
+            compare(case, k, "episode returns", env.ep_returns.cpu().numpy(), ref.ep_returns, lid)
     else:
         obs_arg = obs if rows == 1 else obs.view(K, n, 2, W, H, 26)
         env.rollout_encode(K, obs_arg, rew, fl, actions=d_acts, dtype=tdt)
         rew_h, fl_h = rew.cpu().numpy(), fl.cpu().numpy()
         for k in range(K):
             rew_o, fl_o = ref.step(k)
-            _compare(case, k, "rewards", rew_h[k], rew_o, lid)
-            _compare(case, k, "flags", fl_h[k], fl_o, lid)
+            compare(case, k, "rewards", rew_h[k], rew_o, lid)
+            compare(case, k, "flags", fl_h[k], fl_o, lid)
             if rows == K:
                 _compare_obs(case, k, obs_arg[k], ref)
         if rows == 1:  # one buffer, overwritten every step: the observation of the last step
             _compare_obs(case, K - 1, obs, ref)
-        _compare(case, K - 1, "state", env.get_packed_state(), ref.state, lid, env_axis=1)
-        _compare(case, K - 1, "episode returns", env.ep_returns.cpu().numpy(), ref.ep_returns, lid)
+        compare(case, K - 1, "state", env.get_packed_state(), ref.state, lid, env_axis=1)
+        compare(case, K - 1, "episode returns", env.ep_returns.cpu().numpy(), ref.ep_returns, lid)
     assert env.t_global == case.t0 + (K if case.call in ("rollout", "rollout_single_buffer") else 0), (case.id, env.t_global)
     for what, g, v in (("observation", g_obs, fill), ("rewards", g_rew, -7.0), ("flags", g_fl, 0xEE)):
-        assert bool((g == v).all()), "%s: guard rows behind the %s written" % (case.id, what)
+        guards_untouched(case, what, g, v)

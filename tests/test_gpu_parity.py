@@ -13,36 +13,15 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from case_support import EventCounts  # noqa: E402
+from gpu_support import gpu, make_env, oracle_for, packed_counters  # noqa: E402, F401
+
 TRANSITION_CONFIGS = [
     "cramped_room", "asymmetric_advantages", "coordination_ring", "forced_coordination", "counter_circuit",
     "mdp_test", "cramped_room_old_dynamics", "bonus_order_test", "cramped_room_tomato", "cramped_room_single",
     "cramped_room_padded_9x5",
 ]
 ROLLOUT_CONFIGS = ["cramped_room", "asymmetric_advantages", "counter_circuit", "mdp_test", "cramped_room_old_dynamics"]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test run without a GPU")
-    from overcooked_ai_amd import _lib
-
-    _lib.load()  # fail loudly if the HIP extension is missing
-    return torch.device("cuda:0")
-
-
-def make_env(layouts, n, gpu, **kw):
-    from overcooked_ai_amd.vec_env import VecOvercookedEnv
-
-    return VecOvercookedEnv(layouts, n, device=gpu, **kw)
-
-
-def oracle_for(specs):
-    from oracle import oracle as O
-
-    if not isinstance(specs, (list, tuple)):
-        specs = [specs]
-    return O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in specs])
 
 
 def u8(t):
@@ -1017,21 +996,15 @@ def test_event_masks_and_episode_counters_on_the_fast_paths(layouts, gpu):
     env = make_env(table, n, gpu, horizon=horizon, auto_reset=True, seed=seed, layout_id=lid, track_events=True,
                    random_start_pos=True, rnd_obj_prob_thresh=0.5)  # random starts: events from the first steps on
     st = env.get_packed_state()
-    counts = np.zeros((n, 25, 2), np.int64)
-    done_counts = np.zeros((n, 25, 2), np.int64)
+    events = EventCounts(n)
+    counts, done_counts = events.running, events.published
 
     def account(ev_o, flags_o):
-        bits = ((ev_o[:, None] >> np.arange(50, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.int64).reshape(n, 25, 2)
-        counts[:] += bits
-        fin = (flags_o & 1) != 0
-        done_counts[fin] = counts[fin]
-        counts[(flags_o & 4) != 0] = 0
+        events.update(ev_o, finished=(flags_o & 1) != 0, cleared=(flags_o & 4) != 0)  # (cleared at the restart)
 
     def check_counters():
-        got = env.event_counts.cpu().numpy().astype(np.int64)
-        assert np.array_equal(np.stack([got & 0xFFFF, (got >> 16) & 0xFFFF], -1), counts)
-        gd = env.event_counts_done.cpu().numpy().astype(np.int64)
-        assert np.array_equal(np.stack([gd & 0xFFFF, (gd >> 16) & 0xFFFF], -1), done_counts)
+        assert np.array_equal(packed_counters(env.event_counts), counts)
+        assert np.array_equal(packed_counters(env.event_counts_done), done_counts)
 
     steps = 0
     T = 55  # crosses the horizon once

@@ -2,8 +2,6 @@
 are the Philox stream of oc_rollout_random, every recorded state is the state its step acts on (checked step by step against
 the C oracle), recording changes none of the launch's other results, recorded states feed the observation kernels, and the
 host converter reproduces the drop-in OvercookedEnv.get_rollouts."""
-import os
-
 import numpy as np
 import pytest
 
@@ -13,17 +11,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from case_support import new_oracle as _oracle  # noqa: E402
+from gpu_support import gpu  # noqa: E402, F401
+
 SEVEN = {"grid": "XPPPPPX\nO 1 2 O\nX     X\nXDPSPTX", "onion_time": 3, "tomato_time": 5, "onion_value": 7, "tomato_value": 4}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test run without a GPU")
-    from overcooked_ai_amd import _lib
-
-    _lib.load()
-    return torch.device("cuda:0")
 
 
 def _table(name):
@@ -36,13 +27,6 @@ def _table(name):
     if name.endswith("_old"):  # old dynamics: a full pot starts cooking by itself
         return LayoutTable([spec_from_name(name[:-4], old_dynamics=True)])
     return LayoutTable([spec_from_name(name)])
-
-
-def _oracle(specs):
-    from oracle import oracle as O
-
-    O.set_threads(min(16, len(os.sched_getaffinity(0))))
-    return O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in specs])
 
 
 def _env(gpu, name, n, horizon, seed=3, env_offset=0, t0=0, **kw):

@@ -3,8 +3,6 @@ rollout_random(actions_out=, states_out=, layouts_out=, events_out=) with track_
 recorded step against the C oracle (state, layout id, rewards, flags, event mask), recording against the same launch without
 it, the converter's ep_game_stats against the drop-in get_rollouts on each episode's recorded layout, two shards against one
 batch, and a full-size launch."""
-import os
-
 import numpy as np
 import pytest
 
@@ -14,17 +12,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from case_support import new_oracle as _oracle  # noqa: E402
+from gpu_support import gpu  # noqa: E402, F401
+
 SEVEN = {"grid": "XPPPPPX\nO 1 2 O\nX     X\nXDPSPTX", "onion_time": 3, "tomato_time": 5, "onion_value": 7, "tomato_value": 4}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test run without a GPU")
-    from overcooked_ai_amd import _lib
-
-    _lib.load()
-    return torch.device("cuda:0")
 
 
 def _table(name):
@@ -40,13 +31,6 @@ def _table(name):
     if name.endswith("_old"):  # old dynamics: a full pot starts cooking by itself
         return LayoutTable([spec_from_name(name[:-4], old_dynamics=True)])
     return LayoutTable([spec_from_name(name)])
-
-
-def _oracle(specs):
-    from oracle import oracle as O
-
-    O.set_threads(min(16, len(os.sched_getaffinity(0))))
-    return O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in specs])
 
 
 def _env(gpu, name, n, horizon, seed=3, env_offset=0, t0=0, regen=False, **kw):

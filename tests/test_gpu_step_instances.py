@@ -16,47 +16,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-GUARD = 3  # guard rows (envs) behind every output array
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test run without a GPU")
-    from overcooked_ai_amd import _lib
-
-    _lib.load()  # fail loudly if the HIP extension is missing
-    return torch.device("cuda:0")
-
-
-def _first_difference(case, k, field, got, want, layout_id, env_axis=0):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (case.id, k, field, got.shape, want.shape)
-    bad = np.nonzero(np.moveaxis(got != want, env_axis, 0).reshape(got.shape[env_axis], -1).any(axis=1))[0]
-    e = int(bad[0])
-    lay = 0 if layout_id is None else int(layout_id[e])
-    g, w = np.take(got, e, axis=env_axis).ravel(), np.take(want, e, axis=env_axis).ravel()
-    at = np.nonzero(g != w)[0]
-    return "%s: step %d, env %d (layout %d), %s: %d values differ, the first at %d: got %s, reference %s; %d envs differ" % (
-        case.id, k, e, lay, field, len(at), int(at[0]), g[at[:8]], w[at[:8]], len(bad))
-
-
-def _compare(case, k, field, got, want, layout_id, env_axis=0):
-    """np.array_equal; a failure names the first differing (step, env, layout, field)."""
-    if not np.array_equal(np.asarray(got), np.asarray(want)):
-        pytest.fail(_first_difference(case, k, field, got, want, layout_id, env_axis))
-
-
-def _guarded(rows, row_shape, dtype, fill, gpu):
-    """(the first `rows` rows of a new array of rows + GUARD, all of it filled with `fill`; the guard rows behind them)"""
-    whole = torch.full((rows + GUARD,) + tuple(row_shape), fill, dtype=dtype, device=gpu)
-    return whole[:rows], whole[rows:]
-
-
-def _packed_counters(t):
-    """[n_envs, 25] int32, player 0 in the low half-word -> [n_envs, 25, 2]"""
-    c = t.cpu().numpy().astype(np.int64)
-    return np.stack([c & 0xFFFF, (c >> 16) & 0xFFFF], -1)
+from case_support import compare  # noqa: E402
+from gpu_support import gpu, guarded, guards_untouched, packed_counters  # noqa: E402, F401
 
 
 def _new_env(case, gpu):
@@ -72,15 +33,15 @@ def _compare_env(case, k, env, ref, lid0):
     """What an env holds after step k against the oracle: state, episode returns, counters, layout ids."""
     lid = ref.layout_id
     if lid is not None:
-        _compare(case, k, "layout ids", env.layout_ids(), lid, lid0)
-    _compare(case, k, "state", env.get_packed_state(), ref.state, lid, env_axis=1)
+        compare(case, k, "layout ids", env.layout_ids(), lid, lid0)
+    compare(case, k, "state", env.get_packed_state(), ref.state, lid, env_axis=1)
     if case.returns:
-        _compare(case, k, "episode returns", env.ep_returns.cpu().numpy(), ref.ep_returns, lid)
+        compare(case, k, "episode returns", env.ep_returns.cpu().numpy(), ref.ep_returns, lid)
     else:
         assert env.ep_returns is None
     if SC.with_counts(case):
-        _compare(case, k, "running event counters", _packed_counters(env.event_counts), ref.counts, lid)
-        _compare(case, k, "published event counters", _packed_counters(env.event_counts_done), ref.counts_done, lid)
+        compare(case, k, "running event counters", packed_counters(env.event_counts), ref.counts, lid)
+        compare(case, k, "published event counters", packed_counters(env.event_counts_done), ref.counts_done, lid)
 
 
 @pytest.mark.parametrize("case", SC.CASES, ids=lambda c: c.id)
@@ -100,10 +61,10 @@ def test_every_step_instance_against_the_oracle(case, gpu):
     guards = []
     if case.entry in ("step", "step_out_of_place"):
         oop = case.entry == "step_out_of_place"
-        ev, g_ev = _guarded(n, (), torch.int64, -1, gpu) if masks_on else (None, None)
+        ev, g_ev = guarded(n, (), torch.int64, -1, gpu) if masks_on else (None, None)
         out = None
         if oop:  # [n_planes][n][16], guard rows behind the last plane
-            flat, g_out = _guarded(table.n_planes * n, (16,), torch.uint8, 0xEE, gpu)
+            flat, g_out = guarded(table.n_planes * n, (16,), torch.uint8, 0xEE, gpu)
             out = flat.view(table.n_planes, n, 16)
             guards.append(("state_out", g_out, 0xEE))
         for k in range(K):
@@ -117,21 +78,21 @@ def test_every_step_instance_against_the_oracle(case, gpu):
                 before = env.state.clone()
             r, f = env.step(acts[k], state_out=out, events_out=ev)
             rew_o, fl_o, masks_o = ref.step(k)
-            _compare(case, k, "flags", f.cpu().numpy(), fl_o, lid0)
-            _compare(case, k, "rewards", r.cpu().numpy(), rew_o, lid0)
+            compare(case, k, "flags", f.cpu().numpy(), fl_o, lid0)
+            compare(case, k, "rewards", r.cpu().numpy(), rew_o, lid0)
             if ev is not None:
-                _compare(case, k, "event masks", ev.cpu().numpy().view(np.uint64), masks_o, lid0)
+                compare(case, k, "event masks", ev.cpu().numpy().view(np.uint64), masks_o, lid0)
             if oop:
                 assert torch.equal(env.state, before), "%s: step %d changed its input state" % (case.id, k)
-                _compare(case, k, "state_out", out.cpu().numpy(), ref.state, lid0, env_axis=1)
+                compare(case, k, "state_out", out.cpu().numpy(), ref.state, lid0, env_axis=1)
                 env.state.copy_(out)
             _compare_env(case, k, env, ref, lid0)
         if ev is not None:
             guards.append(("event masks", g_ev, -1))
     elif case.entry == "step_many":
-        rew, g_rew = _guarded(K * n, (4,), torch.float32, -7.0, gpu)
-        fl, g_fl = _guarded(K * n, (), torch.uint8, 0xEE, gpu)
-        ev, g_ev = _guarded(K * n, (), torch.int64, -1, gpu) if masks_on else (None, None)
+        rew, g_rew = guarded(K * n, (4,), torch.float32, -7.0, gpu)
+        fl, g_fl = guarded(K * n, (), torch.uint8, 0xEE, gpu)
+        ev, g_ev = guarded(K * n, (), torch.int64, -1, gpu) if masks_on else (None, None)
         lid0 = None if ref.layout_id is None else ref.layout_id.copy()
         env.step_many(acts, rew.view(K, n, 4), fl.view(K, n), events_out=None if ev is None else ev.view(K, n))
         rew_h, fl_h = rew.view(K, n, 4).cpu().numpy(), fl.view(K, n).cpu().numpy()
@@ -142,29 +103,29 @@ def test_every_step_instance_against_the_oracle(case, gpu):
         for k in range(K):
             lid_k = None if ref.layout_id is None else ref.layout_id.copy()
             rew_o, fl_o, masks_o = ref.step(k)
-            _compare(case, k, "flags", fl_h[k], fl_o, lid_k)
-            _compare(case, k, "rewards", rew_h[k], rew_o, lid_k)
+            compare(case, k, "flags", fl_h[k], fl_o, lid_k)
+            compare(case, k, "rewards", rew_h[k], rew_o, lid_k)
             if ev_h is not None:
-                _compare(case, k, "event masks", ev_h[k], masks_o, lid_k)
+                compare(case, k, "event masks", ev_h[k], masks_o, lid_k)
             r2, f2 = env2.step(acts[k], events_out=ev2)
-            _compare(case, k, "flags of single steps", f2.cpu().numpy(), fl_o, lid_k)
-            _compare(case, k, "rewards of single steps", r2.cpu().numpy(), rew_o, lid_k)
+            compare(case, k, "flags of single steps", f2.cpu().numpy(), fl_o, lid_k)
+            compare(case, k, "rewards of single steps", r2.cpu().numpy(), rew_o, lid_k)
             if ev2 is not None:
-                _compare(case, k, "event masks of single steps", ev2.cpu().numpy().view(np.uint64), masks_o, lid_k)
+                compare(case, k, "event masks of single steps", ev2.cpu().numpy().view(np.uint64), masks_o, lid_k)
             _compare_env(case, k, env2, ref, lid_k)
         _compare_env(case, K - 1, env, ref, lid0)
         guards += [("rewards", g_rew, -7.0), ("flags", g_fl, 0xEE)] + ([("event masks", g_ev, -1)] if ev is not None else [])
     else:  # the resident step: SERVER_SPLIT steps in one play, a sync (the kernel leaves), the others as single steps (a resume)
         A = SC.SERVER_SPLIT
-        rew, g_rew = _guarded(A * n, (4,), torch.float32, -7.0, gpu)
-        fl, g_fl = _guarded(A * n, (), torch.uint8, 0xEE, gpu)
+        rew, g_rew = guarded(A * n, (4,), torch.float32, -7.0, gpu)
+        fl, g_fl = guarded(A * n, (), torch.uint8, 0xEE, gpu)
         with env.step_server() as sv:
             sv.play(acts[:A].contiguous(), rew.view(A, n, 4), fl.view(A, n))
             rew_h, fl_h = rew.view(A, n, 4).cpu().numpy(), fl.view(A, n).cpu().numpy()
             for k in range(A):
                 rew_o, fl_o, _ = ref.step(k)
-                _compare(case, k, "flags", fl_h[k], fl_o, ref.layout_id)
-                _compare(case, k, "rewards", rew_h[k], rew_o, ref.layout_id)
+                compare(case, k, "flags", fl_h[k], fl_o, ref.layout_id)
+                compare(case, k, "rewards", rew_h[k], rew_o, ref.layout_id)
             sv.sync()
             assert sv.steps == A, (case.id, sv.steps)
             _compare_env(case, A - 1, env, ref, ref.layout_id)
@@ -173,12 +134,12 @@ def test_every_step_instance_against_the_oracle(case, gpu):
                 env.flags.fill_(0xEE)
                 r, f = sv.step(acts[k])
                 rew_o, fl_o, _ = ref.step(k)
-                _compare(case, k, "flags", f.cpu().numpy(), fl_o, ref.layout_id)
-                _compare(case, k, "rewards", r.cpu().numpy(), rew_o, ref.layout_id)
+                compare(case, k, "flags", f.cpu().numpy(), fl_o, ref.layout_id)
+                compare(case, k, "rewards", r.cpu().numpy(), rew_o, ref.layout_id)
             sv.sync()
             assert sv.steps == K, (case.id, sv.steps)
             _compare_env(case, K - 1, env, ref, ref.layout_id)
         guards += [("rewards", g_rew, -7.0), ("flags", g_fl, 0xEE)]
     assert env.steps_done == K
     for what, g, v in guards:
-        assert bool((g == v).all()), "%s: guard rows behind the %s written" % (case.id, what)
+        guards_untouched(case, what, g, v)

@@ -4,13 +4,14 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import CANONICAL_5, make_env, oracle_for
+from gpu_support import make_env, oracle_for
+from helpers import CANONICAL_5
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def gpu():
+def gpu():  # (not gpu_support's: this module has always skipped, not failed, where there is no GPU)
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     return torch.device("cuda:0")

@@ -7,7 +7,6 @@ and the observation are integer work; the rewards are small integers in f32; phi
 operations on both sides (`#pragma clang fp contract(off)` in every training kernel, -ffp-contract=off for the oracle; the suite
 holds oc_potential to bit identity already), and shaped = (sparse0 + sparse1) + factor * dense is one sum, one product and one
 sum of float64 on both sides.  So every array is compared with np.array_equal, the float64 ones as bit patterns."""
-import numpy as np
 import pytest
 
 import train_cases as TC
@@ -16,42 +15,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from case_support import compare  # noqa: E402
+from gpu_support import gpu, packed_counters  # noqa: E402, F401
+
 OBS_CHUNK = 16384  # envs per comparison of the observation: the oracle's int32 image of 16 384 cramped_room envs is 68 MB
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test run without a GPU")
-    from overcooked_ai_amd import _lib
-
-    _lib.load()  # fail loudly if the HIP extension is missing
-    return torch.device("cuda:0")
-
-
-def _bits(a):
-    """float64 -> its bit patterns (so that -0.0 != 0.0 and a nan equals itself)"""
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _first_difference(case, t, field, got, want, layout_id):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (case.id, t, field, got.shape, want.shape)
-    env_axis = 1 if field == "state" else 0  # (the packed state is [plane][env][16])
-    differ = _bits(got) != _bits(want) if got.dtype == np.float64 else got != want
-    bad = np.nonzero(np.moveaxis(differ, env_axis, 0).reshape(got.shape[env_axis], -1).any(axis=1))[0]
-    e = int(bad[0])
-    lay = 0 if layout_id is None else int(layout_id[e])
-    return "%s: step %d, env %d (layout %d), %s: got %s, reference %s; %d envs differ" % (
-        case.id, t, e, lay, field, np.take(got, e, axis=env_axis).ravel()[:16], np.take(want, e, axis=env_axis).ravel()[:16], len(bad))
-
-
-def _compare(case, t, field, got, want, layout_id):
-    """np.array_equal, float64 arrays as bit patterns; a failure names the first differing (step, env, layout, field)."""
-    got, want = np.asarray(got), np.asarray(want)
-    same = np.array_equal(_bits(got), _bits(want)) if got.dtype == np.float64 else np.array_equal(got, want)
-    if not same:
-        pytest.fail(_first_difference(case, t, field, got, want, layout_id))
 
 
 @pytest.mark.parametrize("case", TC.CASES, ids=lambda c: c.id)
@@ -67,9 +34,9 @@ def test_every_training_step_instance_against_the_reference(case, gpu):
     ref = TC.oracle_of(case)
     v = env.venv
     lid = lambda: None if ref.layout_id is None else ref.layout_id  # noqa: E731
-    _compare(case, -1, "state", v.get_packed_state(), ref.state, lid())
+    compare(case, -1, "state", v.get_packed_state(), ref.state, lid(), env_axis=1)  # (the packed state is [plane][env][16])
     if case.use_phi:
-        _compare(case, -1, "phi_cur", env.phi_cur.cpu().numpy(), ref.phi_cur, lid())
+        compare(case, -1, "phi_cur", env.phi_cur.cpu().numpy(), ref.phi_cur, lid())
     big = case.n_envs >= 131072
     for t in range(case.steps):
         if case.factor == "anneal" and t == TC.anneal_at(case):
@@ -86,17 +53,15 @@ def test_every_training_step_instance_against_the_reference(case, gpu):
         if ref.layout_id is not None:
             fields.append(("layout_id", v.layout_ids(), ref.layout_id))
         for field, got, want in fields:
-            _compare(case, t, field, got.cpu().numpy() if isinstance(got, torch.Tensor) else got, want, lid())
+            compare(case, t, field, got.cpu().numpy() if isinstance(got, torch.Tensor) else got, want, lid(), env_axis=1 if field == "state" else 0)
         if case.events:
             for field, got, want in (("event counters, running", v.event_counts, ref.counts), ("event counters, published", v.event_counts_done, ref.counts_done)):
-                g = got.cpu().numpy().astype(np.int64)
-                _compare(case, t, field, np.stack([g & 0xFFFF, (g >> 16) & 0xFFFF], -1), want, lid())
+                compare(case, t, field, packed_counters(got), want, lid())
         # the observation of the states the next step starts from, in env chunks (the batch of >= 131 072 envs: the first, the
         # last and every restart-bearing step)
         if case.obs is not None and (not big or t in (0, case.steps - 1) or ref.done.any()):
             assert obs.dtype == dt and obs.shape == (case.n_envs, 2, table.width, table.height, 26)
             for a0 in range(0, case.n_envs, OBS_CHUNK):
                 a1 = min(case.n_envs, a0 + OBS_CHUNK)
-                _compare(case, t, "observation of envs %d.." % a0, obs[a0:a1].cpu().numpy(), ref.obs(a0, a1),
-                         None if ref.layout_id is None else ref.layout_id[a0:a1])
+                compare(case, t, "observation", obs[a0:a1].cpu().numpy(), ref.obs(a0, a1), lid(), e0=a0)
     assert (ref.flags & 2).any()  # (the last step, like every step, carries illegal actions)

@@ -13,19 +13,13 @@ import numpy as np
 import pytest
 
 import derived_cases as DC
-from test_host_observation_instances import _function
-from test_host_observation_plan import batch
+from case_support import CSRC, check_census, function_body as _function, ledger, print_ledger, synthetic_batch as batch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "overcooked_ai_amd", "csrc")
 NEW_TABLES = ("three_pots", "eight_pots_serve_ring", "one_player_two_pots", "mdp_test_tomato")
 
 
 def _ledger():
-    led = {}
-    for c in DC.CASES:
-        led.setdefault(c.expect, []).append(c.id)
-    return led
+    return ledger(DC.CASES, lambda c: c.expect)
 
 
 def _instantiated():
@@ -48,21 +42,13 @@ def _instantiated():
 
 
 def test_every_derived_instance_of_the_sources_has_a_case_or_a_named_exclusion():
-    found = _instantiated()
-    assert len(found) == len(set(found)) == 4, found
-    assert sorted(found) == sorted(DC.INSTANCES)
-    reached = set(_ledger())
-    assert not reached & set(DC.UNREACHABLE)
-    assert reached | set(DC.UNREACHABLE) == set(found), sorted(set(found) - reached - set(DC.UNREACHABLE))
-    assert all(DC.UNREACHABLE.values())
+    check_census(_instantiated(), DC.INSTANCES, DC.UNREACHABLE, set(_ledger()), 4, "potential and featurize kernels")
 
 
 def test_ledger():
     """instance -> case ids (shown by `pytest -s -k test_ledger`)."""
     led = _ledger()
-    print()
-    for text in DC.INSTANCES:
-        print("%s\n%30s%s" % (text, "<- ", ", ".join(led[text]) if text in led else "UNREACHABLE: " + DC.UNREACHABLE[text]))
+    print_ledger(DC.INSTANCES, led, DC.UNREACHABLE)
     assert len(led) + len(DC.UNREACHABLE) == len(DC.INSTANCES) == 4
 
 

@@ -11,10 +11,10 @@ import numpy as np
 import pytest
 
 import obs_cases as OC
-from test_host_observation_plan import F32, ONE_KERNEL, U8, batch, plan
+from case_support import CSRC, check_census, function_body as _function, ledger, observation_plan as plan, pot_kinds, print_ledger, synthetic_batch as batch
+from overcooked_ai_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "overcooked_ai_amd", "csrc")
+U8, F32, ONE_KERNEL = _lib.OBS_U8, _lib.OBS_F32, _lib.OPT_ONE_KERNEL
 ROLLOUTS = [c for c in OC.CASES if c.call != "encode"]
 SINGLE = [c for c in ROLLOUTS if c.expect.startswith("k_rollout_encode<")]
 ENCODES = [c for c in OC.CASES if c.call == "encode"]
@@ -22,17 +22,7 @@ ENCODES = [c for c in OC.CASES if c.call == "encode"]
 
 def _ledger():
     """instance (oc_observation_plan's words) -> ids of the cases that are there for it"""
-    led = {}
-    for c in OC.CASES:
-        led.setdefault(OC.instance_of(c), []).append(c.id)
-    return led
-
-
-def _function(src, name):
-    """The text of the function `name` of csrc/oc_amd.hip: from its head to the first closing brace in column 0."""
-    m = re.search(r"^[A-Za-z][^\n;]*\b%s\([^;{]*\{\n.*?^\}" % name, src, re.S | re.M)
-    assert m, name
-    return m.group(0)
+    return ledger(OC.CASES, OC.instance_of)
 
 
 def _instantiated():
@@ -66,14 +56,9 @@ def test_the_planner_gives_the_case_the_instance_it_names(case):
 
 def test_every_observation_instance_of_the_sources_has_a_case_or_a_named_exclusion():
     found, asked = _instantiated()
-    assert len(found) == len(set(found)) == 13, "csrc/oc_amd.hip instantiates %d observation kernels, not 13: %s" % (len(found), sorted(found))
-    assert sorted(found) == sorted(OC.INSTANCES)
-    assert set(asked) <= set(found) and len(asked) == 4  # (the budget is asked of one instance per FAST and T)
     reached = set(_ledger())
-    assert not reached & set(OC.UNREACHABLE), "reached after all: %s" % sorted(reached & set(OC.UNREACHABLE))
-    missing = sorted(set(found) - reached - set(OC.UNREACHABLE))
-    assert not missing, "no case reaches %s" % missing
-    assert reached | set(OC.UNREACHABLE) == set(found), "not an instance: %s" % sorted((reached | set(OC.UNREACHABLE)) - set(found))
+    check_census(found, OC.INSTANCES, OC.UNREACHABLE, reached, 13, "observation kernels")
+    assert set(asked) <= set(found) and len(asked) == 4  # (the budget is asked of one instance per FAST and T)
     assert len(reached) == 9 and len(OC.UNREACHABLE) == 4
     # the paths that are no instance: oc_step_encode on the single kernel, and both step-by-step entry points
     assert {c.call for c in OC.CASES} == set(OC.CALLS)
@@ -83,9 +68,7 @@ def test_every_observation_instance_of_the_sources_has_a_case_or_a_named_exclusi
 def test_ledger():
     """instance -> case ids, one line per instance (shown by `pytest -s -k test_ledger`)."""
     led = _ledger()
-    print()
-    for text in OC.INSTANCES:
-        print("%s\n%30s%s" % (text, "<- ", ", ".join(led[text]) if text in led else "UNREACHABLE: " + OC.UNREACHABLE[text]))
+    print_ledger(OC.INSTANCES, led, OC.UNREACHABLE)
     assert len(led) + len(OC.UNREACHABLE) == len(OC.INSTANCES) == 13
 
 
@@ -214,25 +197,7 @@ def _objects(state):
 
 
 def _pot_kinds(case, state):
-    """(idle, cooking, ready) pots and held soups somewhere in the batch"""
-    table, lid = OC.table_of(case.table), OC.layout_ids(case)
-    idle = cooking = ready = 0
-    for l, spec in enumerate(table.specs):
-        st = state if lid is None else state[:, lid == l]
-        for k, (x, y) in enumerate(spec.cells_of("P")):
-            cell = y * spec.width + x
-            code = st[1 + (cell >> 4), :, cell & 15].astype(np.int64)
-            tick = st[0, :, 8 + k].astype(np.int64) - 1
-            for o in np.unique(code[code != 0]):
-                cnt, bits = (int(o) >> 3) & 3, int(o) & 7
-                n_t = bin(bits).count("1")
-                ct = int(spec.recipe_time((cnt - n_t, n_t)))
-                sel = tick[code == o]
-                idle += int((sel == -1).sum())
-                cooking += int(((sel >= 0) & (sel < ct)).sum())
-                ready += int((sel >= ct).sum())
-    held = int(((state[0, :, 2] >= 0x80) | (state[0, :, 5] >= 0x80)).sum())
-    return idle, cooking, ready, held
+    return pot_kinds(OC.table_of(case.table), OC.layout_ids(case), state)
 
 
 @pytest.mark.parametrize("case", ROLLOUTS, ids=lambda c: c.id)

@@ -20,26 +20,11 @@ import ctypes
 
 import pytest
 
+from case_support import P, observation_plan as plan, synthetic_batch as batch
 from overcooked_ai_amd import _lib
 
-P = 4096  # a stand-in device pointer: a plan never follows one
-TWO = _lib.BATCH_TWO_PLAYERS
 ONE_KERNEL, AUTO_RESET = _lib.OPT_ONE_KERNEL, _lib.OPT_AUTO_RESET
 U8, F32 = _lib.OBS_U8, _lib.OBS_F32
-
-
-def batch(w, h, n_envs, n_layouts=1, max_pots=1, flags=TWO):
-    return _lib.OcBatch(d_layouts=P, d_layout_id=P if n_layouts > 1 else None, n_envs=n_envs, n_layouts=n_layouts, width=w, height=h,
-                        max_pots=max_pots, batch_flags=flags)
-
-
-def plan(b, dtype=U8, n_steps=0, options=AUTO_RESET, actions=0, outputs=1, start=None, horizon=400):
-    """(rc, text or the refusal's message)"""
-    L = _lib.load()
-    out = ctypes.create_string_buffer(320)
-    rc = L.oc_observation_plan(ctypes.byref(b) if b is not None else None, dtype, horizon, options, n_steps, actions, outputs,
-                               ctypes.byref(start) if start is not None else None, out, len(out))
-    return rc, (out.value.decode() if rc == 0 else L.oc_last_error().decode())
 
 
 ENCODE = [

@@ -9,9 +9,7 @@ import re
 import pytest
 
 import rollout_cases as RC
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "overcooked_ai_amd", "csrc")
+from case_support import CSRC, ledger
 
 # Instances no real table reaches, by name, each with the condition of choose_launch that excludes it (at most two)
 UNREACHABLE = {}
@@ -19,10 +17,7 @@ UNREACHABLE = {}
 
 def _ledger():
     """instance (oc_rollout_plan's words) -> ids of the cases that are there for it"""
-    led = {}
-    for c in RC.CASES:
-        led.setdefault(c.expect, []).append(c.id)
-    return led
+    return ledger(RC.CASES, lambda c: c.expect)
 
 
 @pytest.mark.parametrize("case", RC.CASES, ids=lambda c: c.id)

@@ -9,24 +9,17 @@ import itertools
 import os
 import re
 
-import numpy as np
 import pytest
 
 import step_cases as SC
-from test_host_observation_instances import _function
-from test_host_observation_plan import batch
+from case_support import CSRC, check_census, event_bits, function_body as _function, ledger, pot_kinds, print_ledger, synthetic_batch as batch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "overcooked_ai_amd", "csrc")
 AUTO_RESET = 1  # OC_OPT_AUTO_RESET
 
 
 def _ledger():
     """instance (oc_step_plan's words) -> ids of the cases that are there for it"""
-    led = {}
-    for c in SC.CASES:
-        led.setdefault(SC.instance_of(c), []).append(c.id)
-    return led
+    return ledger(SC.CASES, SC.instance_of)
 
 
 def _instantiated():
@@ -62,24 +55,14 @@ def test_the_planner_gives_the_case_the_instance_it_names(case):
 
 
 def test_every_step_instance_of_the_sources_has_a_case_or_a_named_exclusion():
-    found = _instantiated()
-    assert len(found) == len(set(found)) == 29, "csrc/oc_amd.hip instantiates %d caller-actions kernels, not 29: %s" % (len(found), sorted(found))
-    assert sorted(found) == sorted(SC.INSTANCES)
-    reached = set(_ledger())
-    assert not reached & set(SC.UNREACHABLE), "reached after all: %s" % sorted(reached & set(SC.UNREACHABLE))
-    missing = sorted(set(found) - reached - set(SC.UNREACHABLE))
-    assert not missing, "no case reaches %s" % missing
-    assert reached | set(SC.UNREACHABLE) == set(found), "not an instance: %s" % sorted((reached | set(SC.UNREACHABLE)) - set(found))
-    assert all(SC.UNREACHABLE.values())  # (each exclusion with its reason)
+    check_census(_instantiated(), SC.INSTANCES, SC.UNREACHABLE, set(_ledger()), 29, "caller-actions kernels")
     assert {c.entry for c in SC.CASES} == set(SC.ENTRIES)
 
 
 def test_ledger():
     """instance -> case ids, one line per instance (shown by `pytest -s -k test_ledger`)."""
     led = _ledger()
-    print()
-    for text in SC.INSTANCES:
-        print("%s\n%30s%s" % (text, "<- ", ", ".join(led[text]) if text in led else "UNREACHABLE: " + SC.UNREACHABLE[text]))
+    print_ledger(SC.INSTANCES, led, SC.UNREACHABLE)
     assert len(led) + len(SC.UNREACHABLE) == len(SC.INSTANCES) == 29
 
 
@@ -239,29 +222,12 @@ def test_the_planners_refusals_carry_the_entry_points_name():
 def _event_names(masks):
     from overcooked_ai_amd.mdp import EVENT_TYPES
 
-    seen = ((masks[:, None] >> np.arange(50, dtype=np.uint64)[None, :]) & np.uint64(1)).reshape(-1, 25, 2).any(axis=(0, 2))
+    seen = event_bits(masks).any(axis=(0, 2))
     return {EVENT_TYPES[i] for i in range(25) if seen[i]}
 
 
 def _pot_kinds(case, state):
-    """(idle, cooking, ready) pots and held soups somewhere in the batch"""
-    table, lid = SC.table_of(case.table), SC.layout_ids(case)
-    idle = cooking = ready = 0
-    for l, spec in enumerate(table.specs):
-        st = state if lid is None else state[:, lid == l]
-        for k, (x, y) in enumerate(spec.cells_of("P")):
-            cell = y * spec.width + x
-            code = st[1 + (cell >> 4), :, cell & 15].astype(np.int64)
-            tick = st[0, :, 8 + k].astype(np.int64) - 1
-            for o in np.unique(code[code != 0]):
-                n_t = bin(int(o) & 7).count("1")
-                ct = int(spec.recipe_time((((int(o) >> 3) & 3) - n_t, n_t)))
-                sel = tick[code == o]
-                idle += int((sel == -1).sum())
-                cooking += int(((sel >= 0) & (sel < ct)).sum())
-                ready += int((sel >= ct).sum())
-    held = int(((state[0, :, 2] >= 0x80) | (state[0, :, 5] >= 0x80)).sum())
-    return idle, cooking, ready, held
+    return pot_kinds(SC.table_of(case.table), SC.layout_ids(case), state)
 
 
 @pytest.mark.parametrize("case", SC.CASES, ids=lambda c: c.id)

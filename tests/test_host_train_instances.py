@@ -10,17 +10,12 @@ import numpy as np
 import pytest
 
 import train_cases as TC
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "overcooked_ai_amd", "csrc")
+from case_support import CSRC, check_census, ledger, print_ledger
 
 
 def _ledger():
     """instance or sequence (oc_multi_agent_plan's words) -> ids of the cases that are there for it"""
-    led = {}
-    for c in TC.CASES:
-        led.setdefault(c.expect, []).append(c.id)
-    return led
+    return ledger(TC.CASES, lambda c: c.expect)
 
 
 def _instantiated():
@@ -56,14 +51,7 @@ def test_cases_keep_the_restart_path_inside_the_run():
 
 
 def test_every_training_step_instance_of_the_sources_has_a_case_or_a_named_exclusion():
-    found = _instantiated()
-    assert len(found) == len(set(found)) == 16, "csrc/oc_amd.hip instantiates %d training-step kernels, not 16: %s" % (len(found), sorted(found))
-    assert sorted(found) == sorted(TC.INSTANCES)
-    reached = {text for text in _ledger() if text.startswith("k_")}
-    assert not reached & set(TC.UNREACHABLE), "reached after all: %s" % sorted(reached & set(TC.UNREACHABLE))
-    missing = sorted(set(found) - reached - set(TC.UNREACHABLE))
-    assert not missing, "no case reaches %s" % missing
-    assert reached | set(TC.UNREACHABLE) == set(found), "not an instance: %s" % sorted((reached | set(TC.UNREACHABLE)) - set(found))
+    check_census(_instantiated(), TC.INSTANCES, TC.UNREACHABLE, {text for text in _ledger() if text.startswith("k_")}, 16, "training-step kernels")
     # the sequence: drawn and standard starts, and oc_regen_layouts inside it
     seq = [text for text in _ledger() if text.startswith("sequence:")]
     assert any("oc_regen_layouts" in t for t in seq) and any("oc_reset_random" in t for t in seq) and any(t.endswith("oc_reset, oc_encode_lossless") for t in seq)
@@ -81,9 +69,7 @@ def test_the_named_exclusions_hold():
 def test_ledger():
     """instance -> case ids, one line per instance (shown by `pytest -s -k test_ledger`)."""
     led = _ledger()
-    print()
-    for text in TC.INSTANCES:
-        print("%s\n%30s%s" % (text, "<- ", ", ".join(led[text]) if text in led else "UNREACHABLE: " + TC.UNREACHABLE[text]))
+    print_ledger(TC.INSTANCES, led, TC.UNREACHABLE)
     for text in sorted(t for t in led if t.startswith("sequence:")):
         print("%s\n%30s%s" % (text, "<- ", ", ".join(led[text])))
     assert len([t for t in led if t.startswith("k_")]) + len(TC.UNREACHABLE) == len(TC.INSTANCES) == 16

@@ -12,13 +12,12 @@ Unless a case is there for the standard start it has a nonzero env_offset, drawn
 two restarts per env inside the run (horizon < steps / 2).  The actions are the oracle's Philox draws (O.random_actions), uploaded;
 a fixed handful per step is overwritten with 9, the illegal-action path: such an env stays untouched, timestep included, so
 `steps % horizon` leaves room for it and every env still restarts steps // horizon times."""
-import functools
-import os
 from collections import namedtuple
 
 import numpy as np
 
-from rollout_cases import DRAWN, SEVEN, table_of as _rollout_table_of
+from case_support import DRAWN, EventCounts, layout_ids, new_oracle, register_grid, register_table, start_spec_of, table_of, tf as _tf
+from rollout_cases import SEVEN  # (and its tables: the import registers them)
 
 N_OBS = 32768           # the smallest batch k_train_step_obs serves: a workgroup of 256 envs for half of the 256 CUs (1 024 SIMDs / 8)
 N_BAD = 5               # illegal actions per step
@@ -28,10 +27,6 @@ GAMMA = 0.99
 ANNEAL = dict(reward_shaping_factor=1.0, reward_shaping_horizon=1000)
 ANNEAL_TIMESTEPS = 337
 ANNEALED = 0.663
-
-
-def _tf(v):
-    return "true" if v else "false"
 
 
 def obs_k(MAXP, T, NWV):
@@ -118,27 +113,19 @@ CASES = tuple(CASES)
 assert len({c.id for c in CASES}) == len(CASES)
 
 
-@functools.lru_cache(maxsize=None)
-def table_of(name):
-    """The LayoutTable a case names: rollout_cases' tables, and two of this list's own."""
+def _seven_and_scenario2_s():
     from overcooked_ai_amd.layouts import LayoutSpec, LayoutTable, spec_from_name
 
-    if name == "cramped_room_two_pots":  # 20 cells, two pots: MAXP=2 with private images of >= 6 envs
-        return LayoutTable([LayoutSpec(dict(spec_from_name("cramped_room").to_layout_dict(), layout_name=name,
-                                            grid="XPPXX\nO  2O\nX1  X\nXDXSX"))])
-    if name == "three_pots_old":  # old dynamics accepts three-item orders only (not SEVEN's): cramped_room's, and three pots
-        return LayoutTable([LayoutSpec(dict(spec_from_name("cramped_room", old_dynamics=True).to_layout_dict(), layout_name=name,
-                                            grid="XPPPX\nO  2O\nX1  X\nXDXSX"))])
-    if name == "seven_and_scenario2_s":  # 7 x 4: a table with a layout of more than two pots (four layouts: a re-draw moves 3 envs of 4)
-        return LayoutTable([LayoutSpec(SEVEN), spec_from_name("scenario2_s"), spec_from_name("cramped_room"),
-                            table_of("cramped_room_two_pots").specs[0]], pad_to=(7, 4))
-    return _rollout_table_of(name)
+    return LayoutTable([LayoutSpec(SEVEN), spec_from_name("scenario2_s"), spec_from_name("cramped_room"),
+                        table_of("cramped_room_two_pots").specs[0]], pad_to=(7, 4))
 
 
-def layout_ids(c):
-    """Global env e starts on layout e % K; None for a table of one layout."""
-    K = len(table_of(c.table))
-    return None if K == 1 else ((np.arange(c.n_envs) + c.env_offset) % K).astype(np.uint16)
+# this list's own tables, beside rollout_cases'
+register_grid("cramped_room_two_pots", "XPPXX\nO  2O\nX1  X\nXDXSX")  # 20 cells, two pots: MAXP=2 with private images of >= 6 envs
+# old dynamics accepts three-item orders only (not SEVEN's): cramped_room's, and three pots
+register_grid("three_pots_old", "XPPPX\nO  2O\nX1  X\nXDXSX", old_dynamics=True)
+# 7 x 4: a table with a layout of more than two pots (four layouts: a re-draw moves 3 envs of 4)
+register_table("seven_and_scenario2_s", _seven_and_scenario2_s)
 
 
 def factor_at(c, t):
@@ -166,16 +153,6 @@ def actions_of(c, t):
     if t == 1:
         a[c.n_envs - 1, 0] = 9
     return a
-
-
-def start_spec_of(c, epoch=1):
-    """The _lib.OcStartSpec VecOvercookedMultiAgent.step hands to the library at `epoch`; None for the standard start."""
-    from overcooked_ai_amd import _lib
-
-    if c.start == "standard":
-        return None
-    count = len(table_of(c.table)) if c.start == "regen" else 0
-    return _lib.OcStartSpec(c.seed, c.env_offset, epoch, int(DRAWN["random_start_pos"]), float(DRAWN["rnd_obj_prob_thresh"]), 0, count)
 
 
 def plan_of_case(c):
@@ -217,8 +194,7 @@ class OracleTrainStep:
         from oracle import oracle as O
         from overcooked_ai_amd.potential import potential_params
 
-        O.set_threads(min(16, len(os.sched_getaffinity(0))))
-        self.O, self.orc = O, O.Oracle([O.mdp_from_layout_dict(s.to_layout_dict()) for s in specs])
+        self.O, self.orc = O, new_oracle(specs)
         self.n, self.seed, self.env_offset, self.horizon = n, seed, env_offset, horizon
         self.start, self.regen, self.use_phi, self.events = dict(start or {}), regen, use_phi, events
         self.layout_id = None if layout_id is None else np.ascontiguousarray(layout_id, dtype=np.uint16).copy()
@@ -227,8 +203,8 @@ class OracleTrainStep:
             self.state = self.orc.reset_random(self.state, seed=seed, env_offset=env_offset, epoch=0, layout_id=self.layout_id, **self.start)
         self.epoch = 1
         self.ep_returns = np.zeros((n, 4), np.float32)
-        self.counts = np.zeros((n, 25, 2), np.int64)       # [env][event][player] of the running episode
-        self.counts_done = np.zeros((n, 25, 2), np.int64)  # ... of each env's last finished episode
+        self.event_counts = EventCounts(n)
+        self.counts, self.counts_done = self.event_counts.running, self.event_counts.published
         self.phi_cur = self.phi_next = np.zeros((n,), np.float64)
         if use_phi:
             L = len(specs)
@@ -256,11 +232,7 @@ class OracleTrainStep:
         fin = self.done != 0
         self.ep_out = self.ep_returns.copy()
         if self.events:
-            masks = orc.last_events
-            bits = ((masks[:, None] >> np.arange(50, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.int64)
-            self.counts += bits.reshape(self.n, 25, 2)
-            self.counts_done[fin] = self.counts[fin]
-            self.counts[fin] = 0
+            self.event_counts.update(orc.last_events, finished=fin, cleared=fin)  # (no auto-reset here: cleared where done)
         if self.start or self.regen is not None:
             spec = O.start_spec(seed=self.seed, env_offset=self.env_offset, epoch=self.epoch, regen=self.regen, **self.start)
             if self.regen is not None and self.layout_id is not None:
