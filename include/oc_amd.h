@@ -199,7 +199,15 @@ int oc_batch_hints(const OcLayout* h_layouts, int n_layouts, OcBatch* batch);
  * oc_reset_random for global env g = env_offset + e and
  *      epoch of a restart at step k of the call = epoch + k      (k = 0 for single-step entry points),
  * so a caller that passes epoch = 1 + (steps executed so far) never reuses the draws of its initial
- * oc_reset_random(epoch 0).  Supported by the table-driven kernels (oc_step and oc_step_many without
+ * oc_reset_random(epoch 0) — for 2^32 - 1 steps per env: epoch is a 32-bit word and epoch + k is taken mod 2^32, inside a
+ * call as well (a call that starts at epoch 2^32 - 3 draws its restart at step 5 from epoch 2); a caller that counts
+ * further passes its counter mod 2^32, and the draws of epoch 0 come round again with step 2^32.
+ * The other counters are used in their full 64-bit width: t0 (block index b = t >> 3 of the action stream), env_offset + e
+ * and seed each enter the Philox counter or key as a low and a high 32-bit word, and env_offset + e carries from the low
+ * word into the high one inside a batch.  t0 and env_offset are int64_t in the signatures and are reinterpreted as
+ * uint64_t: a negative value is not refused, it names the counter 2^64 + value (t0 = -8 is block 2^61 - 1, steps
+ * -8..-1, and the call's step 8 is global step 0; env_offset = -1 makes local env 0 global env 2^64 - 1 and local env 1
+ * global env 0).  Supported by the table-driven kernels (oc_step and oc_step_many without
  * OC_OPT_PREDICATE_INTERACT — with or without event logging —, oc_rollout_random without OC_OPT_LANE_PAIR /
  * PREDICATE_INTERACT, oc_step_encode, oc_rollout_encode, oc_multi_agent_step); the others return OC_EINVAL.
  */
@@ -478,9 +486,21 @@ int oc_multi_agent_step(const OcBatch* batch, void* d_state, const uint8_t* d_ac
  *      b = 0: word 0 -> joint position index mulhi(word, n_joint) into the row-major product of free cells
  *      b = 1 + i (player i): {u, kind, n, m}: holds iff u < T; kind < 858993459 dish, < 3435973836 onion, else soup;
  *                            n_onion = 1 + mulhi(n, 3), n_tomato = mulhi(m, 4 - n_onion)
- *      b = 3 + k (pot k):    {u, n, m, q}: filled iff u < T; cooking (tick 0) iff q < T
- *      T = floor(rnd_obj_prob_thresh * 2^32)
- * for global env g = env_offset + e.  d_mask as in oc_reset.
+ *      b = 3 + k (pot k):    {u, n, m, q}: filled iff u < T, with n_onion and n_tomato from n and m as above; cooking
+ *                            (tick 0) iff q < T, else idle (tick -1)
+ *      T = floor(rnd_obj_prob_thresh * 2^32)       (1.0 gives 2^32: every 32-bit word is below it)
+ * for global env g = env_offset + e, with mulhi(a, b) = floor(a * b / 2^32).  In full:
+ *   - a block's words are the four output words of philox4x32_10 in order ({u, kind, n, m} = words 0..3); the key's high
+ *     word is seed_hi ^ 0x52535421 whatever the block, and epoch is the 32-bit word the caller passes (OcStartSpec);
+ *   - the free cells are the layout's floor cells (' ' in its grid, the players' start cells among them) in row-major order,
+ *     cell y * width + x; with F of them and two players n_joint = F * (F - 1) and index j names the ordered pair of distinct
+ *     cells (a, b'): a = j / (F - 1), b = j % (F - 1), b' = b + (b >= a); with one player n_joint = F and the cell is j.
+ *     Without random_start_pos the players stand on the layout's start cells and block 0 is not drawn.  Orientation NORTH;
+ *   - pot k is the layout's k-th pot cell in row-major order; a soup's ingredients are its onions, then its tomatoes; a
+ *     held soup is finished (cooking tick = its recipe's cook time);
+ *   - with rnd_obj_prob_thresh = 0 no block but block 0 is drawn: empty hands, empty pots;
+ *   - no object lies on a counter, timestep 0, and the episode returns of the env are cleared.
+ * d_mask as in oc_reset.
  */
 int oc_reset_random(const OcBatch* batch, void* d_state, const uint8_t* d_mask, float* d_ep_returns, uint64_t seed,
                     int64_t env_offset, uint32_t epoch, int random_start_pos, double rnd_obj_prob_thresh,

@@ -233,12 +233,13 @@ def env_kwargs(c):
 class OracleRun:
     """The C oracle's run of one case.  `state` and `ep_returns` follow the run in place; step(k) gives the rewards [n, 4] and
     flags [n] of step k (random policy: the Philox actions of step t0 + k; a restart at step k draws from epoch 1 + k, as a fresh
-    VecOvercookedEnv's first launch does); obs(a, b) is the int32 lossless encoding of envs a..b-1 of the current states."""
+    VecOvercookedEnv's first launch does, or from epoch0 + k); obs(a, b) is the int32 lossless encoding of envs a..b-1 of the current
+    states."""
 
-    def __init__(self, c):
+    def __init__(self, c, epoch0=None):
         from oracle import oracle as O
 
-        self.c, self.O = c, O
+        self.c, self.O, self.epoch0 = c, O, 1 if epoch0 is None else epoch0
         self.orc = new_oracle(table_of(c.table).specs)
         self.layout_id = layout_ids(c)
         self.state = states_of(c).copy()
@@ -247,7 +248,7 @@ class OracleRun:
 
     def step(self, k):
         c = self.c
-        start = self.O.start_spec(seed=c.seed, env_offset=c.env_offset, epoch=1 + k, **DRAWN) if c.start == "drawn" else None
+        start = self.O.start_spec(seed=c.seed, env_offset=c.env_offset, epoch=self.epoch0 + k, **DRAWN) if c.start == "drawn" else None
         kw = dict(horizon=c.horizon, options=1, layout_id=self.layout_id, ep_returns=self.ep_returns, start=start)
         if self.actions is not None:
             self.state, rew, fl = self.orc.step(self.state, self.actions[k], **kw)

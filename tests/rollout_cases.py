@@ -172,15 +172,17 @@ for _name in ("mix5", "canonical_5_x8", "canonical_4_old", "canonical_4_old_x9",
 
 
 def plan_of(table, n_envs, n_steps, t0, horizon, tiled=False, one_wavefront=False, outputs=True, events=0, start=None, regen=None,
-            seed=0, env_offset=0, epoch=1):
-    """oc_rollout_plan's answer for the call VecOvercookedEnv.rollout_random makes of these (auto_reset on)."""
+            seed=0, env_offset=0, epoch=1, option=None):
+    """oc_rollout_plan's answer for the call VecOvercookedEnv.rollout_random makes of these (auto_reset on; option: None, or the
+    env's switch to an opt-in kernel, "lane_pair" / "predicate_interact")."""
     from overcooked_ai_amd import _lib, dispatch
 
     options = _lib.OPT_AUTO_RESET | (_lib.OPT_FLAGS_TILED8 if tiled else 0) | (_lib.OPT_ONE_WAVEFRONT if one_wavefront else 0)
+    options |= {None: 0, "lane_pair": _lib.OPT_LANE_PAIR, "predicate_interact": _lib.OPT_PREDICATE_INTERACT}[option]
     sp = None
     if start or regen:
         first, count = regen or (0, 0)
-        sp = _lib.OcStartSpec(seed, env_offset, epoch, int(bool((start or {}).get("random_start_pos"))),
+        sp = _lib.OcStartSpec(seed, env_offset, epoch & 0xFFFFFFFF, int(bool((start or {}).get("random_start_pos"))),
                               float((start or {}).get("rnd_obj_prob_thresh", 0.0)), first, count)
     return dispatch.rollout_plan(table, n_envs, n_steps=n_steps, t0=t0, horizon=horizon, options=options, with_outputs=outputs,
                                  event_sink=events, start=sp)

@@ -224,10 +224,10 @@ class OracleRun:
     [player] of the running episode, and of each env's last finished one) follow the run in place; `prev_state` is the state step k
     acted on."""
 
-    def __init__(self, c):
+    def __init__(self, c, epoch0=None):
         from oracle import oracle as O
 
-        self.c, self.O = c, O
+        self.c, self.O, self.epoch0 = c, O, 1 if epoch0 is None else epoch0  # (epoch0: the env's counter where it was set by hand)
         self.orc = new_oracle(table_of(c.table).specs)
         self.layout_id = layout_ids(c)
         self.state = self.prev_state = states_of(c).copy()
@@ -240,7 +240,7 @@ class OracleRun:
         c = self.c
         start = None
         if c.start != "standard":
-            start = self.O.start_spec(seed=c.seed, env_offset=c.env_offset, epoch=1 + k,
+            start = self.O.start_spec(seed=c.seed, env_offset=c.env_offset, epoch=self.epoch0 + k,
                                       regen=(0, len(table_of(c.table))) if c.start == "regen" else None, **DRAWN)
         self.prev_state = self.state
         self.state, rew, fl = self.orc.step(self.state, self.actions[k], horizon=c.horizon, options=1, layout_id=self.layout_id,

@@ -15,66 +15,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from case_support import EventCounts, compare, new_oracle as _oracle  # noqa: E402
-from gpu_support import gpu, packed_counters  # noqa: E402, F401
+from case_support import EventCounts, new_oracle as _oracle  # noqa: E402
+from gpu_support import gpu, long_launch_against_oracle as _long_launch_against_oracle, packed_counters  # noqa: E402, F401
 
-HORIZON, T = 400, 4000
-
-
-def _long_launch_against_oracle(gpu, table, n, lid=None, env_offset=0, seed=0, steps=T, horizon=HORIZON, start=None,
-                                flags_tiled8=False, one_wavefront=False, expect_shaped=True, t0=0, outputs=True, events=0,
-                                regen_layout=False, expect=None, **env_kw):
-    """flags_tiled8: the launch writes the OC_OPT_FLAGS_TILED8 layout (the instances bench.py times), untiled before the
-    comparison; one_wavefront: OC_OPT_ONE_WAVEFRONT (no mover / interact split where the batch would get it); t0: the launch's
-    first global step; outputs=False: no rewards / flags arrays — states, returns and counters are compared all the same;
-    events: 1 per-episode counters (running and published), 2 also the per-step masks, against the popcounts of the oracle's
-    event_infos; regen_layout: every restart re-draws the env's layout, the ids are compared; expect: the instance
-    oc_rollout_plan must name for exactly this call, asked on this device before the launch."""
-    from overcooked_ai_amd.vec_env import VecOvercookedEnv
-
-    env = VecOvercookedEnv(table, n, horizon=horizon, device=gpu, auto_reset=True, seed=seed, env_offset=env_offset,
-                           layout_id=lid, track_events=events > 0, regen_layout=regen_layout, **env_kw)
-    env.one_wavefront = one_wavefront
-    env.t_global = t0
-    assert bool(start) == env.random_starts, "start must name the env's own start_state_fn keywords"
-    if expect is not None:
-        plan = RC.plan_of(env.table, n, steps, t0, horizon, tiled=flags_tiled8, one_wavefront=one_wavefront, outputs=outputs,
-                       events=events, start=start, regen=env.regen, seed=seed, env_offset=env_offset, epoch=env.reset_epoch)
-        assert plan.startswith(expect), "this launch is planned as\n  %s\nnot as\n  %s" % (plan, expect)
-    run = RC.OracleLaunch(env.table.specs, n, layout_id=lid, seed=seed, env_offset=env_offset, horizon=horizon, start=start,
-                       regen=env.regen, events=events > 0)
-    rew = torch.zeros((steps, n, 4), dtype=torch.float32, device=gpu) if outputs else None
-    fl = torch.zeros((steps // 8, n, 8) if flags_tiled8 else (steps, n), dtype=torch.uint8, device=gpu) if outputs else None
-    ev = torch.zeros((steps, n), dtype=torch.int64, device=gpu) if events == 2 else None
-    what = "launch of %d envs x %d steps" % (n, steps)
-    compare(what, t0, "first states", env.get_packed_state(), run.state, lid, env_axis=1)
-    epoch = env.reset_epoch
-    env.rollout_random(steps, rew, fl, events_out=ev, flags_tiled8=flags_tiled8)  # ONE call
-    if flags_tiled8:
-        fl = VecOvercookedEnv.untile_flags(fl)
-    restarts = shaped = sparse = 0
-    for c0, rew_o, fl_o, masks_o in run.chunks(steps, t0=t0, epoch=epoch):
-        k = len(fl_o)
-        if outputs:
-            # ([step][env]...: the step a message names is the chunk's first, the index it gives starts with the step inside the chunk)
-            compare(what, c0, "flags of steps %d..%d" % (c0, c0 + k), fl[c0:c0 + k].cpu().numpy(), fl_o, lid, env_axis=1)
-            compare(what, c0, "rewards of steps %d..%d" % (c0, c0 + k), rew[c0:c0 + k].cpu().numpy(), rew_o, lid, env_axis=1)
-        if ev is not None:
-            compare(what, c0, "event masks of steps %d..%d" % (c0, c0 + k), ev[c0:c0 + k].cpu().numpy().view(np.uint64), masks_o, lid, env_axis=1)
-        restarts += int(((fl_o & 4) != 0).sum())
-        sparse += float(rew_o[..., :2].sum())
-        shaped += float(rew_o[..., 2:].sum())
-    last = t0 + steps - 1
-    if env.regen is not None:
-        compare(what, last, "layout ids", env.layout_ids(), run.layout_id, None)
-    compare(what, last, "final states", env.get_packed_state(), run.state, lid, env_axis=1)
-    compare(what, last, "episode returns", env.ep_returns.cpu().numpy(), run.ep_returns, lid)
-    if events:
-        compare(what, last, "running event counters", packed_counters(env.event_counts), run.counts, lid)
-        compare(what, last, "published event counters", packed_counters(env.event_counts_done), run.counts_done, lid)
-        assert run.counts_done.sum() > 0
-    assert restarts == n * (steps // horizon) and (shaped > 0 or not expect_shaped)
-    return sparse, shaped
+HORIZON = 400  # (the runner's default, gpu_support.long_launch_against_oracle: 4 000 steps at this horizon)
 
 
 def test_bench_launch_shape_cramped_room_65536_x_4000(gpu):

@@ -37,6 +37,11 @@ def _compare_obs(case, k, obs, ref):
 
 @pytest.mark.parametrize("case", OC.CASES, ids=lambda c: c.id)
 def test_every_observation_instance_against_the_oracle(case, gpu):
+    observation_case_against_the_oracle(case, gpu)
+
+
+def observation_case_against_the_oracle(case, gpu, epoch0=None):
+    """epoch0: the epoch the case's calls start from (the env's own counter, set after its construction; the oracle's run likewise)."""
     from overcooked_ai_amd.vec_env import VecOvercookedEnv
 
     table = OC.table_of(case.table)
@@ -46,7 +51,9 @@ def test_every_observation_instance_against_the_oracle(case, gpu):
     env.one_kernel = True
     env.set_packed_state(OC.states_of(case).copy())
     env.t_global = case.t0
-    ref = OC.OracleRun(case)
+    if epoch0 is not None:
+        env._epoch = epoch0
+    ref = OC.OracleRun(case, epoch0)
     lid = ref.layout_id
     acts = OC.actions_of(case)
     single = case.expect.startswith("k_rollout_encode<")

@@ -61,14 +61,17 @@ def _host(bufs):
     return out
 
 
-def _record_and_check(gpu, name, n, K, horizon, t0=0, seed=3, env_offset=0, start=None, regen=False, check_envs=None):
+def _record_and_check(gpu, name, n, K, horizon, t0=0, seed=3, env_offset=0, start=None, regen=False, check_envs=None, epoch0=None):
     """One recorded launch with everything on, then for every step k: oracle.step(states[k], actions[k], layout_id=layouts[k])
     = (states[k + 1] or the final state, layouts[k + 1] or the final ids, rewards[k], flags[k]), and its event mask =
-    events_out[k].  Returns the host arrays, the number of restarts and how many envs changed layout."""
+    events_out[k].  Returns the host arrays, the number of restarts and how many envs changed layout.  epoch0: the epoch the launch
+    starts from (the env's own counter, set after its construction)."""
     from oracle import oracle as O
 
     start = start or {}
     env = _env(gpu, name, n, horizon, seed=seed, env_offset=env_offset, t0=t0, regen=regen, **start)
+    if epoch0 is not None:
+        env._epoch = epoch0
     before, lid0, epoch = env.get_packed_state().copy(), env.layout_ids(), env.reset_epoch
     bufs = _buffers(env, K)
     env.rollout_random(K, **bufs)

@@ -20,10 +20,12 @@ from case_support import compare  # noqa: E402
 from gpu_support import gpu, guarded, guards_untouched, packed_counters  # noqa: E402, F401
 
 
-def _new_env(case, gpu):
+def _new_env(case, gpu, epoch0=None):
     from overcooked_ai_amd.vec_env import VecOvercookedEnv
 
     env = VecOvercookedEnv(SC.table_of(case.table), case.n_envs, device=gpu, **SC.env_kwargs(case))
+    if epoch0 is not None:
+        env._epoch = epoch0
     env.predicate_interact = case.predicate
     env.set_packed_state(SC.states_of(case).copy())
     return env
@@ -46,10 +48,15 @@ def _compare_env(case, k, env, ref, lid0):
 
 @pytest.mark.parametrize("case", SC.CASES, ids=lambda c: c.id)
 def test_every_step_instance_against_the_oracle(case, gpu):
+    step_case_against_the_oracle(case, gpu)
+
+
+def step_case_against_the_oracle(case, gpu, epoch0=None):
+    """epoch0: the epoch the case's calls start from (the env's own counter, set after its construction; the oracle's run likewise)."""
     table = SC.table_of(case.table)
     n, K = case.n_envs, case.n_steps
-    env = _new_env(case, gpu)
-    ref = SC.OracleRun(case)
+    env = _new_env(case, gpu, epoch0)
+    ref = SC.OracleRun(case, epoch0)
     acts = torch.from_numpy(np.array(SC.actions_of(case))).to(gpu)
     masks_on = SC.with_masks(case)
 
@@ -98,7 +105,7 @@ def test_every_step_instance_against_the_oracle(case, gpu):
         rew_h, fl_h = rew.view(K, n, 4).cpu().numpy(), fl.view(K, n).cpu().numpy()
         ev_h = None if ev is None else ev.view(K, n).cpu().numpy().view(np.uint64)
         # ... and the same K steps as single step calls on a second env
-        env2 = _new_env(case, gpu)
+        env2 = _new_env(case, gpu, epoch0)
         ev2 = torch.full((n,), -1, dtype=torch.int64, device=gpu) if masks_on else None
         for k in range(K):
             lid_k = None if ref.layout_id is None else ref.layout_id.copy()

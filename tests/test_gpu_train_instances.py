@@ -23,6 +23,11 @@ OBS_CHUNK = 16384  # envs per comparison of the observation: the oracle's int32 
 
 @pytest.mark.parametrize("case", TC.CASES, ids=lambda c: c.id)
 def test_every_training_step_instance_against_the_reference(case, gpu):
+    training_case_against_the_reference(case, gpu)
+
+
+def training_case_against_the_reference(case, gpu, epoch0=None):
+    """epoch0: the epoch the first step draws from (the env's own counter, set after its construction; the reference's likewise)."""
     from overcooked_ai_amd.multi_agent import VecOvercookedMultiAgent
 
     plan = TC.plan_of_case(case)
@@ -33,6 +38,8 @@ def test_every_training_step_instance_against_the_reference(case, gpu):
     assert env.plan() == plan, (case.id, env.plan(), plan)  # (the env's own batch and arrays give the plan the case was listed for)
     ref = TC.oracle_of(case)
     v = env.venv
+    if epoch0 is not None:
+        v._epoch = ref.epoch = epoch0
     lid = lambda: None if ref.layout_id is None else ref.layout_id  # noqa: E731
     compare(case, -1, "state", v.get_packed_state(), ref.state, lid(), env_axis=1)  # (the packed state is [plane][env][16])
     if case.use_phi:
