@@ -90,7 +90,8 @@ extern "C" {
                                          interact instead of the table-driven one (kept for cross-checking) */
 
 /* 0x10u: reserved (ABI <= 3: OC_OPT_ROLLOUT_V3, the round-1 rollout kernel, retired in ABI 4) */
-#define OC_OPT_ONE_KERNEL 0x20u /* oc_rollout_encode / oc_step_encode: take the single-kernel path (k_rollout_encode)
+#define OC_OPT_ONE_KERNEL 0x20u /* oc_rollout_encode / oc_step_encode / oc_rollout_featurize: take the single-kernel
+                                  path (k_rollout_encode, k_rollout_featurize)
                                   whenever the table allows it; by default it runs only for batches that give every CU
                                   a workgroup (it keeps 256 envs per CU on chip; smaller batches are faster through the
                                   one-step kernels, whose observation kernel spreads over all CUs) */
@@ -430,6 +431,32 @@ int oc_featurize(const OcBatch* batch, const uint8_t* d_plan_blob, const uint32_
                  float* d_features, int num_pots, void* stream);
 
 /*
+ * oc_rollout_featurize (ABI 6: an entry point added beside the others) — n_steps transitions AND featurize_state of both
+ * players after each of them, in one call: the trajectory of (reward, flag, features) per step that a behaviour-cloning data
+ * collection or evaluation rollout gathers (OvercookedEnv.featurize_state_mdp per step, env.py:282-286; the "bc" observation of
+ * OvercookedMultiAgent, rllib.py).  The counterpart of oc_rollout_encode for the other observation; argument for argument as there.
+ *   d_plan_blob / d_plan_off  the motion-cost tables of oc_featurize
+ *   d_actions   NULL: the uniform random policy, the Philox stream of oc_rollout_random (seed, env_offset, t0);
+ *               else [n_steps][n_envs][2] action indices as for oc_step_many (illegal: flagged OC_F_BAD_ACTION, the env
+ *               untouched, its features recomputed unchanged); caller actions need d_rewards and d_flags
+ *   d_rewards   [n_steps][n_envs][4] / d_flags [n_steps][n_envs] (may be NULL with the random policy)
+ *   d_features  features of step k at (char*)d_features + k * feat_step_stride: [n_envs][2][2 * (num_pots * 10 + 26) + 4]
+ *               float32 of the state the NEXT step starts from (after an auto-reset: the start state), exactly what oc_featurize
+ *               of d_state after step k gives; feat_step_stride in bytes, a multiple of 16; 0 = every step overwrites one buffer
+ *   num_pots    0..4, as for oc_featurize, whose every check applies (two-player layouts, 16-byte alignment)
+ *   options     OC_OPT_AUTO_RESET, OC_OPT_ONE_KERNEL (any other bit: OC_EINVAL);  start: as for oc_rollout_encode (a restart at
+ *               step k draws from epoch start->epoch + k; start->env_offset must equal env_offset)
+ * One layout of at most 64 cells with one or two pots, at least two steps and a batch of at least 64 envs per CU (or
+ * OC_OPT_ONE_KERNEL) run as ONE kernel (k_rollout_featurize: the env stays on chip for all steps, every wavefront featurizes its
+ * own 64 envs through a private int16 LDS image, no workgroup barrier in the step loop).  Any other case runs the one-step entry
+ * points and oc_featurize step by step with identical results.  Every check is made before any device call.
+ */
+int oc_rollout_featurize(const OcBatch* batch, const uint8_t* d_plan_blob, const uint32_t* d_plan_off, void* d_state,
+                         const uint8_t* d_actions, float* d_rewards, uint8_t* d_flags, float* d_ep_returns,
+                         float* d_features, int64_t feat_step_stride, int num_pots, int horizon, uint32_t options,
+                         uint64_t seed, int64_t env_offset, int64_t t0, int n_steps, const OcStartSpec* start, void* stream);
+
+/*
  * oc_shape_rewards — the per-agent training reward of the RLlib environment.
  * Replaces the reward arithmetic of OvercookedMultiAgent.step (human_aware_rl/rllib/rllib.py:306-329):
  *      out[e][i] = (sparse0 + sparse1) + reward_shaping_factor * dense_i
@@ -745,6 +772,26 @@ int oc_step_plan(const OcBatch* batch, int entry, int horizon, uint32_t options,
  */
 int oc_potential_plan(const OcBatch* batch, char* out, size_t out_size);
 int oc_featurize_plan(const OcBatch* batch, int num_pots, char* out, size_t out_size);
+
+/*
+ * oc_rollout_featurize_plan (ABI 6: an entry point added beside the others) — what oc_rollout_featurize would launch for this
+ * batch, as text; up to and including '>' the text is the instance's name and stable:
+ *   "k_rollout_featurize<MAXP=2, FAST=3> G=32, grid=256, 70656 B LDS"    one two-player layout of at most 64 cells with one or two
+ *                                                  pots, a batch of at least 64 envs per CU and n_steps >= 2 (or
+ *                                                  OC_OPT_ONE_KERNEL): envs per LDS image (always 32), workgroups, dynamic LDS
+ *   "step by step: oc_rollout_random + k_featurize<LAY_LDS=true> ..."    every other call: per step the one-step entry point
+ *   "step by step: oc_step + k_featurize<LAY_LDS=false> ..."             (oc_step with caller actions), then oc_featurize, whose
+ *                                                                       instance, grid and LDS bytes follow
+ *   "nothing to launch (no envs)" / "nothing to launch (no steps)"
+ * oc_rollout_featurize plans a call before it launches anything and launches from that plan; this is the same plan put into
+ * words: every check applies (a refusal returns its code, with the entry point's own message in oc_last_error), the code that
+ * answers is told which arrays a call has, not where they are, and holds no launch — so it also runs on a host without a GPU
+ * (the device's SIMD count then defaults to MI355X's 1 024).  The call described has the plan blob, a state and a 16-byte
+ * aligned feature array, env_offset equal to the start spec's, and with_actions / with_outputs / start as for oc_observation_plan.
+ *   out, out_size caller's text buffer (>= 256 bytes holds every answer)
+ */
+int oc_rollout_featurize_plan(const OcBatch* batch, int num_pots, int horizon, uint32_t options, int n_steps,
+                              int with_actions, int with_outputs, const OcStartSpec* start, char* out, size_t out_size);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 // observation_plan.hpp — host side of the observation paths: the geometry of a lossless observation and the plans of
-// oc_encode_lossless and oc_rollout_encode.  A plan makes every check and every choice of a call; nothing here launches, touches
+// oc_encode_lossless, oc_rollout_encode and oc_rollout_featurize.  A plan makes every check and every choice of a call; nothing here launches, touches
 // device memory or takes a device address (the one thing read from the runtime is simd_count()).  oc_amd.hip launches from
 // the plans; oc_observation_plan puts them into words.  Included by oc_amd.hip inside its anonymous namespace, after the checks
 // and the tuning knobs it uses.
@@ -218,4 +218,65 @@ void describe_rollout_encode_plan(const RolloutEncodePlan& p, bool caller_action
         const int used = snprintf(out, out_size, "step by step: %s + ", caller_actions ? "oc_step" : "oc_rollout_random");
         if (used > 0 && (size_t)used < out_size) describe_encode_plan(one_step, out + used, out_size - used);
     }
+}
+
+// ---- oc_rollout_featurize.  The instance: k_rollout_featurize<MAXP=2, FAST=3> (one two-player layout of at most 64 cells with
+//      one or two pots), or the one-step entry points and oc_featurize, step by step
+
+// tuning builds: the batch size from which the single kernel is taken without OC_OPT_ONE_KERNEL, forced (read at every call:
+// tools/time_rollout_featurize.py alternates the two paths in one process)
+inline int64_t rollout_featurize_fill(int64_t dflt) {
+    const int v = tuning_int("OC_ROLLOUT_FEATURIZE_FILL", -1);
+    return v >= 0 ? (int64_t)v : dflt;
+}
+
+struct RolloutFeaturizeArrays {
+    bool plan, state, actions, rewards, flags, features;  // plan: the blob and its offsets
+    bool features_aligned16;  // d_features and feat_step_stride are multiples of 16 bytes
+};
+struct RolloutFeaturizePlan {
+    int rc = OC_OK;  // the call is refused with this code (the message: oc_last_error)
+    enum Path { NOTHING, ONE_KERNEL, STEP_BY_STEP } path = NOTHING;  // no envs or no steps / k_rollout_featurize / the one-step entry points
+    int n_obj = 0;
+    StartArgs sa = {};
+    unsigned grid = 0; // ONE_KERNEL
+    size_t smem = 0;   // ONE_KERNEL: dynamic LDS
+};
+
+RolloutFeaturizePlan plan_rollout_featurize(const OcBatch* b, const RolloutFeaturizeArrays& have, int num_pots, int horizon, uint32_t options,
+                                            int64_t env_offset, int n_steps, const OcStartSpec* start) {
+    const char* const who = "oc_rollout_featurize";
+    RolloutFeaturizePlan p;
+    const auto refused = [&p](int rc) { p.rc = rc; return p; };
+    if (int rc = check_batch(b, &p.n_obj)) return refused(rc);
+    if (int rc = check_start(who, start, &p.sa, b)) return refused(rc);
+    if (!have.plan || !have.state || !have.features) return refused(refuse(who, "NULL plan / state / features pointer"));
+    if (num_pots < 0 || num_pots > 4) return refused(refuse(who, "num_pots must be in 0..4"));
+    if (!(b->batch_flags & OC_BATCH_TWO_PLAYERS)) return refused(refuse(who, "needs 2-player layouts"));
+    if (!have.features_aligned16) return refused(refuse(who, "d_features and feat_step_stride must be multiples of 16 bytes"));
+    if (int rc = check_horizon(who, horizon)) return refused(rc);
+    if (n_steps < 0 || n_steps > (1 << 30)) return refused(refuse(who, "n_steps must be in 0..2^30"));
+    if (options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_KERNEL))
+        return refused(refuse(who, "options other than OC_OPT_AUTO_RESET / OC_OPT_ONE_KERNEL"));
+    if (have.actions && (!have.rewards || !have.flags)) return refused(refuse(who, "caller actions need the rewards and flags arrays"));
+    if (start && start->env_offset != env_offset)  // (both paths: the one-step fallback would refuse it, the single kernel must too)
+        return refused(refuse(who, "start.env_offset differs from env_offset"));
+    if (b->n_envs == 0 || n_steps == 0) return p;
+    p.path = RolloutFeaturizePlan::STEP_BY_STEP;  // every table the single kernel does not take: the same result from the one-step kernels
+    // one layout of at most 64 cells with one or two pots: the whole trajectory in one launch (k_rollout_featurize), from 64
+    // envs per CU (16 384 on MI355X) and two steps on — or where OC_OPT_ONE_KERNEL asks.  oc_rollout_encode's rule, 192 envs per
+    // CU, was the starting point; measured (us per step, one kernel vs step by step, cramped_room / asymmetric_advantages):
+    // 16 384 envs 7.0 vs 15.8 / 7.3 vs 18.3, 32 768 envs 7.1 vs 18.2 / 7.4 vs 21.1, 65 536 envs 9.4 vs 23.7 / 8.9 vs 26.2
+    // (profiles/rollout_featurize.txt): a step of the kernel costs less than the second launch it saves long before every CU has
+    // a workgroup.  16 384 is the smallest batch measured; below it the one-step kernels stay
+    const bool fills_gpu = b->n_envs >= rollout_featurize_fill((simd_count() / 4) * 64) && n_steps >= 2;
+    if (!((fills_gpu || (options & OC_OPT_ONE_KERNEL)) && b->n_layouts == 1 && b->max_pots >= 1 && b->max_pots <= 2 &&
+          b->width * b->height <= 64))
+        return p;
+    // the LDS of a workgroup: the cell words of its 256 envs, their headers and one int16 image of RF_GROUP envs per wavefront
+    // (at most 32768 + 4096 + 4 * 17664 = 107 520 bytes: 64 cells, num_pots = 4)
+    p.grid = grid_for(b->n_envs);
+    p.smem = (size_t)p.n_obj * 16 * BLOCK * sizeof(uint16_t) + (size_t)BLOCK * 16 + 4 * feat_image_shorts(num_pots) * sizeof(int16_t);
+    p.path = RolloutFeaturizePlan::ONE_KERNEL;
+    return p;
 }

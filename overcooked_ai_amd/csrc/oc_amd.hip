@@ -14,11 +14,12 @@
 //   encode.hpp          lossless_state_encoding mdp.py:2385-2561: k_encode, k_encode_uniform
 //   rollout_encode.hpp  K transitions with the observation of every step in one launch: k_rollout_encode
 //   featurize.hpp       featurize_state mdp.py:2579-2898: k_featurize
+//   rollout_featurize.hpp  K transitions with the featurize_state observation of every step in one launch: k_rollout_featurize
 //   potential.hpp       potential_function mdp.py:2920-3238: k_potential, k_potential2
 //   shaping.hpp         OvercookedMultiAgent.step reward, rllib.py:306-329: k_shape_rewards
 //   train_obs.hpp       the training step with its observation in one kernel: k_train_step_obs
 //   stores_only.hpp     the output stores of a rollout and nothing else: k_output_stores_only (oc_output_stores_only)
-//   observation_plan.hpp  host only: the observation geometry and the plans of oc_encode_lossless / oc_rollout_encode
+//   observation_plan.hpp  host only: the observation geometry and the plans of oc_encode_lossless / oc_rollout_encode / oc_rollout_featurize
 //   this file           launch dispatch and the extern "C" entry points declared in include/oc_amd.h: oc_rollout_random,
 //                       oc_multi_agent_step, oc_encode_lossless, oc_rollout_encode, oc_step, oc_step_many and oc_step_server_open plan
 //                       a call (checks, then choices; no launch, no device address), then launch from the plan; oc_rollout_plan,
@@ -56,6 +57,7 @@ namespace {
 #include "encode.hpp"
 #include "rollout_encode.hpp"
 #include "featurize.hpp"
+#include "rollout_featurize.hpp"
 #include "potential.hpp"
 #include "shaping.hpp"
 #include "train_obs.hpp"
@@ -1387,6 +1389,62 @@ int rollout_encode_step_by_step(const RolloutEncodeCall& c) {
     }
     return OC_OK;
 }
+
+// ---- oc_rollout_featurize: planned first (observation_plan.hpp: plan_rollout_featurize), then launched from that plan — or, by
+//      oc_rollout_featurize_plan, described
+// The arrays and scalars of one oc_rollout_featurize call
+struct RolloutFeaturizeCall {
+    const OcBatch* b;
+    const uint8_t* d_plan_blob;
+    const uint32_t* d_plan_off;
+    void* d_state;
+    const uint8_t* d_actions;
+    float* d_rewards;
+    uint8_t* d_flags;
+    float* d_ep_returns;
+    float* d_features;
+    int64_t feat_step_stride;
+    int num_pots, horizon;
+    uint32_t step_options;  // OC_OPT_AUTO_RESET or nothing
+    uint64_t seed;
+    int64_t env_offset, t0;
+    int n_steps;
+    const OcStartSpec* start;
+    hipStream_t stream;
+};
+
+// the whole trajectory in one launch (k_rollout_featurize)
+int launch_rollout_featurize(const RolloutFeaturizePlan& p, const RolloutFeaturizeCall& c) {
+    const OcBatch* b = c.b;
+    if (want_lds(k_rollout_featurize<2, 3>, p.smem))
+        hipLaunchKernelGGL((k_rollout_featurize<2, 3>), dim3(p.grid), dim3(BLOCK), p.smem, c.stream, b->d_layouts, (uint4*)c.d_state,
+                           c.d_actions, (float4*)c.d_rewards, c.d_flags, (float4*)c.d_ep_returns, c.d_plan_blob, c.d_plan_off,
+                           (uint8_t*)c.d_features, c.feat_step_stride, b->n_envs, b->width, b->height, p.n_obj, c.num_pots, c.horizon,
+                           c.step_options, (uint32_t)c.seed, (uint32_t)(c.seed >> 32), c.env_offset, c.t0, c.n_steps, p.sa);
+    return check_launch("oc_rollout_featurize");
+}
+
+// every other table: the same result from the one-step entry points and oc_featurize, step by step
+int rollout_featurize_step_by_step(const RolloutFeaturizeCall& c) {
+    const OcBatch* b = c.b;
+    for (int k = 0; k < c.n_steps; ++k) {
+        const int64_t off = (int64_t)k * b->n_envs;
+        OcStartSpec sk;
+        if (c.start) { sk = *c.start; sk.epoch = c.start->epoch + (uint32_t)k; }  // a restart at step k draws from epoch + k
+        const OcStartSpec* spk = c.start ? &sk : nullptr;
+        int rc;
+        if (c.d_actions)
+            rc = oc_step(b, c.d_state, c.d_state, c.d_actions + 2 * off, c.d_rewards + 4 * off, c.d_flags + off, c.d_ep_returns, nullptr,
+                         c.horizon, c.step_options, spk, nullptr, c.stream);
+        else
+            rc = oc_rollout_random(b, c.d_state, c.d_rewards ? c.d_rewards + 4 * off : nullptr, c.d_flags ? c.d_flags + off : nullptr,
+                                   c.d_ep_returns, c.horizon, c.step_options, c.seed, c.env_offset, c.t0 + k, 1, spk, nullptr, c.stream);
+        if (rc) return rc;
+        float* feat_k = (float*)((uint8_t*)c.d_features + (int64_t)k * c.feat_step_stride);
+        if ((rc = oc_featurize(b, c.d_plan_blob, c.d_plan_off, c.d_state, feat_k, c.num_pots, c.stream))) return rc;
+    }
+    return OC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1451,6 +1509,44 @@ int oc_observation_plan(const OcBatch* b, int obs_dtype, int horizon, uint32_t o
         if (one_step.rc != OC_OK) return one_step.rc;
     }
     describe_rollout_encode_plan(p, have.actions, one_step, out, out_size);
+    return OC_OK;
+}
+
+int oc_rollout_featurize(const OcBatch* b, const uint8_t* d_plan_blob, const uint32_t* d_plan_off, void* d_state,
+                         const uint8_t* d_actions, float* d_rewards, uint8_t* d_flags, float* d_ep_returns, float* d_features,
+                         int64_t feat_step_stride, int num_pots, int horizon, uint32_t options, uint64_t seed, int64_t env_offset,
+                         int64_t t0, int n_steps, const OcStartSpec* start, void* stream) {
+    const RolloutFeaturizeArrays have = {d_plan_blob && d_plan_off, d_state != nullptr, d_actions != nullptr, d_rewards != nullptr,
+                                         d_flags != nullptr, d_features != nullptr,
+                                         aligned16(d_features) && feat_step_stride >= 0 && (feat_step_stride & 15) == 0};
+    const RolloutFeaturizePlan p = plan_rollout_featurize(b, have, num_pots, horizon, options, env_offset, n_steps, start);
+    if (p.rc != OC_OK || p.path == RolloutFeaturizePlan::NOTHING) return p.rc;
+    const RolloutFeaturizeCall c = {b, d_plan_blob, d_plan_off, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_features,
+                                    feat_step_stride, num_pots, horizon, options & (uint32_t)OC_OPT_AUTO_RESET, seed, env_offset, t0,
+                                    n_steps, start, (hipStream_t)stream};
+    if (p.path == RolloutFeaturizePlan::ONE_KERNEL) return launch_rollout_featurize(p, c);
+    return rollout_featurize_step_by_step(c);
+}
+
+int oc_rollout_featurize_plan(const OcBatch* b, int num_pots, int horizon, uint32_t options, int n_steps, int with_actions,
+                              int with_outputs, const OcStartSpec* start, char* out, size_t out_size) {
+    if (!out || out_size == 0) return fail(OC_EINVAL, "oc_rollout_featurize_plan: no output buffer");
+    out[0] = 0;
+    // the call oc_rollout_featurize would get: the plan blob, a state, an aligned feature buffer, the named arrays, the env offset of
+    // the start spec
+    const RolloutFeaturizeArrays have = {true, true, with_actions != 0, with_outputs != 0, with_outputs != 0, true, true};
+    const RolloutFeaturizePlan p = plan_rollout_featurize(b, have, num_pots, horizon, options, start ? start->env_offset : 0, n_steps, start);
+    if (p.rc != OC_OK) return p.rc;
+    if (p.path == RolloutFeaturizePlan::NOTHING) {
+        snprintf(out, out_size, "nothing to launch (%s)", b->n_envs == 0 ? "no envs" : "no steps");
+    } else if (p.path == RolloutFeaturizePlan::ONE_KERNEL) {
+        snprintf(out, out_size, "k_rollout_featurize<MAXP=2, FAST=3> G=%d, grid=%u, %zu B LDS", RF_GROUP, p.grid, p.smem);
+    } else {  // per step the one-step entry point named here, then oc_featurize, whose own plan follows
+        const FeaturizePlan f = plan_featurize(b, true, true, num_pots);
+        if (f.rc != OC_OK) return f.rc;
+        snprintf(out, out_size, "step by step: %s + k_featurize<LAY_LDS=%s> grid=%u, %zu B LDS", with_actions ? "oc_step" : "oc_rollout_random",
+                 f.lay_lds ? "true" : "false", f.grid, f.smem);
+    }
     return OC_OK;
 }
 

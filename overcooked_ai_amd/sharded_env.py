@@ -125,6 +125,16 @@ class ShardedVecOvercookedEnv:
             return torch.empty(shape if n_steps is None else (int(n_steps),) + shape, dtype=dtype, device=s.device)
         return self._each(ob)
 
+    def alloc_features(self, n_steps=None, num_pots=2):
+        """Per-shard feature buffers: float32 [n, 2, 2*(num_pots*10+26)+4] (n_steps None: one row per env and player) or the
+        trajectory form [n_steps, n, 2, total] of rollout_featurize."""
+        total = 2 * (int(num_pots) * 10 + 26) + 4
+
+        def fe(s, i):
+            shape = (s.stop - s.start, 2, total)
+            return torch.empty(shape if n_steps is None else (int(n_steps),) + shape, dtype=torch.float32, device=s.device)
+        return self._each(fe)
+
     def _split(self, t, per_env_dim=0):
         """A caller tensor over this object's envs -> per-shard tensors on the shards' devices (async copies)."""
         if isinstance(t, (list, tuple)):
@@ -176,6 +186,17 @@ class ShardedVecOvercookedEnv:
                                                      None if flags_out is None else flags_out[i],
                                                      None if acts is None else acts[i], dtype=dtype))
         return obs_out, rewards_out, flags_out
+
+    def rollout_featurize(self, n_steps, feats_out, rewards_out=None, flags_out=None, actions=None, num_pots=2, counter_goals="none"):
+        """n_steps transitions with featurize_state after every step on every shard (VecOvercookedEnv.rollout_featurize).
+        feats_out: per-shard list (alloc_features(n_steps) for the trajectory, alloc_features() for the last step only);
+        actions: None (the random policy, the global Philox stream) or uint8 [n_steps, n_local, 2] / a per-shard list."""
+        acts = None if actions is None else self._split(actions, per_env_dim=1)
+        self._each(lambda s, i: s.env.rollout_featurize(n_steps, feats_out[i], None if rewards_out is None else rewards_out[i],
+                                                        None if flags_out is None else flags_out[i],
+                                                        None if acts is None else acts[i], num_pots=num_pots,
+                                                        counter_goals=counter_goals))
+        return feats_out, rewards_out, flags_out
 
     def step_encode(self, actions, dtype=torch.uint8, out=None):
         """step(actions) + the lossless observation of the new states in one C call per shard (VecOvercookedEnv.step_encode).

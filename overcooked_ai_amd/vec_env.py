@@ -44,7 +44,7 @@ class VecOvercookedEnv:
         self.lane_pair = False     # rollout_random: force the lane-pair kernel where the table allows it
         self.one_wavefront = False # rollout_random: keep every env-step in one wavefront (OC_OPT_ONE_WAVEFRONT: no mover / interact split)
         self.predicate_interact = False  # rollout_random: lane-per-env kernel with the predicate-network interact
-        self.one_kernel = False          # step_encode / rollout_encode: the single-kernel path whatever the batch size
+        self.one_kernel = False          # step_encode / rollout_encode / rollout_featurize: the single-kernel path whatever the batch size
         self.seed = int(seed)
         self.env_offset = int(env_offset)
         self.t_global = 0  # global step counter feeding the Philox counter of rollout_random
@@ -521,6 +521,71 @@ class VecOvercookedEnv:
         instance's name), with its grid and dynamic LDS bytes; counter_goals changes no choice."""
         out = ctypes.create_string_buffer(320)
         _lib.check(self.lib.oc_featurize_plan(self._bref, int(num_pots), out, len(out)), "oc_featurize_plan")
+        return out.value.decode()
+
+    def rollout_featurize(self, n_steps, feats_out, rewards_out=None, flags_out=None, actions=None, num_pots=2, counter_goals="none"):
+        """n_steps transitions with featurize_state (mdp.py:2579) of both players after every step, one C call
+        (oc_rollout_featurize; a single kernel for one layout of at most 64 cells with one or two pots from 64 envs per CU
+        and n_steps >= 2 on — or `one_kernel` —, else the one-step kernels and featurize step by step;
+        `plan_rollout_featurize` says which).  actions: None = the random policy of rollout_random (same Philox stream), or uint8
+        [n_steps, n_envs, 2].  feats_out: float32 [n_steps, n_envs, 2, 2*(num_pots*10+26)+4] (the whole trajectory) or
+        [n_envs, 2, total] (every step overwrites it: only the last features survive).  rewards_out float32 [n_steps, n_envs, 4] /
+        flags_out uint8 [n_steps, n_envs] (required with caller actions).  counter_goals: as for featurize.  With track_events
+        the one-step calls run step by step (the event counters ride on their OcEventSink)."""
+        K = int(n_steps)
+        blob, offs = self._plan(counter_goals)
+        total = 2 * (int(num_pots) * 10 + 26) + 4
+        per_step = self.n_envs * 2 * total
+        if feats_out.dim() == 4:
+            self._check(feats_out, torch.float32, K * per_step, "feats_out")
+            stride = per_step * 4
+        else:
+            self._check(feats_out, torch.float32, per_step, "feats_out")
+            stride = 0
+        if actions is not None:
+            self._check(actions, torch.uint8, K * self.n_envs * 2, "actions")
+        if rewards_out is not None:
+            self._check(rewards_out, torch.float32, K * self.n_envs * 4, "rewards_out")
+        if flags_out is not None:
+            self._check(flags_out, torch.uint8, K * self.n_envs, "flags_out")
+        if actions is not None and (rewards_out is None or flags_out is None):
+            raise ValueError("caller actions need rewards_out and flags_out")
+        if self.event_counts is not None:  # event counters: the one-step calls, step by step
+            for k in range(K):
+                if actions is None:
+                    self.rollout_random(1, None if rewards_out is None else rewards_out[k:k + 1],
+                                        None if flags_out is None else flags_out[k:k + 1])
+                else:
+                    r, f = self.step(actions[k])
+                    rewards_out[k].copy_(r)
+                    flags_out[k].copy_(f)
+                self.featurize(num_pots, counter_goals, out=feats_out[k] if stride else feats_out)
+            return feats_out, rewards_out, flags_out
+        rc = self._launch(self.lib.oc_rollout_featurize, self._bref, blob.data_ptr(), offs.data_ptr(), self._state_ptr,
+                          actions.data_ptr() if actions is not None else None,
+                          rewards_out.data_ptr() if rewards_out is not None else None,
+                          flags_out.data_ptr() if flags_out is not None else None, self._ep_ptr, feats_out.data_ptr(), stride,
+                          int(num_pots), self.horizon,
+                          (_lib.OPT_AUTO_RESET if self.auto_reset else 0) | (_lib.OPT_ONE_KERNEL if self.one_kernel else 0),
+                          self.seed, self.env_offset, self.t_global, K, self._start_spec() if self.auto_reset else None)
+        _lib.check(rc, "oc_rollout_featurize")
+        if actions is None:
+            self.t_global += K
+        self._advance(K)
+        return feats_out, rewards_out, flags_out
+
+    def plan_rollout_featurize(self, n_steps, num_pots=2, actions=False, outputs=True):
+        """What the next rollout_featurize(n_steps, ..., num_pots=num_pots) launches, in oc_rollout_featurize_plan's words (up to and
+        including '>' the instance's name; "step by step: <one-step entry point> + <featurize instance>" where every step is two
+        calls).  actions: caller actions are given; outputs: rewards_out and flags_out are.  `one_kernel` is honoured."""
+        one_step = "oc_step" if actions else "oc_rollout_random"
+        if self.event_counts is not None and int(n_steps) >= 1:  # (this class's own loop over the one-step calls)
+            return "step by step: %s + %s" % (one_step, self.featurize_plan(num_pots))
+        out = ctypes.create_string_buffer(320)
+        options = (_lib.OPT_AUTO_RESET if self.auto_reset else 0) | (_lib.OPT_ONE_KERNEL if self.one_kernel else 0)
+        rc = self.lib.oc_rollout_featurize_plan(self._bref, int(num_pots), self.horizon, options, int(n_steps), int(bool(actions)),
+                                                int(bool(outputs)), self._start_spec() if self.auto_reset else None, out, len(out))
+        _lib.check(rc, "oc_rollout_featurize_plan")
         return out.value.decode()
 
     def _plan(self, counter_goals):
