@@ -90,8 +90,9 @@ extern "C" {
                                          interact instead of the table-driven one (kept for cross-checking) */
 
 /* 0x10u: reserved (ABI <= 3: OC_OPT_ROLLOUT_V3, the round-1 rollout kernel, retired in ABI 4) */
-#define OC_OPT_ONE_KERNEL 0x20u /* oc_rollout_encode / oc_step_encode / oc_rollout_featurize: take the single-kernel
-                                  path (k_rollout_encode, k_rollout_featurize)
+#define OC_OPT_ONE_KERNEL 0x20u /* oc_rollout_encode / oc_step_encode / oc_rollout_featurize /
+                                  oc_multi_agent_step_featurize: take the single-kernel
+                                  path (k_rollout_encode, k_rollout_featurize, k_train_step_feat)
                                   whenever the table allows it; by default it runs only for batches that give every CU
                                   a workgroup (it keeps 256 envs per CU on chip; smaller batches are faster through the
                                   one-step kernels, whose observation kernel spreads over all CUs) */
@@ -792,6 +793,59 @@ int oc_featurize_plan(const OcBatch* batch, int num_pots, char* out, size_t out_
  */
 int oc_rollout_featurize_plan(const OcBatch* batch, int num_pots, int horizon, uint32_t options, int n_steps,
                               int with_actions, int with_outputs, const OcStartSpec* start, char* out, size_t out_size);
+
+/*
+ * oc_multi_agent_step_featurize (ABI 6: an entry point added beside the others; no existing signature, struct or option changes,
+ * so the version stays) — oc_multi_agent_step with featurize_state (mdp.py:2579-2898, the observation of behaviour-cloning
+ * agents) of the states the next step starts from: what a training or evaluation loop with a "bc" partner needs every decision.
+ * Every argument of oc_multi_agent_step, in its order, up to and including d_obs, obs_dtype, horizon; then
+ *   d_feat_plan_blob, d_feat_plan_off   oc_featurize's motion-cost tables (planner.pack_plan_tables).  A pair of its own beside
+ *               d_plan_blob / d_plan_off: phi always uses the counter_goals = "none" tables, features may be asked with "all";
+ *               the two pairs may be the same pointers.  Required whenever d_features != NULL, also with d_phi_tables == NULL.
+ *   d_features  float32 [n_envs][2][2 * (num_pots * 10 + 26) + 4], 16-byte aligned: featurize_state of the state the NEXT step
+ *               starts from — after a restart the standard or drawn start state, on a re-drawn layout that layout's: exactly
+ *               what oc_featurize of d_state gives after the call, the convention of d_obs.  NULL: the call IS
+ *               oc_multi_agent_step, argument for argument.
+ *   num_pots    0..4, as for oc_featurize;  options: 0 or OC_OPT_ONE_KERNEL (any other bit: OC_EINVAL)
+ * All of oc_multi_agent_step's and all of oc_featurize's checks apply (two-player layouts), every one before any device call;
+ * refusals carry this entry point's name.  The paths, chosen by one planner (oc_multi_agent_step_featurize_plan says which):
+ *   k_train_step_feat<MAXP> (csrc/train_feat.hpp)   the whole call in ONE kernel — d_features without d_obs, one two-player
+ *               layout of at most 64 cells with one or two pots, no event sink, and a batch that gives at least a quarter of
+ *               the CUs a workgroup of 256 envs (>= 16 384 envs on MI355X; profiles/train_step_feat.txt) or OC_OPT_ONE_KERNEL:
+ *               eight wavefronts per 256 envs — four step and restart, four compute phi and the shaped rewards, all eight
+ *               featurize and stream the rows.  65 536 cramped_room envs, num_pots = 2: 15.4-15.5 us per call against 21.9-22.3 us
+ *               for the two launches
+ *   oc_multi_agent_step's own planned path, then k_featurize   every other call with features (d_obs as well, an event sink,
+ *               65..128 cells, several layouts, more than two pots, small batches), with identical results.
+ */
+int oc_multi_agent_step_featurize(const OcBatch* batch, void* d_state, const uint8_t* d_actions, float* d_rewards,
+                                  uint8_t* d_flags, float* d_ep_returns, float* d_ep_returns_out,
+                                  const uint8_t* d_plan_blob, const uint32_t* d_plan_off, const uint8_t* d_phi_tables,
+                                  double* d_phi_next, double* d_phi_cur, const double* d_phi_start,
+                                  double reward_shaping_factor, double* d_shaped, uint8_t* d_done, void* d_obs, int obs_dtype,
+                                  int horizon, const uint8_t* d_feat_plan_blob, const uint32_t* d_feat_plan_off,
+                                  float* d_features, int num_pots, uint32_t options, const OcStartSpec* start,
+                                  const OcEventSink* events, void* stream);
+
+/*
+ * oc_multi_agent_step_featurize_plan (ABI 6: an entry point added beside the others) — what oc_multi_agent_step_featurize would
+ * launch for this batch, as text; up to and including '>' the text is the instance's name and stable:
+ *   "k_train_step_feat<MAXP=1> G=32, grid=256, 124928 B LDS"     the one-kernel path: envs per private LDS image (32, 16 or 8: the
+ *                                                  largest whose eight images fit the LDS budget), workgroups, dynamic LDS
+ *   "k_train_step1<UNIFORM=true, MAXP=1, LAY_LDS=true> + k_featurize<LAY_LDS=true> grid=512, 56320 B LDS"
+ *                                                  every other call with features: oc_multi_agent_plan's text of the call, then
+ *                                                  oc_featurize_plan's
+ *   "nothing to launch (no envs)"
+ * with_features = 0: oc_multi_agent_plan's answer, word for word.  The same plan the entry point launches from, put into words:
+ * every check applies (refusals carry oc_multi_agent_step_featurize's name), the code that answers is told which arrays a call
+ * has, not where they are, and holds no launch — so it also runs on a host without a GPU (the device's SIMD count then defaults
+ * to MI355X's 1 024).  The call described has every required array (aligned), both episode-return arrays, the feature tables and,
+ * as named, d_obs, the phi tables and buffers, an event sink with per-episode counters.
+ *   out, out_size caller's text buffer (>= 256 bytes holds every answer)
+ */
+int oc_multi_agent_step_featurize_plan(const OcBatch* batch, int horizon, int with_obs, int obs_dtype, int with_features,
+                                       int num_pots, uint32_t options, int use_phi, int event_sink, const OcStartSpec* start,
+                                       char* out, size_t out_size);
 
 #ifdef __cplusplus
 }

@@ -22,9 +22,9 @@ OBS_U8, OBS_F32 = 0, 1
 
 EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes", "oc_batch_hints", "oc_step", "oc_step_many",
            "oc_rollout_random", "oc_rollout_record", "oc_rollout_record_ex", "oc_encode_lossless", "oc_step_encode", "oc_rollout_encode", "oc_featurize", "oc_rollout_featurize", "oc_potential",
-           "oc_phi_table_size", "oc_reset", "oc_reset_random", "oc_regen_layouts", "oc_shape_rewards", "oc_multi_agent_step",
+           "oc_phi_table_size", "oc_reset", "oc_reset_random", "oc_regen_layouts", "oc_shape_rewards", "oc_multi_agent_step", "oc_multi_agent_step_featurize",
            "oc_mailbox_open", "oc_mailbox_buffer", "oc_mailbox_step", "oc_mailbox_close", "oc_output_stores_only", "oc_rollout_plan", "oc_multi_agent_plan",
-           "oc_observation_plan", "oc_step_plan", "oc_potential_plan", "oc_featurize_plan", "oc_rollout_featurize_plan",
+           "oc_observation_plan", "oc_step_plan", "oc_potential_plan", "oc_featurize_plan", "oc_rollout_featurize_plan", "oc_multi_agent_step_featurize_plan",
            "oc_step_server_open", "oc_step_server_requests", "oc_step_server_responses", "oc_step_server_resume",
            "oc_step_server_play", "oc_step_server_sync", "oc_step_server_steps", "oc_step_server_close")
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
@@ -128,6 +128,9 @@ def load():
     L.oc_phi_table_size.restype = i32
     L.oc_multi_agent_step.restype = i32
     L.oc_multi_agent_step.argtypes = [bp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, vp, i32, i32, sp, ep, vp]
+    L.oc_multi_agent_step_featurize.restype = i32
+    L.oc_multi_agent_step_featurize.argtypes = [bp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, vp, i32, i32,
+                                                vp, vp, vp, i32, u32, sp, ep, vp]
     L.oc_shape_rewards.restype = i32
     L.oc_shape_rewards.argtypes = [bp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, vp]
     L.oc_reset_random.restype = i32
@@ -172,6 +175,8 @@ def load():
     L.oc_featurize_plan.argtypes = [bp, i32, ctypes.c_char_p, ctypes.c_size_t]
     L.oc_rollout_featurize_plan.restype = i32
     L.oc_rollout_featurize_plan.argtypes = [bp, i32, i32, u32, i32, i32, i32, sp, ctypes.c_char_p, ctypes.c_size_t]
+    L.oc_multi_agent_step_featurize_plan.restype = i32
+    L.oc_multi_agent_step_featurize_plan.argtypes = [bp, i32, i32, i32, i32, i32, u32, i32, i32, sp, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

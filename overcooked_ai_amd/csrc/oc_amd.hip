@@ -18,12 +18,13 @@
 //   potential.hpp       potential_function mdp.py:2920-3238: k_potential, k_potential2
 //   shaping.hpp         OvercookedMultiAgent.step reward, rllib.py:306-329: k_shape_rewards
 //   train_obs.hpp       the training step with its observation in one kernel: k_train_step_obs
+//   train_feat.hpp      the training step with the featurize_state observation in one kernel: k_train_step_feat
 //   stores_only.hpp     the output stores of a rollout and nothing else: k_output_stores_only (oc_output_stores_only)
 //   observation_plan.hpp  host only: the observation geometry and the plans of oc_encode_lossless / oc_rollout_encode / oc_rollout_featurize
 //   this file           launch dispatch and the extern "C" entry points declared in include/oc_amd.h: oc_rollout_random,
-//                       oc_multi_agent_step, oc_encode_lossless, oc_rollout_encode, oc_step, oc_step_many and oc_step_server_open plan
+//                       oc_multi_agent_step, oc_multi_agent_step_featurize, oc_encode_lossless, oc_rollout_encode, oc_step, oc_step_many and oc_step_server_open plan
 //                       a call (checks, then choices; no launch, no device address), then launch from the plan; oc_rollout_plan,
-//                       oc_multi_agent_plan, oc_observation_plan, oc_step_plan, oc_potential_plan and oc_featurize_plan put the plans into words
+//                       oc_multi_agent_plan, oc_multi_agent_step_featurize_plan, oc_observation_plan, oc_step_plan, oc_potential_plan and oc_featurize_plan put the plans into words
 //
 // Execution model: one lane per env, 64-lane wavefronts, 256-lane workgroups.  This is integer /
 // indexing work (no MFMA).  Per-env state arrives as coalesced 16-byte planes (1 KiB per wavefront
@@ -61,6 +62,7 @@ namespace {
 #include "potential.hpp"
 #include "shaping.hpp"
 #include "train_obs.hpp"
+#include "train_feat.hpp"
 #include "stores_only.hpp"
 
 // ------------------------------------------------------------------------------------------
@@ -1044,8 +1046,8 @@ TrainObsShape train_obs_shape(const OcBatch* b, int n_obj, const TrainArrays& ha
 
 // Which of oc_multi_agent_step's paths, and which kernel instance of it, serves a call: the one place that reads the batch
 // and the call for it.  The train_step_* functions below launch what it returns; oc_multi_agent_plan puts it into words.
-TrainPlan plan_train_step(const OcBatch* b, const TrainArrays& have, int obs_dtype, int horizon, const OcStartSpec* start) {
-    const char* const who = "oc_multi_agent_step";
+TrainPlan plan_train_step(const OcBatch* b, const TrainArrays& have, int obs_dtype, int horizon, const OcStartSpec* start,
+                          const char* who = "oc_multi_agent_step") {  // who: the entry point a refusal names
     TrainPlan p;
     const auto refused = [&p](int rc) { p.rc = rc; return p; };
     if (!have.done) return refused(refuse(who, "d_done is required (it is the reset mask)"));
@@ -1216,6 +1218,102 @@ void describe_train_plan(const OcBatch* b, const TrainPlan& p, const TrainArrays
         snprintf(out, out_size, "k_train_step<UNIFORM=%s, EV=%s>%s", tf(p.uniform), tf(p.ev), then_obs);
     }
 }
+// the launches of a planned oc_multi_agent_step call
+int launch_train_step(const TrainStep& a, const TrainPlan& p) {
+    if (p.path == TrainPlan::GENERAL) return train_step_general(a);
+    if (p.path == TrainPlan::OBS) return train_step_obs(a, p);
+    return train_step_fused(a, p);
+}
+
+// ---- oc_multi_agent_step_featurize: oc_multi_agent_step with featurize_state of the states the next step starts from.  Planned
+//      first (plan_train_step_featurize: oc_multi_agent_step's checks and plan, oc_featurize's checks and plan, then the choice; no
+//      launch, no device memory), then launched from that plan — or, by oc_multi_agent_step_featurize_plan, described.  The paths:
+//        k_train_step_feat<MAXP>                                   the step and its features in one kernel (train_step_feat)
+//        oc_multi_agent_step's own path, then k_featurize<LAY_LDS>  every other call with features
+struct TrainFeatPlan {
+    int rc = OC_OK;
+    enum Path { NOTHING, ONE_KERNEL, TWO_LAUNCHES } path = TWO_LAUNCHES;
+    TrainPlan step;      // oc_multi_agent_step's plan of the call (ONE_KERNEL: its checks, n_obj and start arguments)
+    FeaturizePlan feat;  // TWO_LAUNCHES: oc_featurize's
+    int maxp = 2, g = 0;  // ONE_KERNEL: the instance's MAXP, envs per private image
+    size_t smem = 0;      // ONE_KERNEL: dynamic LDS
+};
+
+// The batch size from which k_train_step_feat is taken without OC_OPT_ONE_KERNEL: a quarter of the CUs get a workgroup of 256 envs
+// (16 384 envs on MI355X).  It started from k_train_step_obs's rule (half of the CUs) and was settled by run 1 of
+// profiles/train_step_feat.txt (tools/time_train_step_feat.py): at 16 384 envs, the smallest batch measured, a call takes 11.9 us
+// with the one kernel against 17.5 us for k_train_step1 + k_featurize on cramped_room and 12.1 against 17.4 us on
+// asymmetric_advantages (65 536 envs: 15.4 against 22.3 and 16.8 against 23.3 us).  Smaller batches are not measured and stay
+// with the two launches, whose k_featurize spreads over twice as many CUs.
+inline int64_t train_feat_fill() { return (simd_count() / 16) * BLOCK; }
+
+// feat_tables: both feature plan pointers are there; feat_aligned: d_features is 16-byte aligned
+TrainFeatPlan plan_train_step_featurize(const OcBatch* b, const TrainArrays& have, bool feat_tables, bool feat_aligned, int obs_dtype,
+                                        int horizon, int num_pots, uint32_t options, const OcStartSpec* start) {
+    const char* const who = "oc_multi_agent_step_featurize";
+    TrainFeatPlan p;
+    const auto refused = [&p](int rc) { p.rc = rc; return p; };
+    p.step = plan_train_step(b, have, obs_dtype, horizon, start, who);
+    if (p.step.rc != OC_OK) return refused(p.step.rc);
+    if (!feat_tables) return refused(refuse(who, "d_features needs the feature plan tables (d_feat_plan_blob, d_feat_plan_off)"));
+    if (num_pots < 0 || num_pots > 4) return refused(refuse(who, "num_pots must be in 0..4"));
+    if (!(b->batch_flags & OC_BATCH_TWO_PLAYERS)) return refused(refuse(who, "d_features needs 2-player layouts"));
+    if (!feat_aligned) return refused(refuse(who, "d_features must be 16-byte aligned"));
+    if (b->n_envs == 0) { p.path = TrainFeatPlan::NOTHING; return p; }
+    p.feat = plan_featurize(b, true, true, num_pots);  // (its checks were made above, under this entry point's name)
+    if (p.feat.rc != OC_OK) return refused(p.feat.rc);
+    // one kernel: no observation array, one layout of at most 64 cells with one or two pots on the wire-format step (no event
+    // sink), a batch that fills the device (or OC_OPT_ONE_KERNEL), and private images of at least 8 envs within the LDS budget
+    const TrainPlan& s = p.step;
+    if (have.obs || s.path != TrainPlan::FUSED || !s.lean || !s.uniform || b->width * b->height > 64) return p;
+    if (!(b->n_envs >= train_feat_fill() || (options & OC_OPT_ONE_KERNEL))) return p;
+    const size_t budget = 150 * 1024;
+    for (int g : {32, 16, 8}) {
+        if (train_feat_lds(s.n_obj, g, num_pots) > budget) continue;
+        p.path = TrainFeatPlan::ONE_KERNEL;
+        p.maxp = b->max_pots == 1 ? 1 : 2;
+        p.g = g;
+        p.smem = train_feat_lds(s.n_obj, g, num_pots);
+        break;
+    }
+    return p;
+}
+
+// the step and its features in one kernel (k_train_step_feat)
+int train_step_feat(const TrainStep& a, const TrainFeatPlan& p, const uint8_t* d_feat_plan_blob, const uint32_t* d_feat_plan_off,
+                    float* d_features, int num_pots) {
+    const OcBatch* b = a.b;
+    const dim3 grid(grid_for(b->n_envs));
+#define FEAT_GO(MP)                                                                                                      \
+    do {                                                                                                                 \
+        if (!want_lds(k_train_step_feat<MP>, p.smem)) break;                                                             \
+        hipLaunchKernelGGL((k_train_step_feat<MP>), grid, dim3(TF_WAVES * 64), p.smem, a.stream, b->d_layouts,           \
+                           (uint4*)a.d_state, a.d_actions, (float4*)a.d_rewards, a.d_flags, (float4*)a.d_ep_returns,     \
+                           (float4*)a.d_ep_returns_out, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_phi_next,       \
+                           a.d_phi_cur, a.d_phi_start, a.reward_shaping_factor, a.d_shaped, a.d_done, d_feat_plan_blob,  \
+                           d_feat_plan_off, d_features, b->n_envs, b->width, b->height, a.n_obj, num_pots, a.horizon,    \
+                           p.g, a.sa);                                                                                   \
+    } while (0)
+    if (p.maxp == 1) FEAT_GO(1);
+    else FEAT_GO(2);
+#undef FEAT_GO
+    return check_launch("oc_multi_agent_step_featurize");
+}
+
+// A plan in words (oc_multi_agent_step_featurize_plan): up to and including '>' the kernel instance, as tests match it
+void describe_train_feat_plan(const OcBatch* b, const TrainFeatPlan& p, const TrainArrays& have, int obs_dtype, const OcStartSpec* start,
+                              char* out, size_t out_size) {
+    if (p.path == TrainFeatPlan::NOTHING) {
+        snprintf(out, out_size, "nothing to launch (no envs)");
+    } else if (p.path == TrainFeatPlan::ONE_KERNEL) {
+        snprintf(out, out_size, "k_train_step_feat<MAXP=%d> G=%d, grid=%u, %zu B LDS", p.maxp, p.g, grid_for(b->n_envs), p.smem);
+    } else {
+        char step[320];
+        describe_train_plan(b, p.step, have, obs_dtype, start, step, sizeof(step));
+        snprintf(out, out_size, "%s + k_featurize<LAY_LDS=%s> grid=%u, %zu B LDS", step, p.feat.lay_lds ? "true" : "false", p.feat.grid,
+                 p.feat.smem);
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -1234,9 +1332,7 @@ int oc_multi_agent_step(const OcBatch* b, void* d_state, const uint8_t* d_action
     const TrainStep a = {b, p.n_obj, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
                          d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, reward_shaping_factor, d_shaped, d_done, d_obs, obs_dtype,
                          horizon, start, p.sa, ea, (hipStream_t)stream};
-    if (p.path == TrainPlan::GENERAL) return train_step_general(a);
-    if (p.path == TrainPlan::OBS) return train_step_obs(a, p);
-    return train_step_fused(a, p);
+    return launch_train_step(a, p);
 }
 
 int oc_multi_agent_plan(const OcBatch* b, int horizon, int with_obs, int obs_dtype, int use_phi, int event_sink, const OcStartSpec* start,
@@ -1254,6 +1350,55 @@ int oc_multi_agent_plan(const OcBatch* b, int horizon, int with_obs, int obs_dty
     const TrainPlan p = plan_train_step(b, have, obs_dtype, horizon, start);
     if (p.rc != OC_OK) return p.rc;
     describe_train_plan(b, p, have, obs_dtype, start, out, out_size);
+    return OC_OK;
+}
+
+int oc_multi_agent_step_featurize(const OcBatch* b, void* d_state, const uint8_t* d_actions, float* d_rewards, uint8_t* d_flags,
+                                  float* d_ep_returns, float* d_ep_returns_out, const uint8_t* d_plan_blob,
+                                  const uint32_t* d_plan_off, const uint8_t* d_phi_tables, double* d_phi_next, double* d_phi_cur,
+                                  const double* d_phi_start, double reward_shaping_factor, double* d_shaped, uint8_t* d_done,
+                                  void* d_obs, int obs_dtype, int horizon, const uint8_t* d_feat_plan_blob,
+                                  const uint32_t* d_feat_plan_off, float* d_features, int num_pots, uint32_t options,
+                                  const OcStartSpec* start, const OcEventSink* events, void* stream) {
+    if (options & ~(uint32_t)OC_OPT_ONE_KERNEL) return refuse("oc_multi_agent_step_featurize", "options other than OC_OPT_ONE_KERNEL");
+    if (!d_features)  // no features: the call is oc_multi_agent_step
+        return oc_multi_agent_step(b, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
+                                   d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, reward_shaping_factor, d_shaped, d_done, d_obs,
+                                   obs_dtype, horizon, start, events, stream);
+    const EvArgs ea = ev_args(events, nullptr, 1u);
+    const TrainArrays have = train_arrays_of(d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
+                                             d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, d_shaped, d_done, d_obs, ev_on(ea));
+    const TrainFeatPlan p = plan_train_step_featurize(b, have, d_feat_plan_blob && d_feat_plan_off, aligned16(d_features), obs_dtype, horizon,
+                                                      num_pots, options, start);
+    if (p.rc != OC_OK || p.path == TrainFeatPlan::NOTHING) return p.rc;
+    const TrainStep a = {b, p.step.n_obj, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
+                         d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, reward_shaping_factor, d_shaped, d_done, d_obs, obs_dtype,
+                         horizon, start, p.step.sa, ea, (hipStream_t)stream};
+    if (p.path == TrainFeatPlan::ONE_KERNEL) return train_step_feat(a, p, d_feat_plan_blob, d_feat_plan_off, d_features, num_pots);
+    if (int rc = launch_train_step(a, p.step)) return rc;
+    if (p.feat.lay_lds) launch_featurize<true>(p.feat, b, d_feat_plan_blob, d_feat_plan_off, d_state, d_features, num_pots, a.stream);
+    else launch_featurize<false>(p.feat, b, d_feat_plan_blob, d_feat_plan_off, d_state, d_features, num_pots, a.stream);
+    return check_launch("oc_multi_agent_step_featurize");
+}
+
+int oc_multi_agent_step_featurize_plan(const OcBatch* b, int horizon, int with_obs, int obs_dtype, int with_features, int num_pots,
+                                       uint32_t options, int use_phi, int event_sink, const OcStartSpec* start, char* out,
+                                       size_t out_size) {
+    if (!out || out_size == 0) return fail(OC_EINVAL, "oc_multi_agent_step_featurize_plan: no output buffer");
+    out[0] = 0;
+    if (options & ~(uint32_t)OC_OPT_ONE_KERNEL) return refuse("oc_multi_agent_step_featurize", "options other than OC_OPT_ONE_KERNEL");
+    if (!with_features) return oc_multi_agent_plan(b, horizon, with_obs, obs_dtype, use_phi, event_sink, start, out, out_size);
+    // the call VecOvercookedMultiAgent.step makes: every required array (aligned), the named optional ones
+    TrainArrays have = {};
+    have.state = have.actions = have.rewards = have.flags = have.shaped = have.shaped_aligned16 = have.done = true;
+    have.phi_tables = have.phi_rest = use_phi != 0;
+    have.ep_returns = have.ep_returns_out = true;
+    have.obs = with_obs != 0;
+    have.obs_aligned16 = true;
+    have.events = event_sink != 0;
+    const TrainFeatPlan p = plan_train_step_featurize(b, have, true, true, obs_dtype, horizon, num_pots, options, start);
+    if (p.rc != OC_OK) return p.rc;
+    describe_train_feat_plan(b, p, have, obs_dtype, start, out, out_size);
     return OC_OK;
 }
 

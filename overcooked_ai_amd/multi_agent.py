@@ -7,6 +7,9 @@ human_aware_rl/rllib/rllib.py:112-438) on top of the accelerated path.
 `bc` partners need a behaviour-cloning model, which is outside this package — their observation (`featurize_state`)
 is available through `observations("bc")`.
 
+With `obs="features"` the same call also returns featurize_state of the states the next step starts from (`obs="both"`: the
+lossless encoding and the features), through `oc_multi_agent_step_featurize` — one kernel for single-layout batches.
+
 `OvercookedMultiAgent` is the per-env, dict-keyed form RLlib-style training code holds (one `OvercookedEnv` underneath;
 agent ids "ppo_0" / "bc_1" redrawn every reset from the bc schedule, observations by agent kind, the same reward
 arithmetic) — the surface of the reference class without its RLlib base class or registry (those belong to the
@@ -172,11 +175,17 @@ class OvercookedMultiAgent:
 class VecOvercookedMultiAgent:
     """N two-agent training envs in HBM.  `step(actions)` takes uint8 [n_envs, 2] action indices (player order) and
     returns (obs, rewards, dones, infos) as device tensors; finished episodes restart inside the call, and `obs` of
-    those envs is the first observation of the new episode (the usual vector-env convention)."""
+    those envs is the first observation of the new episode (the usual vector-env convention).
+
+    obs: "ppo" — the lossless encoding [n_envs, 2, W, H, 26], written by the step call; "bc" — the step call gets no observation
+    array and step() returns observations("bc"), a second launch; "features" — featurize_state [n_envs, 2, 2*(num_pots*10+26)+4]
+    float32 written by the step call itself (oc_multi_agent_step_featurize) into a persistent buffer, with `num_pots` and
+    `counter_goals` as for VecOvercookedEnv.featurize; "both" — the pair (lossless, features) from the same call.  one_kernel:
+    take the single-kernel path of "features" whatever the batch size (`plan()` says what runs)."""
 
     def __init__(self, layouts, n_envs, horizon=400, reward_shaping_factor=0.0, reward_shaping_horizon=0, use_phi=True,
                  gamma=0.99, obs="ppo", obs_dtype=None, device="cuda", random_start_pos=False, rnd_obj_prob_thresh=0.0,
-                 **venv_kwargs):
+                 num_pots=2, counter_goals="none", one_kernel=False, **venv_kwargs):
         import torch
 
         from . import _lib
@@ -191,7 +200,10 @@ class VecOvercookedMultiAgent:
         self.n_envs, self.horizon, self.use_phi, self.gamma = v.n_envs, v.horizon, bool(use_phi), float(gamma)
         self._initial_reward_shaping_factor = self.reward_shaping_factor = reward_shaping_factor
         self.reward_shaping_horizon = reward_shaping_horizon
+        if obs not in ("ppo", "bc", "features", "both"):
+            raise ValueError("Unsupported observation kind {0}".format(obs))
         self.obs_kind = obs
+        self.num_pots, self.counter_goals, self.one_kernel = int(num_pots), counter_goals, bool(one_kernel)
         # start_state_fn = mdp.get_random_start_state_fn(random_start_pos, rnd_obj_prob_thresh) of the reference's
         # env_params (mdp.py:1307-1369): every episode, including the restarts inside step(), begins from a random state
         self.random_start_pos, self.rnd_obj_prob_thresh = bool(random_start_pos), float(rnd_obj_prob_thresh)
@@ -205,6 +217,7 @@ class VecOvercookedMultiAgent:
         self.phi_start = torch.zeros((len(v.table),), dtype=torch.float64, device=dev)
         self.ep_returns = torch.zeros((self.n_envs, 4), dtype=torch.float32, device=dev)
         self._obs = None
+        self._feat = None
         self._phi_args = None
         if self.use_phi:
             # phi of each layout's STANDARD start state (what a standard reset carries into phi_cur), from a probe batch of
@@ -220,14 +233,25 @@ class VecOvercookedMultiAgent:
                                           dtype=self.obs_dtype, device=self.venv.device)
         return self._obs
 
+    def _feat_buffer(self):
+        if self._feat is None:
+            self._feat = self._torch.empty((self.n_envs, 2, 2 * (self.num_pots * 10 + 26) + 4), dtype=self._torch.float32,
+                                           device=self.venv.device)
+        return self._feat
+
     def observations(self, kind=None):
         """Both agents' observations of the current states: "ppo" -> [n_envs, 2, W, H, 26] (lossless encoding),
-        "bc" -> [n_envs, 2, 96] (featurize_state)."""
+        "bc" -> [n_envs, 2, 96] (featurize_state), "features" -> [n_envs, 2, 2*(num_pots*10+26)+4] (featurize_state with this
+        env's num_pots and counter_goals, in its persistent buffer), "both" -> the pair (lossless, features)."""
         kind = kind or self.obs_kind
         if kind == "ppo":
             return self.venv.encode_lossless(self.obs_dtype, out=self._obs_buffer())
         if kind == "bc":
             return self.venv.featurize()
+        if kind == "features":
+            return self.venv.featurize(self.num_pots, self.counter_goals, out=self._feat_buffer())
+        if kind == "both":
+            return self.observations("ppo"), self.observations("features")
         raise ValueError("Unsupported agent type {0}".format(kind))
 
     def reset(self):
@@ -247,7 +271,7 @@ class VecOvercookedMultiAgent:
         code, OcStartSpec* or None — random starts: finished envs restart from drawn states in the same call —, OcEventSink* or
         None)."""
         v = self.venv
-        obs = self._obs_buffer() if self.obs_kind == "ppo" else None
+        obs = self._obs_buffer() if self.obs_kind in ("ppo", "both") else None
         code = {self._torch.uint8: self._lib.OBS_U8, self._torch.float32: self._lib.OBS_F32}[self.obs_dtype]
         return obs, code, v._start_spec(), v._event_sink() if v.event_counts is not None else None
 
@@ -259,13 +283,28 @@ class VecOvercookedMultiAgent:
         v = self.venv
         obs, code, start, sink = self._call_args()
         out = ctypes.create_string_buffer(320)
+        if self._with_features:  # (oc_multi_agent_step_featurize_plan's words)
+            rc = v.lib.oc_multi_agent_step_featurize_plan(v._bref, self.horizon, int(obs is not None), code, 1, self.num_pots,
+                                                          self._feat_options, int(self.use_phi), int(sink is not None), start, out,
+                                                          len(out))
+            self._lib.check(rc, "oc_multi_agent_step_featurize_plan")
+            return out.value.decode()
         rc = v.lib.oc_multi_agent_plan(v._bref, self.horizon, int(obs is not None), code, int(self.use_phi), int(sink is not None),
                                        start, out, len(out))
         self._lib.check(rc, "oc_multi_agent_plan")
         return out.value.decode()
 
+    @property
+    def _with_features(self):
+        return self.obs_kind in ("features", "both")
+
+    @property
+    def _feat_options(self):
+        return self._lib.OPT_ONE_KERNEL if self.one_kernel else 0
+
     def step(self, actions):
-        """One batched training step, enqueued by a single C call (oc_multi_agent_step)."""
+        """One batched training step, enqueued by a single C call (oc_multi_agent_step; with obs = "features" or "both"
+        oc_multi_agent_step_featurize, which also writes the feature buffer)."""
         v, torch = self.venv, self._torch
         if actions.dtype != torch.uint8 or actions.shape != (self.n_envs, 2) or not actions.is_contiguous() \
                 or actions.device != v.state.device:
@@ -279,18 +318,29 @@ class VecOvercookedMultiAgent:
             plan, off, tables = self._phi_args
         else:
             plan = off = tables = None
-        rc = v._launch(v.lib.oc_multi_agent_step, v._bref, v._state_ptr, actions.data_ptr(), v._rewards_ptr, v._flags_ptr,
-                       v._ep_ptr, self.ep_returns.data_ptr(), plan, off, tables, self.phi_next.data_ptr(),
-                       self.phi_cur.data_ptr(), self.phi_start.data_ptr(), float(self.reward_shaping_factor),
-                       self.shaped.data_ptr(), self.done.data_ptr(), obs.data_ptr() if obs is not None else None, code,
-                       self.horizon, start, sink)
-        self._lib.check(rc, "oc_multi_agent_step")
+        args = (v._bref, v._state_ptr, actions.data_ptr(), v._rewards_ptr, v._flags_ptr, v._ep_ptr, self.ep_returns.data_ptr(), plan, off,
+                tables, self.phi_next.data_ptr(), self.phi_cur.data_ptr(), self.phi_start.data_ptr(), float(self.reward_shaping_factor),
+                self.shaped.data_ptr(), self.done.data_ptr(), obs.data_ptr() if obs is not None else None, code, self.horizon)
+        feat = None
+        if self._with_features:
+            feat = self._feat_buffer()
+            fblob, foffs = v._plan(self.counter_goals)
+            rc = v._launch(v.lib.oc_multi_agent_step_featurize, *args, fblob.data_ptr(), foffs.data_ptr(), feat.data_ptr(), self.num_pots,
+                           self._feat_options, start, sink)
+            self._lib.check(rc, "oc_multi_agent_step_featurize")
+        else:
+            rc = v._launch(v.lib.oc_multi_agent_step, *args, start, sink)
+            self._lib.check(rc, "oc_multi_agent_step")
         v._advance(1)
         infos = {"sparse_r_by_agent": v.rewards[:, 0:2], "shaped_r_by_agent": v.rewards[:, 2:4], "flags": v.flags,
                  "ep_returns": self.ep_returns}  # episode totals so far; final where done (the reset cleared the live ones)
         if self.use_phi:
             infos["phi_s_prime"] = self.phi_next
-        return (obs if obs is not None else self.observations()), self.shaped, self.done, infos
+        if feat is not None:
+            out = feat if obs is None else (obs, feat)
+        else:
+            out = obs if obs is not None else self.observations()
+        return out, self.shaped, self.done, infos
 
     def anneal_reward_shaping_factor(self, timesteps):
         self.reward_shaping_factor = linear_anneal(self._initial_reward_shaping_factor, timesteps,
