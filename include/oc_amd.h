@@ -260,10 +260,15 @@ int oc_state_planes(int width, int height);
  * done/bookkeeping (env.py:244-274, 321-325, 382-392).
  *   d_state_in/out [oc_state_planes * n_envs] 16-byte words; may alias (in-place step)
  *   d_actions      [n_envs][2] action indices 0..5 (player 0, player 1)
- *   d_rewards      [n_envs][4] float: sparse_reward_by_agent[0..1], shaped_reward_by_agent[0..1]
- *   d_flags        [n_envs] OC_F_* bits
+ *   d_rewards      [n_envs][4] float: sparse_reward_by_agent[0..1], shaped_reward_by_agent[0..1]; 16-byte aligned (every
+ *                  kernel writes a row as one 16-byte store)
+ *   d_flags        [n_envs] OC_F_* bits; any address (written a byte at a time)
  *   d_ep_returns   [n_envs][4] float running sums of d_rewards over the episode
- *                  (game_stats cumulative_*_rewards_by_agent, env.py:387-392), or NULL
+ *                  (game_stats cumulative_*_rewards_by_agent, env.py:387-392); 16-byte aligned, or NULL
+ * A d_rewards or d_ep_returns that is not 16-byte aligned is OC_EINVAL, here and in every entry point below that takes one
+ * (oc_step_many, oc_rollout_random, oc_rollout_record, oc_rollout_record_ex, oc_step_encode, oc_rollout_encode, oc_rollout_featurize,
+ * oc_multi_agent_step with its d_ep_returns_out, oc_multi_agent_step_featurize, oc_step_server_open, oc_step_server_play), before
+ * any device call.
  *   d_events       [n_envs] u64 event_infos of this step (EVENT_TYPES, mdp.py:1027-1058): bit 2*k + p is
  *                  event_infos[EVENT_TYPES[k]][p]; or NULL (shorthand for an OcEventSink with only d_events)
  *   events         per-episode event counters / masks (OcEventSink), or NULL
@@ -282,6 +287,7 @@ int oc_step(const OcBatch* batch, const void* d_state_in, void* d_state_out, con
  * d_actions[k][n_envs][2] and writes d_rewards[k][n_envs][4], d_flags[k][n_envs]; the envs stay on chip between the
  * steps (replaying a fixed joint plan or a pre-sampled action tensor: OvercookedEnv.execute_plan, env.py:334-345;
  * AgentEvaluator._check_trajectories_dynamics, benchmarking.py:366).  Results are those of n_steps oc_step calls.
+ * d_rewards and d_ep_returns (or NULL) 16-byte aligned, d_flags at any address, as for oc_step.
  */
 int oc_step_many(const OcBatch* batch, void* d_state, const uint8_t* d_actions, float* d_rewards, uint8_t* d_flags,
                  float* d_ep_returns, int n_steps, int horizon, uint32_t options, const OcStartSpec* start,
@@ -302,6 +308,8 @@ int oc_step_many(const OcBatch* batch, void* d_state, const uint8_t* d_actions, 
  * step grid (t0 or n_steps not a multiple of 8) is split inside the call — head and tail steps through the one-wavefront kernels —, a
  * ragged batch takes the one-wavefront kernels altogether (oc_rollout_plan says which instance a call takes).
  *   d_rewards  [n_steps][n_envs][4] or NULL;  d_flags [n_steps][n_envs] or NULL ([n_steps / 8][n_envs][8] with OC_OPT_FLAGS_TILED8)
+ *              alignment: d_rewards and d_ep_returns 16 bytes (rows written as 16-byte stores: OC_EINVAL otherwise); d_flags any
+ *              address ([step][env] flags are written a byte at a time), 8 bytes with OC_OPT_FLAGS_TILED8 (tiles are 8-byte stores)
  *   env_offset global index of local env 0 (multi-GPU shards draw disjoint streams)
  *   t0         global step index of the first fused step
  */
@@ -320,7 +328,7 @@ int oc_rollout_random(const OcBatch* batch, void* d_state, float* d_rewards, uin
  *                  state, after the previous step's restart (slice 0 = d_state on entry; the state after the last step is d_state
  *                  on return); each slice is a packed-state array of its own (oc_encode_lossless, oc_featurize, ...); 16-byte
  *                  aligned, or NULL.  Not both NULL.
- *   d_rewards, d_flags: optional, as in oc_rollout_random.  recorded bytes per env-step: 16 per plane + 2 + 16 + 1 — 67 on grids of
+ *   d_rewards, d_flags: optional, as in oc_rollout_random (d_rewards and d_ep_returns 16-byte aligned, d_flags at any address).  recorded bytes per env-step: 16 per plane + 2 + 16 + 1 — 67 on grids of
  *                  17..32 cells (cramped_room: 48 state, 2 actions, 16 rewards, 1 flags), 83 on 33..48 (asymmetric_advantages).
  * Runs the one-wavefront arithmetic-movement kernel (k_rollout4, MODE 0) with recording stores.  options: OC_OPT_AUTO_RESET;
  * OC_OPT_ONE_WAVEFRONT is accepted and has no effect; any other bit (OC_OPT_FLAGS_TILED8, OC_OPT_LANE_PAIR,
@@ -356,7 +364,7 @@ typedef struct OcRecordSink {
  * Runs the one-wavefront arithmetic-movement kernel (k_rollout4, MODE 0) with recording stores, and with the event log when
  * `events` names masks or counters.  options: OC_OPT_AUTO_RESET; OC_OPT_ONE_WAVEFRONT is accepted and has no effect.  OC_EINVAL,
  * before any device call: any other option bit, a table without OC_BATCH_TWO_PLAYERS, rec NULL or all three of its arrays NULL,
- * a misaligned array, and the start-spec errors of oc_rollout_record (but for regen_count, which is accepted).
+ * a misaligned array (rec's, d_rewards or d_ep_returns: 16 bytes, as in oc_rollout_random), and the start-spec errors of oc_rollout_record (but for regen_count, which is accepted).
  */
 int oc_rollout_record_ex(const OcBatch* batch, void* d_state, const OcRecordSink* rec, float* d_rewards, uint8_t* d_flags,
                          float* d_ep_returns, int horizon, uint32_t options, uint64_t seed, int64_t env_offset, int64_t t0,
@@ -392,6 +400,7 @@ int oc_step_encode(const OcBatch* batch, void* d_state, const uint8_t* d_actions
  *   d_actions  NULL: the uniform random policy, the Philox stream of oc_rollout_random (seed, env_offset, t0);
  *              else [n_steps][n_envs][2] action indices as for oc_step_many (illegal: flagged, env untouched)
  *   d_rewards  [n_steps][n_envs][4] / d_flags [n_steps][n_envs] (may be NULL with the random policy)
+ *              d_rewards and d_ep_returns 16-byte aligned, d_flags at any address (as for oc_step; oc_step_encode too)
  *   d_obs      observation of step k at (char*)d_obs + k * obs_step_stride: [n_envs][2][W][H][26] of obs_dtype, the state
  *              the NEXT step starts from (after an auto-reset: the start state), exactly what oc_step_encode emits;
  *              obs_step_stride in bytes, a multiple of 16; 0 = every step overwrites the same observation
@@ -441,6 +450,7 @@ int oc_featurize(const OcBatch* batch, const uint8_t* d_plan_blob, const uint32_
  *               else [n_steps][n_envs][2] action indices as for oc_step_many (illegal: flagged OC_F_BAD_ACTION, the env
  *               untouched, its features recomputed unchanged); caller actions need d_rewards and d_flags
  *   d_rewards   [n_steps][n_envs][4] / d_flags [n_steps][n_envs] (may be NULL with the random policy)
+ *               d_rewards and d_ep_returns 16-byte aligned, d_flags at any address (as for oc_step)
  *   d_features  features of step k at (char*)d_features + k * feat_step_stride: [n_envs][2][2 * (num_pots * 10 + 26) + 4]
  *               float32 of the state the NEXT step starts from (after an auto-reset: the start state), exactly what oc_featurize
  *               of d_state after step k gives; feat_step_stride in bytes, a multiple of 16; 0 = every step overwrites one buffer
@@ -479,7 +489,8 @@ int oc_shape_rewards(const OcBatch* batch, const float* d_rewards, const uint8_t
  * Replaces OvercookedMultiAgent.step (human_aware_rl/rllib/rllib.py:293-342) for a batch: oc_step (no auto-reset) ->
  * oc_potential on s' (when d_phi_tables != NULL: use_phi) -> oc_shape_rewards -> copy of the episode returns ->
  * oc_reset of the finished envs (mask = d_done) -> oc_encode_lossless of the states the next step starts from
- * (when d_obs != NULL).  Arguments as in those entry points; d_done is required.  Two-player tables with at most two
+ * (when d_obs != NULL).  Arguments as in those entry points (d_rewards, d_ep_returns and d_ep_returns_out 16-byte aligned: float4
+ * rows; d_flags and d_done at any address; OC_EINVAL otherwise); d_done is required.  Two-player tables with at most two
  * pots run everything before the encoding as one kernel (k_train_step) with identical results.  With `start`, finished
  * envs restart from drawn start states and d_phi_cur receives the potential of those.
  * ABI 5, round 5: with d_obs, ONE layout on a grid of at most 64 cells, no event sink and a batch that gives at least half
@@ -626,6 +637,7 @@ int oc_mailbox_close(OcMailbox* mailbox);
  *                        receives the client kernel's duration (HIP events on `stream`).
  *   oc_step_server_steps steps served so far (the host's count; exact after _play / _sync)
  * One caller at a time: the entry points of a server are not thread-safe, and two clients must not play on it concurrently.
+ * d_ep_returns (oc_step_server_open; or NULL) and d_rewards (oc_step_server_play) are 16-byte aligned, d_flags sits at any address.
  * The resident kernel reads d_state / d_ep_returns on a stream of its own whenever it is (re)launched — at _open, and at a _play /
  * _resume that finds it gone: work of the caller's on those arrays must be complete by then (_play waits for `stream` before a
  * relaunch; before _open and _resume the caller synchronises its stream itself).

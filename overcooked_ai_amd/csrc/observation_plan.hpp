@@ -128,6 +128,7 @@ inline bool rollout_encode_fast(const OcBatch* b) { return (b->batch_flags & OC_
 struct RolloutEncodeArrays {
     bool state, actions, rewards, flags, obs;
     bool obs_aligned16;  // d_obs and obs_step_stride are multiples of 16 bytes
+    bool rewards_aligned16 = true, ep_returns_aligned16 = true;
 };
 struct RolloutEncodePlan {
     int rc = OC_OK;  // the call is refused with this code (the message: oc_last_error)
@@ -151,6 +152,7 @@ RolloutEncodePlan plan_rollout_encode(const OcBatch* b, const RolloutEncodeArray
     if (!have.state || !have.obs) return refused(refuse(who, "NULL state / observation pointer"));
     if (!obs_dtype_ok(obs_dtype)) return refused(refuse(who, "bad obs_dtype"));
     if (!have.obs_aligned16) return refused(refuse(who, "d_obs and obs_step_stride must be multiples of 16 bytes"));
+    if (int rc = check_quads(who, have.rewards_aligned16, have.ep_returns_aligned16)) return refused(rc);
     if (int rc = check_horizon(who, horizon)) return refused(rc);
     if (n_steps < 0 || n_steps > (1 << 30)) return refused(refuse(who, "n_steps must be in 0..2^30"));
     if (options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_KERNEL))
@@ -233,6 +235,7 @@ inline int64_t rollout_featurize_fill(int64_t dflt) {
 struct RolloutFeaturizeArrays {
     bool plan, state, actions, rewards, flags, features;  // plan: the blob and its offsets
     bool features_aligned16;  // d_features and feat_step_stride are multiples of 16 bytes
+    bool rewards_aligned16 = true, ep_returns_aligned16 = true;
 };
 struct RolloutFeaturizePlan {
     int rc = OC_OK;  // the call is refused with this code (the message: oc_last_error)
@@ -254,6 +257,7 @@ RolloutFeaturizePlan plan_rollout_featurize(const OcBatch* b, const RolloutFeatu
     if (num_pots < 0 || num_pots > 4) return refused(refuse(who, "num_pots must be in 0..4"));
     if (!(b->batch_flags & OC_BATCH_TWO_PLAYERS)) return refused(refuse(who, "needs 2-player layouts"));
     if (!have.features_aligned16) return refused(refuse(who, "d_features and feat_step_stride must be multiples of 16 bytes"));
+    if (int rc = check_quads(who, have.rewards_aligned16, have.ep_returns_aligned16)) return refused(rc);
     if (int rc = check_horizon(who, horizon)) return refused(rc);
     if (n_steps < 0 || n_steps > (1 << 30)) return refused(refuse(who, "n_steps must be in 0..2^30"));
     if (options & ~(uint32_t)(OC_OPT_AUTO_RESET | OC_OPT_ONE_KERNEL))

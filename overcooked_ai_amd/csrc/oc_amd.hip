@@ -151,6 +151,11 @@ int check_start(const char* who, const OcStartSpec* sp, StartArgs* sa, const OcB
 }
 inline bool obs_dtype_ok(int obs_dtype) { return obs_dtype == OC_OBS_U8 || obs_dtype == OC_OBS_F32; }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// d_rewards and d_ep_returns (either may be NULL where the entry point allows it): every kernel writes them as float4 rows
+int check_quads(const char* who, bool rewards_aligned16, bool ep_returns_aligned16) {
+    if (!rewards_aligned16) return refuse(who, "d_rewards must be 16-byte aligned");
+    return ep_returns_aligned16 ? OC_OK : refuse(who, "d_ep_returns must be 16-byte aligned");
+}
 int check_obs(const char* who, int obs_dtype, bool obs_aligned16) {
     if (!obs_dtype_ok(obs_dtype)) return refuse(who, "bad obs_dtype");
     return obs_aligned16 ? OC_OK : refuse(who, "d_obs must be 16-byte aligned");
@@ -324,6 +329,7 @@ void launch_step(const OcBatch* b, int n_obj, const void* d_state_in, void* d_st
 struct StepArrays {
     bool required;             // the state(s), actions, rewards and flags of the entry point (the server: the state)
     bool ev_masks, ev_counts;  // per-step event masks (oc_step's d_events or the sink's) / per-episode counters
+    bool rewards_aligned16 = true, ep_returns_aligned16 = true;  // (the server: d_ep_returns; its rewards come with oc_step_server_play)
 };
 struct StepPlan {
     int rc = OC_OK;  // the call is refused with this code (the message: oc_last_error)
@@ -356,6 +362,7 @@ StepPlan plan_step(const OcBatch* b, int entry, const StepArrays& have, int hori
     }
     if (!have.required) return refused(refuse(who, entry == ENTRY_SERVER ? "NULL state pointer" : "NULL state/actions/rewards/flags pointer"));
     if (int rc = check_horizon(who, horizon)) return refused(rc);
+    if (int rc = check_quads(who, have.rewards_aligned16, have.ep_returns_aligned16)) return refused(rc);
     if (entry == ENTRY_SERVER) {
         if (options & ~(uint32_t)OC_OPT_AUTO_RESET) return refused(refuse(who, "the only option is OC_OPT_AUTO_RESET"));
         if (b->n_envs < 1) return refused(refuse(who, "no envs"));
@@ -396,6 +403,7 @@ struct RolloutChoice {
 struct RolloutArrays {
     bool state, rewards, flags, flags_aligned8;
     bool ev_masks, ev_counts;  // the event sink's per-step masks / per-episode counters
+    bool rewards_aligned16 = true, ep_returns_aligned16 = true;
 };
 inline bool ev_on(const RolloutArrays& have) { return have.ev_masks || have.ev_counts; }
 
@@ -571,6 +579,7 @@ int rollout_record(bool ex, const OcBatch* b, void* d_state, const oc_detail::Re
     if (!d_state) return refuse(who, "NULL state pointer");
     if (int rc = check_horizon(who, horizon)) return rc;
     if (n_steps < 0 || n_steps > (1 << 30)) return refuse(who, "n_steps must be in 0..2^30");
+    if (int rc = check_quads(who, aligned16(d_rewards), aligned16(d_ep_returns))) return rc;
     if (b->n_envs == 0 || n_steps == 0) return OC_OK;
     const EvArgs ea = ev_args(events, nullptr);
     const RolloutArrays have = {true, d_rewards != nullptr, d_flags != nullptr, false, ea.events != nullptr, ea.counts != nullptr};
@@ -602,6 +611,7 @@ RolloutPlan plan_rollout(const OcBatch* b, const RolloutArrays& have, int horizo
     if (!have.state) return refused(refuse(who, "NULL state pointer"));
     if (int rc = check_horizon(who, horizon)) return refused(rc);
     if (n_steps < 0 || n_steps > (1 << 30)) return refused(refuse(who, "n_steps must be in 0..2^30"));
+    if (int rc = check_quads(who, have.rewards_aligned16, have.ep_returns_aligned16)) return refused(rc);
     if (options & OC_OPT_FLAGS_TILED8) {  // the launch-shape half of the option's conditions (the batch half: choose_launch)
         if (!have.rewards || !have.flags || !have.flags_aligned8)
             return refused(refuse(who, "OC_OPT_FLAGS_TILED8 needs d_rewards and an 8-byte aligned d_flags"));
@@ -769,7 +779,8 @@ int oc_step(const OcBatch* b, const void* d_state_in, void* d_state_out, const u
             uint8_t* d_flags, float* d_ep_returns, uint64_t* d_events, int horizon, uint32_t options,
             const OcStartSpec* start, const OcEventSink* events, void* stream) {
     const EvArgs ea = ev_args(events, d_events);
-    const StepArrays have = {d_state_in && d_state_out && d_actions && d_rewards && d_flags, ea.events != nullptr, ea.counts != nullptr};
+    const StepArrays have = {d_state_in && d_state_out && d_actions && d_rewards && d_flags, ea.events != nullptr, ea.counts != nullptr,
+                             aligned16(d_rewards), aligned16(d_ep_returns)};
     const StepPlan p = plan_step(b, ENTRY_STEP, have, horizon, options, 1, start);
     if (p.rc != OC_OK || p.ch.family == StepChoice::NOTHING) return p.rc;
     if (int rc = launch_step_from(p.ch, b, p.n_obj, d_state_in, d_state_out, d_actions, d_rewards, d_flags, d_ep_returns, horizon, options,
@@ -782,7 +793,8 @@ int oc_step_many(const OcBatch* b, void* d_state, const uint8_t* d_actions, floa
                  float* d_ep_returns, int n_steps, int horizon, uint32_t options, const OcStartSpec* start,
                  const OcEventSink* events, void* stream) {
     const EvArgs ea = ev_args(events, nullptr);
-    const StepArrays have = {d_state && d_actions && d_rewards && d_flags, ea.events != nullptr, ea.counts != nullptr};
+    const StepArrays have = {d_state && d_actions && d_rewards && d_flags, ea.events != nullptr, ea.counts != nullptr,
+                             aligned16(d_rewards), aligned16(d_ep_returns)};
     const StepPlan p = plan_step(b, ENTRY_STEP_MANY, have, horizon, options, n_steps, start);
     if (p.rc != OC_OK || p.ch.family == StepChoice::NOTHING) return p.rc;
     if (!p.step_by_step) {  // all K transitions in one launch, the envs stay on chip in between
@@ -825,7 +837,7 @@ int oc_rollout_random(const OcBatch* b, void* d_state, float* d_rewards, uint8_t
                       const OcStartSpec* start, const OcEventSink* events, void* stream) {
     const EvArgs ea = ev_args(events, nullptr);
     const RolloutArrays have = {d_state != nullptr, d_rewards != nullptr, d_flags != nullptr, ((uintptr_t)d_flags & 7u) == 0,
-                                ea.events != nullptr, ea.counts != nullptr};
+                                ea.events != nullptr, ea.counts != nullptr, aligned16(d_rewards), aligned16(d_ep_returns)};
     const RolloutPlan p = plan_rollout(b, have, horizon, options, env_offset, t0, n_steps, start);
     if (p.rc != OC_OK || p.family == RolloutPlan::NOTHING) return p.rc;
     const oc_detail::Rollout4Call c = {b, p.n_obj, d_state, d_rewards, d_flags, d_ep_returns, horizon, options, seed,
@@ -995,6 +1007,7 @@ struct TrainArrays {
     bool state, actions, rewards, flags, shaped, shaped_aligned16, done;
     bool phi_tables, phi_rest;  // use_phi: the phi tables / the plan tables and the three phi buffers
     bool ep_returns, ep_returns_out;  // (no choice depends on them: read by describe_train_plan only, for the sequence's copy)
+    bool quads_aligned16 = true;      // d_rewards, d_ep_returns and d_ep_returns_out
     bool obs, obs_aligned16;
     bool events;  // an event sink with counters or masks
 };
@@ -1060,6 +1073,7 @@ TrainPlan plan_train_step(const OcBatch* b, const TrainArrays& have, int obs_dty
     if (fused && have.phi_tables && !have.phi_rest) return refused(refuse(who, "use_phi needs the plan tables and the three phi buffers"));
     if (int rc = check_horizon(who, horizon)) return refused(rc);
     if (fused && !have.shaped_aligned16) return refused(refuse(who, "d_shaped must be 16-byte aligned"));
+    if (!have.quads_aligned16) return refused(refuse(who, "d_rewards, d_ep_returns and d_ep_returns_out must be 16-byte aligned"));
     if (!fused) return p;
     p.path = TrainPlan::FUSED;
     p.uniform = b->n_layouts == 1;
@@ -1192,6 +1206,7 @@ TrainArrays train_arrays_of(const void* d_state, const void* d_actions, const vo
     have.phi_tables = d_phi_tables != nullptr;
     have.phi_rest = d_plan_blob && d_plan_off && d_phi_next && d_phi_cur && d_phi_start;
     have.ep_returns = d_ep_returns != nullptr; have.ep_returns_out = d_ep_returns_out != nullptr;
+    have.quads_aligned16 = aligned16(d_rewards) && aligned16(d_ep_returns) && aligned16(d_ep_returns_out);
     have.obs = d_obs != nullptr; have.obs_aligned16 = aligned16(d_obs);
     have.events = events;
     return have;
@@ -1607,6 +1622,7 @@ int oc_step_encode(const OcBatch* b, void* d_state, const uint8_t* d_actions, fl
     if (int rc = check_batch(b, &n_obj)) return rc;
     if (!d_state || !d_actions || !d_rewards || !d_flags || !d_obs) return fail(OC_EINVAL, "oc_step_encode: NULL pointer");
     if (int rc = check_obs("oc_step_encode", obs_dtype, aligned16(d_obs))) return rc;
+    if (int rc = check_quads("oc_step_encode", aligned16(d_rewards), aligned16(d_ep_returns))) return rc;
     if (int rc = check_horizon("oc_step_encode", horizon)) return rc;
     StartArgs sa;
     if (int rc = check_start("oc_step_encode", start, &sa, b)) return rc;
@@ -1625,7 +1641,8 @@ int oc_rollout_encode(const OcBatch* b, void* d_state, const uint8_t* d_actions,
                       uint32_t options, uint64_t seed, int64_t env_offset, int64_t t0, int n_steps,
                       const OcStartSpec* start, void* stream) {
     const RolloutEncodeArrays have = {d_state != nullptr, d_actions != nullptr, d_rewards != nullptr, d_flags != nullptr, d_obs != nullptr,
-                                      aligned16(d_obs) && obs_step_stride >= 0 && (obs_step_stride & 15) == 0};
+                                      aligned16(d_obs) && obs_step_stride >= 0 && (obs_step_stride & 15) == 0, aligned16(d_rewards),
+                                      aligned16(d_ep_returns)};
     const RolloutEncodePlan p = plan_rollout_encode(b, have, obs_dtype, horizon, options, env_offset, n_steps, start, rollout_encode_lds(b, obs_dtype));
     if (p.rc != OC_OK || p.path == RolloutEncodePlan::NOTHING) return p.rc;
     const RolloutEncodeCall c = {b, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_obs, obs_dtype, obs_step_stride, horizon,
@@ -1663,7 +1680,8 @@ int oc_rollout_featurize(const OcBatch* b, const uint8_t* d_plan_blob, const uin
                          int64_t t0, int n_steps, const OcStartSpec* start, void* stream) {
     const RolloutFeaturizeArrays have = {d_plan_blob && d_plan_off, d_state != nullptr, d_actions != nullptr, d_rewards != nullptr,
                                          d_flags != nullptr, d_features != nullptr,
-                                         aligned16(d_features) && feat_step_stride >= 0 && (feat_step_stride & 15) == 0};
+                                         aligned16(d_features) && feat_step_stride >= 0 && (feat_step_stride & 15) == 0, aligned16(d_rewards),
+                                         aligned16(d_ep_returns)};
     const RolloutFeaturizePlan p = plan_rollout_featurize(b, have, num_pots, horizon, options, env_offset, n_steps, start);
     if (p.rc != OC_OK || p.path == RolloutFeaturizePlan::NOTHING) return p.rc;
     const RolloutFeaturizeCall c = {b, d_plan_blob, d_plan_off, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_features,
@@ -1855,7 +1873,7 @@ int oc_step_server_open(const OcBatch* b, void* d_state, float* d_ep_returns, in
                         const OcStartSpec* start, double idle_ms, double life_s, OcStepServer** out) {
     if (!out) return fail(OC_EINVAL, "oc_step_server_open: NULL result pointer");
     *out = nullptr;
-    const StepPlan p = plan_step(b, ENTRY_SERVER, StepArrays{d_state != nullptr, false, false}, horizon, options, 1, start);
+    const StepPlan p = plan_step(b, ENTRY_SERVER, StepArrays{d_state != nullptr, false, false, true, aligned16(d_ep_returns)}, horizon, options, 1, start);
     if (p.rc != OC_OK) return p.rc;
     const int n_obj = p.n_obj;
     const StartArgs& sa = p.sa;
@@ -1917,6 +1935,7 @@ int oc_step_server_play(OcStepServer* m, const uint8_t* d_actions, float* d_rewa
     if (!m) return fail(OC_EINVAL, "oc_step_server_play: NULL server");
     if (!d_actions || !d_rewards || !d_flags) return fail(OC_EINVAL, "oc_step_server_play: NULL actions/rewards/flags pointer");
     if (n_steps < 0 || n_steps > (1 << 24)) return fail(OC_EINVAL, "oc_step_server_play: n_steps must be in 0..2^24");
+    if (!aligned16(d_rewards)) return refuse("oc_step_server_play", "d_rewards must be 16-byte aligned");
     if (elapsed_ms) *elapsed_ms = 0.f;
     if (n_steps == 0) return OC_OK;
     SvDevice dev(m->device);

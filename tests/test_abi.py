@@ -197,6 +197,63 @@ def test_argument_validation_without_gpu():
     assert L.oc_output_stores_only(64, 8, 4096, None, 0x40, None) == -1 and L.oc_output_stores_only(0, 8, 4096, 4096, 0x40, None) == 0
 
 
+def test_reward_and_return_arrays_must_be_16_byte_aligned():
+    """include/oc_amd.h: d_rewards and d_ep_returns (the training step's d_ep_returns_out too) are written as float4 rows, so every
+    entry point that takes them refuses one that is not 16-byte aligned — by name, on the host, before the empty-batch exit (a lost
+    check would show as OC_OK here: the batch has no envs).  Flat d_flags are written a byte at a time: any address is accepted."""
+    from overcooked_ai_amd import _lib
+
+    L = _lib.load()
+    e = _lib.OcBatch(d_layouts=4096, d_layout_id=None, n_envs=0, n_layouts=1, width=5, height=4, max_pots=1,
+                     batch_flags=_lib.BATCH_TWO_PLAYERS | _lib.BATCH_NEW_DYNAMICS)
+    er, P = ctypes.byref(e), 4096
+    rec = _lib.OcRecordSink(d_actions=P, d_states=P, d_layout_ids=None)
+    server = ctypes.c_void_p()
+
+    def calls(rew, ep, fl=P):
+        return {
+            "oc_step": lambda: L.oc_step(er, P, P, P, rew, fl, ep, None, 400, 0, None, None, None),
+            "oc_step_many": lambda: L.oc_step_many(er, P, P, rew, fl, ep, 3, 400, 0, None, None, None),
+            "oc_rollout_random": lambda: L.oc_rollout_random(er, P, rew, fl, ep, 400, 1, 0, 0, 0, 8, None, None, None),
+            "oc_rollout_record": lambda: L.oc_rollout_record(er, P, P, P, rew, fl, ep, 400, 1, 0, 0, 0, 8, None, None),
+            "oc_rollout_record_ex": lambda: L.oc_rollout_record_ex(er, P, ctypes.byref(rec), rew, fl, ep, 400, 1, 0, 0, 0, 8, None, None,
+                                                                   None),
+            "oc_step_encode": lambda: L.oc_step_encode(er, P, P, rew, fl, ep, P, 0, 400, 1, None, None),
+            "oc_rollout_encode": lambda: L.oc_rollout_encode(er, P, None, rew, fl, ep, P, 0, 0, 400, 1, 0, 0, 0, 3, None, None),
+            "oc_rollout_featurize": lambda: L.oc_rollout_featurize(er, P, P, P, None, rew, fl, ep, P, 0, 2, 400, 1, 0, 0, 0, 3, None, None),
+        }
+
+    for off in (4, 8, 12):
+        for name, call in calls(P + off, P).items():
+            assert call() == -1, (name, off)
+            assert L.oc_last_error().decode() == name + ": d_rewards must be 16-byte aligned", (name, off)
+        for name, call in calls(P, P + off).items():
+            assert call() == -1, (name, off)
+            assert L.oc_last_error().decode() == name + ": d_ep_returns must be 16-byte aligned", (name, off)
+        assert L.oc_step_server_open(er, P, P + off, 400, 1, None, 0.0, 0.0, ctypes.byref(server)) == -1
+        assert L.oc_last_error().decode() == "oc_step_server_open: d_ep_returns must be 16-byte aligned"
+        # the training step: one message for its three float4 arrays; with more than two pots (the sequence of entry points) as well
+        for pots in (1, 3):
+            e.max_pots = pots
+            for rew, ep, ep_out in ((P + off, P, P), (P, P + off, P), (P, P, P + off)):
+                assert L.oc_multi_agent_step(er, P, P, rew, P, ep, ep_out, None, None, None, None, None, None, 1.0, P, P, None, 0, 400,
+                                             None, None, None) == -1, (pots, off)
+                assert L.oc_last_error().decode() == "oc_multi_agent_step: d_rewards, d_ep_returns and d_ep_returns_out must be 16-byte aligned"
+                assert L.oc_multi_agent_step_featurize(er, P, P, rew, P, ep, ep_out, None, None, None, None, None, None, 1.0, P, P, None, 0,
+                                                       400, P, P, P, 2, 0, None, None, None) == -1, (pots, off)
+                assert L.oc_last_error().decode().startswith("oc_multi_agent_step_featurize: d_rewards, d_ep_returns and d_ep_returns_out")
+        e.max_pots = 1
+    # aligned arrays, NULL returns, and [step][env] flags at an odd address: accepted (no envs: nothing to launch)
+    for ep in (P, None):
+        for name, call in calls(P + 16, ep, fl=P + 3).items():
+            assert call() == 0, (name, L.oc_last_error())
+    assert L.oc_multi_agent_step(er, P, P, P + 16, P + 3, None, None, None, None, None, None, None, None, 1.0, P, P + 1, None, 0, 400, None,
+                                 None, None) == 0, L.oc_last_error()
+    # (tiled flags keep their 8-byte rule)
+    assert L.oc_rollout_random(er, P, P, P + 4, None, 400, 0x41, 0, 0, 0, 16, None, None, None) == -1
+    assert b"8-byte aligned" in L.oc_last_error()
+
+
 def test_product_never_imports_the_oracle():
     """The oracle is test infrastructure: nothing under overcooked_ai_amd/ may reference it."""
     pkg = os.path.join(ROOT, "overcooked_ai_amd")

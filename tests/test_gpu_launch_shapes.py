@@ -4,7 +4,8 @@ configs[3] / configs[4] put on EACH of 8 GPUs (65 536 and 131 072 envs per GPU; 
 global env offset of an inner rank), and every instance `oc_rollout_random` can launch (tests/rollout_cases.py), compared with
 the C oracle (pinned to the reference by
 tests/test_oracle_golden.py): every reward quad and flag byte of every env-step, the final packed states and the
-episode returns, bit for bit.  The oracle runs in 400-step chunks to bound host memory."""
+episode returns, bit for bit.  The oracle runs in 400-step chunks to bound host memory.  Every rewards, flags and event-mask array
+of a rollout starts as sentinels between guard rows, off the base of its allocation (gpu_support.RolloutOutputs)."""
 import numpy as np
 import pytest
 
@@ -16,7 +17,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from case_support import EventCounts, new_oracle as _oracle  # noqa: E402
-from gpu_support import gpu, long_launch_against_oracle as _long_launch_against_oracle, packed_counters  # noqa: E402, F401
+from gpu_support import RolloutOutputs, gpu, long_launch_against_oracle as _long_launch_against_oracle, no_sentinel, packed_counters  # noqa: E402, F401
 
 HORIZON = 400  # (the runner's default, gpu_support.long_launch_against_oracle: 4 000 steps at this horizon)
 
@@ -161,14 +162,14 @@ def test_mover_interact_split_with_layouts_redrawn_at_every_restart(table_kind, 
         ep_o = np.zeros((n, 4), np.float32)
         steps = 0
         for T_, tiled in ((32, False), (40, True), (48, False)):
-            rew = torch.zeros((T_, n, 4), dtype=torch.float32, device=gpu)
-            fl = torch.zeros((T_ // 8, n, 8) if tiled else (T_, n), dtype=torch.uint8, device=gpu)
-            env.rollout_random(T_, rew, fl, flags_tiled8=tiled)
-            if tiled:
-                fl = VecOvercookedEnv.untile_flags(fl)
+            out = RolloutOutputs(T_, n, gpu, tiled=tiled)
+            env.rollout_random(T_, out.rew, out.fl, flags_tiled8=tiled)
+            out.guards_untouched(table_kind)
+            rew, fl = out.rew, out.flags()
             sp = O.start_spec(seed, off, 1 + steps, regen=(0, K), **start_kw)
             rew_o, fl_o = orc.rollout_random(st, T_, horizon=horizon, options=1, seed=seed, env_offset=off, t0=steps,
                                              layout_id=lid_o, ep_returns=ep_o, start=sp)
+            no_sentinel(table_kind, rew_o, fl_o)
             steps += T_
             assert np.array_equal(env.layout_ids(), lid_o), "layout ids differ after %d steps" % steps
             assert np.array_equal(fl.cpu().numpy(), fl_o) and np.array_equal(rew.cpu().numpy(), rew_o), steps
@@ -228,12 +229,14 @@ def test_layout_redrawn_every_episode_inside_the_fused_auto_reset(table_kind, gp
         ep_o = np.zeros((n, 4), np.float32)
         steps = 0
         for T in (31, 40):  # the fused rollout: three boundaries (steps 23, 46, 69)
-            rew = torch.zeros((T, n, 4), dtype=torch.float32, device=gpu)
-            fl = torch.zeros((T, n), dtype=torch.uint8, device=gpu)
+            out = RolloutOutputs(T, n, gpu)
+            rew, fl = out.rew, out.fl
             env.rollout_random(T, rew, fl)
+            out.guards_untouched(table_kind)
             sp = O.start_spec(seed, off, 1 + steps, regen=(0, K), **start_kw)
             rew_o, fl_o = orc.rollout_random(st, T, horizon=horizon, options=1, seed=seed, env_offset=off, t0=steps,
                                              layout_id=lid_o, ep_returns=ep_o, start=sp)
+            no_sentinel(table_kind, rew_o, fl_o)
             steps += T
             assert np.array_equal(env.layout_ids(), lid_o), "layout ids differ after %d steps" % steps
             assert np.array_equal(fl.cpu().numpy(), fl_o) and np.array_equal(rew.cpu().numpy(), rew_o)
@@ -250,12 +253,14 @@ def test_layout_redrawn_every_episode_inside_the_fused_auto_reset(table_kind, gp
         assert np.array_equal(env.layout_ids(), lid_o) and np.array_equal(env.get_packed_state(), st)
         Ks = horizon + 4  # K steps in one launch (oc_step_many), a fifth boundary
         acts_k = rng.integers(0, 6, size=(Ks, n, 2)).astype(np.uint8)
-        rew_k = torch.zeros((Ks, n, 4), dtype=torch.float32, device=gpu)
-        fl_k = torch.zeros((Ks, n), dtype=torch.uint8, device=gpu)
+        out_k = RolloutOutputs(Ks, n, gpu)
+        rew_k, fl_k = out_k.rew, out_k.fl
         env.step_many(torch.from_numpy(acts_k).to(gpu), rew_k, fl_k)
+        out_k.guards_untouched(table_kind)
         for k in range(Ks):
             sp = O.start_spec(seed, off, 1 + steps + k, regen=(0, K), **start_kw)
             st, r_o, f_o = orc.step(st, acts_k[k], horizon=horizon, options=1, layout_id=lid_o, ep_returns=ep_o, start=sp)
+            no_sentinel(table_kind, r_o, f_o)
             assert np.array_equal(rew_k[k].cpu().numpy(), r_o) and np.array_equal(fl_k[k].cpu().numpy(), f_o), k
         steps += Ks
         assert np.array_equal(env.layout_ids(), lid_o) and np.array_equal(env.get_packed_state(), st)
@@ -300,18 +305,24 @@ def test_xcd_contiguous_block_mapping_on_ragged_batches(n, gpu):
         st = orc.reset(orc.new_state(n))
         K = 12
         acts = rng.integers(0, 6, size=(K, n, 2)).astype(np.uint8)
-        rew = torch.zeros((K, n, 4), dtype=torch.float32, device=gpu)
-        fl = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
+        out = RolloutOutputs(K, n, gpu)
+        rew, fl = out.rew, out.fl
         env.step_many(torch.from_numpy(acts).to(gpu), rew, fl)
+        out.guards_untouched((name, n))
         for k in range(K):
             st, r_o, f_o = orc.step(st, acts[k], horizon=9, options=1)
+            no_sentinel((name, n), r_o, f_o)
             assert np.array_equal(rew[k].cpu().numpy(), r_o) and np.array_equal(fl[k].cpu().numpy(), f_o), (name, n, k)
         assert np.array_equal(env.get_packed_state(), st), (name, n)
         env.one_kernel = True
         obs = torch.zeros((K, n, 2, env.width, env.height, 26), dtype=torch.uint8, device=gpu)
+        out = RolloutOutputs(K, n, gpu)  # (new arrays: the ones above hold the results of step_many)
+        rew, fl = out.rew, out.fl
         env.rollout_encode(K, obs, rew, fl)
+        out.guards_untouched((name, n))
         for k in range(K):
             r_o, f_o = orc.rollout_random(st, 1, horizon=9, options=1, seed=2, t0=k)  # (the Philox clock counts random-policy steps only)
+            no_sentinel((name, n), r_o, f_o)
             assert np.array_equal(rew[k].cpu().numpy(), r_o[0]) and np.array_equal(fl[k].cpu().numpy(), f_o[0]), (name, n, k)
             assert np.array_equal(obs[k].cpu().numpy().astype(np.int32), orc.encode_lossless(st, horizon=9)), (name, n, k)
         assert np.array_equal(env.get_packed_state(), st), (name, n)
@@ -344,16 +355,17 @@ def test_mover_interact_event_log_against_oracle(layouts, gpu):
     counts, done_counts = events.running, events.published
     steps = 0
     for T_, tiled in ((64, False), (56, True)):
-        rew = torch.zeros((T_, n, 4), dtype=torch.float32, device=gpu)
-        fl = torch.zeros((T_ // 8, n, 8) if tiled else (T_, n), dtype=torch.uint8, device=gpu)
-        env.rollout_random(T_, rew, fl, flags_tiled8=tiled)
-        fl_np = (VecOvercookedEnv.untile_flags(fl) if tiled else fl).cpu().numpy()
-        rew_np = rew.cpu().numpy()
+        out = RolloutOutputs(T_, n, gpu, tiled=tiled)
+        env.rollout_random(T_, out.rew, out.fl, flags_tiled8=tiled)
+        out.guards_untouched(layouts)
+        fl_np = out.flags().cpu().numpy()
+        rew_np = out.rew.cpu().numpy()
         for k in range(T_):
             acts = O.random_actions(seed, off, steps, n)
             st, r_o, f_o = orc.step(st, acts, horizon=horizon, options=1, layout_id=lid,
                                     start=O.start_spec(seed, off, 1 + steps, True, 0.5))
             steps += 1
+            no_sentinel(layouts, r_o, f_o)
             assert np.array_equal(fl_np[k], f_o) and np.array_equal(rew_np[k], r_o), steps
             events.update(orc.last_events, finished=(f_o & 1) != 0, cleared=(f_o & 4) != 0)  # (cleared at the restart)
         assert np.array_equal(env.get_packed_state(), st)
@@ -384,10 +396,10 @@ def test_rollouts_without_output_arrays_equal_the_ones_with(gpu):
     for ci, (table, lid, kw) in enumerate(cases):
         a = VecOvercookedEnv(table, n, horizon=100, device=gpu, auto_reset=True, seed=2, layout_id=lid, **kw)
         b = VecOvercookedEnv(table, n, horizon=100, device=gpu, auto_reset=True, seed=2, layout_id=lid, **kw)
-        rew = torch.zeros((T, n, 4), dtype=torch.float32, device=gpu)
-        fl = torch.zeros((T, n), dtype=torch.uint8, device=gpu)
+        out = RolloutOutputs(T, n, gpu)
         a.rollout_random(T)
-        b.rollout_random(T, rew, fl)
+        b.rollout_random(T, out.rew, out.fl)
+        out.all_written(ci)  # (no oracle here: every reward and flag written, nothing around them)
         assert torch.equal(a.state, b.state) and torch.equal(a.ep_returns, b.ep_returns), ci
         if kw:
             assert torch.equal(a.event_counts, b.event_counts) and torch.equal(a.event_counts_done, b.event_counts_done)
@@ -413,10 +425,12 @@ def test_long_launches_off_the_eight_step_grid_split_around_whole_blocks(gpu):
         b = VecOvercookedEnv(table, n, horizon=37, device=gpu, auto_reset=True, seed=6, layout_id=lid, **kw)
         b.one_wavefront = True
         for T in (3, 1000, 13, 407, 800):  # first steps 0, 3, 1003, 1016, 1423: off the grid from the second call on
-            ra, fa = torch.zeros((T, n, 4), dtype=torch.float32, device=gpu), torch.zeros((T, n), dtype=torch.uint8, device=gpu)
-            rb, fb = torch.zeros_like(ra), torch.zeros_like(fa)
+            out_a, out_b = RolloutOutputs(T, n, gpu), RolloutOutputs(T, n, gpu)
+            (ra, fa), (rb, fb) = (out_a.rew, out_a.fl), (out_b.rew, out_b.fl)
             a.rollout_random(T, ra, fa)
             b.rollout_random(T, rb, fb)
+            for out in (out_a, out_b):  # (two launches that could drop the same store: every reward and flag must have been written)
+                out.all_written((ci, T))
             assert torch.equal(ra, rb) and torch.equal(fa, fb), (ci, T)
             assert torch.equal(a.state, b.state) and torch.equal(a.ep_returns, b.ep_returns), (ci, T)
         if "track_events" in kw:

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from case_support import new_oracle as _oracle  # noqa: E402
-from gpu_support import gpu  # noqa: E402, F401
+from gpu_support import gpu, no_sentinel, record_buffers  # noqa: E402, F401
 
 SEVEN = {"grid": "XPPPPPX\nO 1 2 O\nX     X\nXDPSPTX", "onion_time": 3, "tomato_time": 5, "onion_value": 7, "tomato_value": 4}
 
@@ -40,10 +40,9 @@ def _env(gpu, name, n, horizon, seed=3, env_offset=0, t0=0, **kw):
 
 
 def _buffers(env, K):
-    dev, n = env.state.device, env.n_envs
-    return (torch.full((K, n, 2), 0xEE, dtype=torch.uint8, device=dev),
-            torch.full((K, env.n_planes, n, 16), 0xEE, dtype=torch.uint8, device=dev),
-            torch.zeros((K, n, 4), dtype=torch.float32, device=dev), torch.zeros((K, n), dtype=torch.uint8, device=dev))
+    """(actions, states, rewards, flags), all sentinels between guard rows, and the check of those rows (gpu_support.record_buffers)"""
+    bufs, check = record_buffers(K, env.n_envs, env.n_planes, env.state.device)
+    return (bufs["actions_out"], bufs["states_out"], bufs["rewards_out"], bufs["flags_out"]), check
 
 
 def _record_and_check(gpu, name, n, K, horizon, t0=0, seed=3, env_offset=0, start=None, check_envs=None):
@@ -53,9 +52,10 @@ def _record_and_check(gpu, name, n, K, horizon, t0=0, seed=3, env_offset=0, star
 
     env, lid = _env(gpu, name, n, horizon, seed=seed, env_offset=env_offset, t0=t0, **(start or {}))
     before, epoch = env.get_packed_state().copy(), env.reset_epoch
-    acts, states, rew, fl = _buffers(env, K)
+    (acts, states, rew, fl), guards_untouched = _buffers(env, K)
     env.rollout_random(K, rew, fl, actions_out=acts, states_out=states)
     assert env.t_global == t0 + K
+    guards_untouched(name)
     A, S, R, F = acts.cpu().numpy(), states.cpu().numpy(), rew.cpu().numpy(), fl.cpu().numpy()
     final = env.get_packed_state()
     for k in range(K):
@@ -71,6 +71,7 @@ def _record_and_check(gpu, name, n, K, horizon, t0=0, seed=3, env_offset=0, star
             raise AssertionError("drawn starts are keyed by the global env: check all envs")
         nxt, r, f = orc.step(np.ascontiguousarray(S[k][:, sel]), A[k][sel], horizon=horizon, options=1, layout_id=lid_s, start=sp)
         after = S[k + 1][:, sel] if k + 1 < K else final[:, sel]
+        no_sentinel(name, r, f)
         assert np.array_equal(nxt, after), "state after step %d" % k
         assert np.array_equal(r, R[k][sel]), "rewards of step %d" % k
         assert np.array_equal(f, F[k][sel]), "flags of step %d" % k
@@ -99,8 +100,9 @@ def test_actions_only_65536_envs(gpu):
     from oracle import oracle as O
 
     env, _ = _env(gpu, "cramped_room", 65536, 400, seed=9, t0=13)
-    acts, _, _, _ = _buffers(env, 19)
+    (acts, _, _, _), guards_untouched = _buffers(env, 19)
     env.rollout_random(19, actions_out=acts)
+    guards_untouched("actions only")
     A = acts.cpu().numpy()
     for k in range(19):
         assert np.array_equal(A[k], O.random_actions(9, 0, 13 + k, 65536))
@@ -112,11 +114,14 @@ def test_recording_changes_nothing(gpu, name):
     runs = []
     for record in (False, True):
         env, _ = _env(gpu, name, 3000, 50, seed=17, t0=6, **start)
-        acts, states, rew, fl = _buffers(env, 130)
+        (acts, states, rew, fl), guards_untouched = _buffers(env, 130)
         if record:
             env.rollout_random(130, rew, fl, actions_out=acts, states_out=states)
         else:
             env.rollout_random(130, rew, fl)
+        guards_untouched(name)
+        # (two launches that could drop the same store: every reward and flag must have been written)
+        assert not bool((rew == -7.0).any()) and not bool((fl == 0xEE).any()), (name, record)
         runs.append((rew.cpu().numpy(), fl.cpu().numpy(), env.ep_returns.cpu().numpy(), env.get_packed_state(), env.t_global,
                      env.reset_epoch))
     for a, b in zip(*runs):
@@ -126,8 +131,9 @@ def test_recording_changes_nothing(gpu, name):
 def test_recorded_states_encode_like_rollout_encode(gpu):
     K, n = 24, 1024
     env, _ = _env(gpu, "cramped_room", n, 10, seed=2)
-    acts, states, rew, fl = _buffers(env, K)
+    (acts, states, rew, fl), guards_untouched = _buffers(env, K)
     env.rollout_random(K, rew, fl, actions_out=acts, states_out=states)
+    guards_untouched("recorded states")
     env2, _ = _env(gpu, "cramped_room", n, 10, seed=2)
     obs = torch.zeros((K, n, 2, env.width, env.height, 26), dtype=torch.uint8, device=gpu)
     env2.rollout_encode(K, obs)
@@ -160,8 +166,10 @@ def test_converter_matches_dropin_get_rollouts(gpu):
     env, _ = _env(gpu, "cramped_room", n, H, seed=4)
     recs = []
     for K in (37, H * games - 37 + 5):  # two recordings joined along the step axis
-        recs.append(_buffers(env, K))
+        bufs, guards_untouched = _buffers(env, K)
+        recs.append(bufs)
         env.rollout_random(K, recs[-1][2], recs[-1][3], actions_out=recs[-1][0], states_out=recs[-1][1])
+        guards_untouched("converter")
     acts, states, rew, fl = (torch.cat([r[i] for r in recs]) for i in range(4))
     envs = [0, 7, 63]
     traj = recorded_trajectories(env, states, acts, rew, fl, envs=envs)

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from case_support import new_oracle as _oracle  # noqa: E402
-from gpu_support import gpu  # noqa: E402, F401
+from gpu_support import gpu, no_sentinel, record_buffers  # noqa: E402, F401
 
 SEVEN = {"grid": "XPPPPPX\nO 1 2 O\nX     X\nXDPSPTX", "onion_time": 3, "tomato_time": 5, "onion_value": 7, "tomato_value": 4}
 
@@ -45,13 +45,9 @@ def _env(gpu, name, n, horizon, seed=3, env_offset=0, t0=0, regen=False, **kw):
 
 
 def _buffers(env, K):
-    dev, n = env.state.device, env.n_envs
-    return dict(actions_out=torch.full((K, n, 2), 0xEE, dtype=torch.uint8, device=dev),
-                states_out=torch.full((K, env.n_planes, n, 16), 0xEE, dtype=torch.uint8, device=dev),
-                layouts_out=torch.full((K, n), -1, dtype=torch.int16, device=dev),
-                events_out=torch.full((K, n), -1, dtype=torch.int64, device=dev),
-                rewards_out=torch.zeros((K, n, 4), dtype=torch.float32, device=dev),
-                flags_out=torch.zeros((K, n), dtype=torch.uint8, device=dev))
+    """The six arrays of a recorded launch (rollout_random's keywords), all sentinels between guard rows, and the check of those rows
+    (gpu_support.record_buffers)"""
+    return record_buffers(K, env.n_envs, env.n_planes, env.state.device, layouts=True, masks=True)
 
 
 def _host(bufs):
@@ -73,9 +69,10 @@ def _record_and_check(gpu, name, n, K, horizon, t0=0, seed=3, env_offset=0, star
     if epoch0 is not None:
         env._epoch = epoch0
     before, lid0, epoch = env.get_packed_state().copy(), env.layout_ids(), env.reset_epoch
-    bufs = _buffers(env, K)
+    bufs, guards_untouched = _buffers(env, K)
     env.rollout_random(K, **bufs)
     assert env.t_global == t0 + K
+    guards_untouched(name)
     H = _host(bufs)
     S, A, Lid, E, R, F = H["states_out"], H["actions_out"], H["layouts_out"], H["events_out"], H["rewards_out"], H["flags_out"]
     final, lid_final = env.get_packed_state(), env.layout_ids()
@@ -98,6 +95,7 @@ def _record_and_check(gpu, name, n, K, horizon, t0=0, seed=3, env_offset=0, star
         nxt, r, f = orc.step(np.ascontiguousarray(S[k][:, sel]), A[k][sel], horizon=horizon, options=1, layout_id=lid, start=sp)
         after, lid_after = (S[k + 1][:, sel], Lid[k + 1][sel]) if k + 1 < K else (final[:, sel], lid_final[sel])
         assert np.array_equal(nxt, after), "state after step %d" % k
+        no_sentinel(name, r, f, orc.last_events)
         if multi:
             assert np.array_equal(lid, lid_after), "layout ids after step %d" % k
         assert np.array_equal(r, R[k][sel]), "rewards of step %d" % k
@@ -134,11 +132,14 @@ def test_recording_changes_nothing(gpu, name, regen):
     runs = []
     for record in (False, True):
         env = _env(gpu, name, 3000, 50, seed=17, t0=6, regen=regen, **start)
-        bufs = _buffers(env, 130)
+        bufs, guards_untouched = _buffers(env, 130)
         if record:
             env.rollout_random(130, **bufs)
         else:
             env.rollout_random(130, bufs["rewards_out"], bufs["flags_out"], bufs["events_out"])
+        guards_untouched(name)
+        # (two launches that could drop the same store: every reward, flag and mask must have been written)
+        assert not any(bool((bufs[k] == fill).any()) for k, fill in (("rewards_out", -7.0), ("flags_out", 0xEE), ("events_out", -1))), (name, record)
         stats = [{k: v.cpu().numpy() for k, v in env.event_stats(finished).items()} for finished in (False, True)]
         runs.append([bufs["rewards_out"].cpu().numpy(), bufs["flags_out"].cpu().numpy(), bufs["events_out"].cpu().numpy(),
                      env.ep_returns.cpu().numpy(), env.get_packed_state(), env.layout_ids(), env.t_global, env.reset_epoch,
@@ -181,8 +182,10 @@ def test_converter_matches_dropin_get_rollouts(gpu):
     env = _env(gpu, "mix5", n, H, seed=4, regen=True)
     recs = []
     for K in (37, H * games - 37 + 5):  # two recordings joined along the step axis
-        recs.append(_buffers(env, K))
+        bufs, guards_untouched = _buffers(env, K)
+        recs.append(bufs)
         env.rollout_random(K, **recs[-1])
+        guards_untouched("converter")
     joined = {k: torch.cat([r[k] for r in recs]) for k in recs[0]}
     envs = [0, 7, 63]
     traj = recorded_trajectories(env, joined["states_out"], joined["actions_out"], joined["rewards_out"], joined["flags_out"],
@@ -221,12 +224,14 @@ def test_two_shards_equal_one_batch(gpu):
     lid = ((np.arange(n) * 7 + 3) % 5).astype(np.uint16)
     kw = dict(horizon=H, auto_reset=True, seed=21, regen_layout=True, track_events=True)
     one = _env(gpu, "mix5", n, H, seed=21, regen=True)
-    ref = _buffers(one, K)
+    ref, ref_guards_untouched = _buffers(one, K)
     one.rollout_random(K, **ref)
     sh = ShardedVecOvercookedEnv(table, n, devices=["cuda:0", "cuda:0"], layout_id=lid, **kw)
-    per = [_buffers(s.env, K) for s in sh.shards]
+    per, per_guards_untouched = zip(*[_buffers(s.env, K) for s in sh.shards])
     sh.rollout_random(K, **{k: [p[k] for p in per] for k in per[0]})
     sh.synchronize()
+    for shard, check in enumerate((ref_guards_untouched,) + per_guards_untouched):
+        check("batch / shard %d" % shard)
     for key, axis in (("actions_out", 1), ("states_out", 2), ("layouts_out", 1), ("events_out", 1), ("rewards_out", 1),
                       ("flags_out", 1)):
         assert torch.equal(torch.cat([p[key] for p in per], dim=axis), ref[key]), key

@@ -1,10 +1,11 @@
 """The resident batched step (oc_step_server_*, csrc/step_server.hpp): k_step_server + its device-side client against
-oc_step_many / oc_step and the oracle — OvercookedEnv.step (overcooked_env.py:244-274) without a launch per step."""
+oc_step_many / oc_step and the oracle — OvercookedEnv.step (overcooked_env.py:244-274) without a launch per step.  The rewards and
+flags the server writes start as values no result holds (-7.0; 0xEE) and have guard rows behind them that must come back untouched."""
 import numpy as np
 import pytest
 import torch
 
-from gpu_support import make_env, oracle_for
+from gpu_support import guarded, guards_untouched, make_env, no_sentinel, oracle_for
 from helpers import CANONICAL_5
 
 pytestmark = pytest.mark.gpu
@@ -15,6 +16,18 @@ def gpu():  # (not gpu_support's: this module has always skipped, not failed, wh
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     return torch.device("cuda:0")
+
+
+def _outputs(K, n, gpu):
+    """(rewards [K, n, 4], flags [K, n], their guards): filled and guarded as tests/test_gpu_step_instances.py's server branch does"""
+    rew, g_rew = guarded(K * n, (4,), torch.float32, -7.0, gpu)
+    fl, g_fl = guarded(K * n, (), torch.uint8, 0xEE, gpu)
+    return rew.view(K, n, 4), fl.view(K, n), (("rewards", g_rew, -7.0), ("flags", g_fl, 0xEE))
+
+
+def _untouched(case, guards):
+    for what, g, fill in guards:
+        guards_untouched(case, what, g, fill)
 
 
 def test_step_server_equals_single_steps_with_illegal_actions_and_resets(gpu):
@@ -35,8 +48,7 @@ def test_step_server_equals_single_steps_with_illegal_actions_and_resets(gpu):
         acts = torch.from_numpy(a).to(gpu)
         res = make_env(layouts, n, gpu, horizon=horizon, auto_reset=True, layout_id=lid)
         one = make_env(layouts, n, gpu, horizon=horizon, auto_reset=True, layout_id=lid)
-        rew = torch.zeros((K, n, 4), dtype=torch.float32, device=gpu)
-        fl = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
+        rew, fl, guards = _outputs(K, n, gpu)
         specs = layouts.specs if n_lay else [layouts if not isinstance(layouts, str) else spec_from_name(layouts)]
         orc = oracle_for(specs)
         st = orc.reset(orc.new_state(n), layout_id=lid)
@@ -57,10 +69,12 @@ def test_step_server_equals_single_steps_with_illegal_actions_and_resets(gpu):
                 assert torch.equal(r1, r2) and torch.equal(f1, f2), k
         for k in range(K):
             st, r_o, f_o = orc.step(st, a[k], horizon=horizon, options=1, layout_id=lid, ep_returns=ep)
+            no_sentinel("%d envs" % n, r_o, f_o)
             assert np.array_equal(r_o, rew[k].cpu().numpy()) and np.array_equal(f_o, fl[k].cpu().numpy()), k
         assert torch.equal(res.state, one.state) and torch.equal(res.ep_returns, one.ep_returns)
         assert np.array_equal(res.get_packed_state(), st) and np.array_equal(res.ep_returns.cpu().numpy(), ep)
         assert (fl & 2).any() and (fl & 4).any()
+        _untouched("%d envs" % n, guards)
 
 
 def test_step_server_drawn_starts_and_idle_exit(gpu):
@@ -74,8 +88,7 @@ def test_step_server_drawn_starts_and_idle_exit(gpu):
     one = make_env("asymmetric_advantages", n, gpu, horizon=horizon, auto_reset=True, **kw)
     assert torch.equal(res.state, one.state)
     acts = torch.randint(0, 6, (K, n, 2), dtype=torch.uint8, device=gpu, generator=torch.Generator(device=gpu).manual_seed(3))
-    rew = torch.zeros((K, n, 4), dtype=torch.float32, device=gpu)
-    fl = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
+    rew, fl, guards = _outputs(K, n, gpu)
     with res.step_server(idle_ms=4.0, life_s=5.0) as sv:
         sv.play(acts[:25], rew[:25], fl[:25])
         time.sleep(0.1)  # 25 x the idle window: the kernel has left by itself
@@ -90,6 +103,7 @@ def test_step_server_drawn_starts_and_idle_exit(gpu):
             assert torch.equal(r1, rew[k]) and torch.equal(f1, fl[k]), k
     assert torch.equal(res.state, one.state) and torch.equal(res.ep_returns, one.ep_returns)
     assert (fl & 4).any()
+    _untouched("drawn starts", guards)
 
 
 def test_step_server_refuses_what_it_does_not_serve(gpu):
@@ -118,12 +132,12 @@ def test_step_server_leaves_and_returns_around_its_idle_and_life_windows(gpu):
         for burst in range(120):
             K = int(rng.integers(1, 9))
             acts = torch.randint(0, 6, (K, n, 2), dtype=torch.uint8, device=gpu, generator=g)
-            rew = torch.zeros((K, n, 4), dtype=torch.float32, device=gpu)
-            fl = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
+            rew, fl, guards = _outputs(K, n, gpu)
             sv.play(acts, rew, fl)
             for k in range(K):
                 r1, f1 = one.step(acts[k])
                 assert torch.equal(r1, rew[k]) and torch.equal(f1, fl[k]), (burst, k)
+            _untouched("burst %d" % burst, guards)
             total += K
             time.sleep(float(rng.choice([0.0, 0.0005, 0.001, 0.002, 0.03])))
         assert sv.steps == total
@@ -138,8 +152,7 @@ def test_step_server_relaunch_sees_the_callers_pending_work_on_the_states(gpu):
     one = make_env("cramped_room", n, gpu, horizon=horizon, auto_reset=True)
     g = torch.Generator(device=gpu).manual_seed(4)
     acts = torch.randint(0, 6, (60, n, 2), dtype=torch.uint8, device=gpu, generator=g)
-    rew = torch.zeros((60, n, 4), dtype=torch.float32, device=gpu)
-    fl = torch.zeros((60, n), dtype=torch.uint8, device=gpu)
+    rew, fl, guards = _outputs(60, n, gpu)
     with res.step_server(idle_ms=5.0) as sv:
         sv.play(acts[:20], rew[:20], fl[:20])
         sv.sync()
@@ -155,6 +168,7 @@ def test_step_server_relaunch_sees_the_callers_pending_work_on_the_states(gpu):
             r1, f1 = one.step(acts[k])
             assert torch.equal(r1, rew[k]) and torch.equal(f1, fl[k]), k
     assert torch.equal(res.state, one.state) and torch.equal(res.ep_returns, one.ep_returns)
+    _untouched("pending work", guards)
 
 
 def test_step_server_on_a_table_read_through_l2_with_layout_redraws(gpu):
@@ -170,8 +184,7 @@ def test_step_server_on_a_table_read_through_l2_with_layout_redraws(gpu):
     res = make_env(table, n, gpu, **kw)
     one = make_env(table, n, gpu, **kw)
     acts = torch.randint(0, 6, (K, n, 2), dtype=torch.uint8, device=gpu, generator=torch.Generator(device=gpu).manual_seed(8))
-    rew = torch.zeros((K, n, 4), dtype=torch.float32, device=gpu)
-    fl = torch.zeros((K, n), dtype=torch.uint8, device=gpu)
+    rew, fl, guards = _outputs(K, n, gpu)
     with res.step_server(idle_ms=5.0) as sv:
         sv.play(acts, rew, fl)
     for k in range(K):
@@ -179,3 +192,4 @@ def test_step_server_on_a_table_read_through_l2_with_layout_redraws(gpu):
         assert torch.equal(r1, rew[k]) and torch.equal(f1, fl[k]), k
     assert torch.equal(res.state, one.state) and np.array_equal(res.layout_ids(), one.layout_ids())
     assert (fl & 4).any() and not np.array_equal(res.layout_ids(), lid)
+    _untouched("layout redraws", guards)

@@ -6,7 +6,12 @@ The tolerance is zero, and it is derived, not chosen: the transition, the restar
 and the observation are integer work; the rewards are small integers in f32; phi is the same sequence of IEEE float64
 operations on both sides (`#pragma clang fp contract(off)` in every training kernel, -ffp-contract=off for the oracle; the suite
 holds oc_potential to bit identity already), and shaped = (sparse0 + sparse1) + factor * dense is one sum, one product and one
-sum of float64 on both sides.  So every array is compared with np.array_equal, the float64 ones as bit patterns."""
+sum of float64 on both sides.  So every array is compared with np.array_equal, the float64 ones as bit patterns.
+
+The env owns its output arrays and reuses them from step to step, so a row that a step does not write would keep the row of the step
+before — for `done`, sparse rewards and most observation cells the same value.  Before every step the arrays the step must overwrite
+completely are filled with values no result holds, and the persistent observation lies between guard rows."""
+import numpy as np
 import pytest
 
 import train_cases as TC
@@ -16,9 +21,38 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from case_support import compare  # noqa: E402
-from gpu_support import gpu, packed_counters  # noqa: E402, F401
+from gpu_support import FLAG_FILL, GUARD, REW_FILL, gpu, guarded, guards_untouched, no_sentinel, packed_counters  # noqa: E402, F401
 
+F64_FILL = -12345.0  # no training reward (a few rewards plus a factor <= 1 times a potential difference) and no potential holds it
 OBS_CHUNK = 16384  # envs per comparison of the observation: the oracle's int32 image of 16 384 cramped_room envs is 68 MB
+
+
+def guarded_observation(env, case, table, dt, device):
+    """The env's persistent observation buffer replaced by the middle rows of an array of sentinels (0xEE for u8, -7.0 for f32):
+    GUARD rows behind the output and as many before it, or one more where the kernels' 16-byte alignment of d_obs needs it (a row
+    of a u8 observation of an odd number of cells is a multiple of 4 bytes only).  -> (the fill, the guard slices)"""
+    fill = FLAG_FILL if dt == torch.uint8 else REW_FILL
+    row_bytes = 2 * table.width * table.height * 26 * torch.empty((), dtype=dt).element_size()
+    before = next(r for r in range(GUARD, GUARD + 4) if r * row_bytes % 16 == 0)
+    env._obs, guards = guarded(case.n_envs, (2, table.width, table.height, 26), dt, fill, device, before=before)
+    assert env._obs.data_ptr() % 16 == 0 and env._obs.is_contiguous() and env._obs_buffer() is env._obs
+    return fill, guards
+
+
+def fill_step_outputs(env, case, obs_fill):
+    """Before a step: sentinels in every env-owned array the step must overwrite completely.  Not in what a step carries over or adds
+    to: the state, ep_returns (read, added to, copied out), phi_cur (this step's phi(s)), the event counters.  None of the filled
+    arrays is read before it is written: the kernels of the one-kernel paths only store to them, and the sequence writes rewards and
+    flags in oc_step, phi_next in oc_potential, shaped and done in oc_shape_rewards, before oc_shape_rewards / oc_reset read them."""
+    v = env.venv
+    env.shaped.fill_(F64_FILL)
+    env.done.fill_(FLAG_FILL)
+    if case.use_phi:
+        env.phi_next.fill_(F64_FILL)
+    v.rewards.fill_(REW_FILL)
+    v.flags.fill_(FLAG_FILL)
+    if obs_fill is not None:
+        env._obs.fill_(obs_fill)
 
 
 @pytest.mark.parametrize("case", TC.CASES, ids=lambda c: c.id)
@@ -36,6 +70,7 @@ def training_case_against_the_reference(case, gpu, epoch0=None):
     dt = {"u8": torch.uint8, "f32": torch.float32, None: None}[case.obs]
     env = VecOvercookedMultiAgent(table, case.n_envs, device=gpu, obs_dtype=dt, **TC.env_kwargs(case))
     assert env.plan() == plan, (case.id, env.plan(), plan)  # (the env's own batch and arrays give the plan the case was listed for)
+    obs_fill, obs_guards = guarded_observation(env, case, table, dt, gpu) if case.obs is not None else (None, None)
     ref = TC.oracle_of(case)
     v = env.venv
     if epoch0 is not None:
@@ -50,8 +85,12 @@ def training_case_against_the_reference(case, gpu, epoch0=None):
             env.anneal_reward_shaping_factor(TC.ANNEAL_TIMESTEPS)
         assert env.reward_shaping_factor == TC.factor_at(case, t)
         a = TC.actions_of(case, t)
+        fill_step_outputs(env, case, obs_fill)
         obs, shaped, done, infos = env.step(torch.from_numpy(a).to(gpu))
         ref.step(a, TC.factor_at(case, t))
+        no_sentinel(case, ref.rewards, ref.flags)
+        assert not (ref.done == FLAG_FILL).any() and not (ref.shaped == F64_FILL).any(), case.id
+        assert not case.use_phi or not (ref.phi_next == F64_FILL).any(), case.id
         fields = [("state", v.get_packed_state(), ref.state), ("rewards", v.rewards, ref.rewards), ("flags", v.flags, ref.flags),
                   ("ep_returns", v.ep_returns, ref.ep_returns), ("infos[ep_returns]", infos["ep_returns"], ref.ep_out),
                   ("shaped", shaped, ref.shaped), ("done", done, ref.done)]
@@ -67,8 +106,12 @@ def training_case_against_the_reference(case, gpu, epoch0=None):
         # the observation of the states the next step starts from, in env chunks (the batch of >= 131 072 envs: the first, the
         # last and every restart-bearing step)
         if case.obs is not None and (not big or t in (0, case.steps - 1) or ref.done.any()):
-            assert obs.dtype == dt and obs.shape == (case.n_envs, 2, table.width, table.height, 26)
+            assert obs.dtype == dt and obs.shape == (case.n_envs, 2, table.width, table.height, 26) and obs.data_ptr() == env._obs.data_ptr()
             for a0 in range(0, case.n_envs, OBS_CHUNK):
                 a1 = min(case.n_envs, a0 + OBS_CHUNK)
-                compare(case, t, "observation", obs[a0:a1].cpu().numpy(), ref.obs(a0, a1), lid(), e0=a0)
+                want = ref.obs(a0, a1)
+                assert not (np.asarray(want) == obs_fill).any(), "%s: an oracle observation cell equals the fill" % case.id
+                compare(case, t, "observation", obs[a0:a1].cpu().numpy(), want, lid(), e0=a0)
+    if obs_guards is not None:
+        guards_untouched(case, "observation", obs_guards, obs_fill)
     assert (ref.flags & 2).any()  # (the last step, like every step, carries illegal actions)
