@@ -859,6 +859,81 @@ int oc_multi_agent_step_featurize_plan(const OcBatch* batch, int horizon, int wi
                                        int num_pots, uint32_t options, int use_phi, int event_sink, const OcStartSpec* start,
                                        char* out, size_t out_size);
 
+/*
+ * The action sampler (ABI 6: entry points added beside the others; no existing signature, struct or option changes, so the
+ * version stays) — both players' actions of every env drawn from a policy's logits on the library's counter-based stream, with
+ * their log-probabilities (what PPO stores).  Everything between the policy's forward pass and the next observation is then one
+ * call (oc_multi_agent_step_sample), and the draws are a function of (seed, global env, step): a sharded batch draws what the
+ * whole batch draws, and any draw can be replayed.
+ *
+ * Stream.  For global env g = env_offset + e and the caller's 64-bit step counter t = step:
+ *   r[0..3] = philox4x32_10(counter = {t_lo, g_lo, g_hi, t_hi}, key = {seed_lo, seed_hi ^ 0x53414D50 ("SAMP")})
+ *   player p uses u_p = (float)(r[p] >> 8) * 2^-24, which is exact in f32 (0 <= u_p < 1); words 2 and 3 are reserved.
+ * All counters are used in full 64-bit width, with a carry from g_lo into g_hi inside a batch, as for the other streams.
+ *
+ * Arithmetic, per player, on its six logits l_0..l_5.  All steps are f32, in this order, with no contraction and the
+ * full-precision expf / logf (not the fast intrinsics):
+ *   m = max_i l_i;  w_i = expf(l_i - m);  c_i = c_{i-1} + w_i, summed left to right;  S = c_5
+ *   OC_SAMPLE_CATEGORICAL: x = u_p * S; the action is the number of i with c_i <= x, clamped to 5.  A -inf logit has w = 0 and
+ *                          is never drawn.
+ *   OC_SAMPLE_ARGMAX:      the lowest index holding m (u_p is not used).
+ *   logp = (l_a - m) - logf(S)
+ * Invalid rows.  If any of the six logits is NaN, or S is not finite and greater than 0 (all -inf, or a +inf), the action is 255
+ * and logp is NaN.  Every step kernel flags an action above 5 as OC_F_BAD_ACTION and leaves the env untouched; so here.
+ */
+#define OC_SAMPLE_CATEGORICAL 0u
+#define OC_SAMPLE_ARGMAX      1u
+typedef struct OcActionSampler {
+    const float* d_logits;   /* [n_envs][2][6] f32 (player, action index), 16-byte aligned */
+    uint8_t* d_actions_out;  /* [n_envs][2] u8, 2-byte aligned; required */
+    float* d_logp_out;       /* [n_envs][2] f32, 8-byte aligned; or NULL */
+    uint64_t seed;
+    int64_t env_offset;
+    int64_t step;
+    uint32_t mode;           /* OC_SAMPLE_CATEGORICAL / OC_SAMPLE_ARGMAX */
+} OcActionSampler;
+
+/*
+ * oc_sample_actions — the sampler alone (k_sample_actions, csrc/sample.hpp): one lane per env draws both players' actions from
+ * three 16-byte loads and one Philox block.  Of the batch only n_envs is read.  A NULL sampler, NULL d_logits or d_actions_out, a
+ * misaligned array or an unknown mode is OC_EINVAL, before any device call.
+ */
+int oc_sample_actions(const OcBatch* batch, const OcActionSampler* sampler, void* stream);
+
+/*
+ * oc_multi_agent_step_sample — oc_multi_agent_step_featurize whose actions are drawn from policy logits inside the call: every
+ * argument of oc_multi_agent_step_featurize, in its order, with `sampler` in the place of d_actions.  The drawn actions go to
+ * sampler->d_actions_out (they are the step's d_actions) and their log-probabilities to sampler->d_logp_out.  d_features == NULL
+ * gives the plain step's paths.  All checks of the step, of oc_featurize and of the sampler (as for oc_sample_actions) run before
+ * any device call; refusals carry this entry point's name.  The paths (oc_multi_agent_step_sample_plan says which):
+ *   fused      wherever the same call with an actions array is planned as k_train_step_obs, k_train_step_feat or k_train_step1, the
+ *              SAMPLE = true instance of that kernel runs: its owner lanes draw where the others read the actions, store the draws
+ *              and step — one launch (followed by what follows that kernel in the step's plan: oc_encode_lossless, k_featurize)
+ *   otherwise  k_sample_actions into d_actions_out, then the step's own planned path reading it: k_train_step<.., EV>, 65..128
+ *              cells, more than two pots (the sequence)
+ * Both paths call one device function, so their results are bit-equal (profiles/train_step_sample.txt: what each costs).
+ */
+int oc_multi_agent_step_sample(const OcBatch* batch, void* d_state, const OcActionSampler* sampler, float* d_rewards,
+                               uint8_t* d_flags, float* d_ep_returns, float* d_ep_returns_out, const uint8_t* d_plan_blob,
+                               const uint32_t* d_plan_off, const uint8_t* d_phi_tables, double* d_phi_next, double* d_phi_cur,
+                               const double* d_phi_start, double reward_shaping_factor, double* d_shaped, uint8_t* d_done,
+                               void* d_obs, int obs_dtype, int horizon, const uint8_t* d_feat_plan_blob,
+                               const uint32_t* d_feat_plan_off, float* d_features, int num_pots, uint32_t options,
+                               const OcStartSpec* start, const OcEventSink* events, void* stream);
+
+/*
+ * oc_multi_agent_step_sample_plan — what oc_multi_agent_step_sample would launch, as text: oc_multi_agent_step_featurize_plan's
+ * arguments (a whole, aligned sampler is assumed) and its words, changed in one of two ways:
+ *   "k_train_step_obs<MAXP=1, T=u8, NWV=16, SAMPLE=true> unit=..."     the fused path: SAMPLE=true as the step kernel's last parameter
+ *   "k_sample_actions + k_train_step<UNIFORM=true, EV=true> + ..."      every other plan
+ *   "nothing to launch (no envs)"
+ * Usable without a GPU, like the other plan calls; refusals carry oc_multi_agent_step_sample's name.
+ *   out, out_size caller's text buffer (>= 320 bytes holds every answer)
+ */
+int oc_multi_agent_step_sample_plan(const OcBatch* batch, int horizon, int with_obs, int obs_dtype, int with_features,
+                                    int num_pots, uint32_t options, int use_phi, int event_sink, const OcStartSpec* start,
+                                    char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ BATCH_NEW_DYNAMICS = 0x2
 BATCH_UNIFORM_SHAPING = 0x4
 BATCH_NO_SHARED_FACES = 0x8
 OBS_U8, OBS_F32 = 0, 1
+SAMPLE_CATEGORICAL, SAMPLE_ARGMAX = 0, 1
 
 EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes", "oc_batch_hints", "oc_step", "oc_step_many",
            "oc_rollout_random", "oc_rollout_record", "oc_rollout_record_ex", "oc_encode_lossless", "oc_step_encode", "oc_rollout_encode", "oc_featurize", "oc_rollout_featurize", "oc_potential",
@@ -26,7 +27,8 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_mailbox_open", "oc_mailbox_buffer", "oc_mailbox_step", "oc_mailbox_close", "oc_output_stores_only", "oc_rollout_plan", "oc_multi_agent_plan",
            "oc_observation_plan", "oc_step_plan", "oc_potential_plan", "oc_featurize_plan", "oc_rollout_featurize_plan", "oc_multi_agent_step_featurize_plan",
            "oc_step_server_open", "oc_step_server_requests", "oc_step_server_responses", "oc_step_server_resume",
-           "oc_step_server_play", "oc_step_server_sync", "oc_step_server_steps", "oc_step_server_close")
+           "oc_step_server_play", "oc_step_server_sync", "oc_step_server_steps", "oc_step_server_close",
+           "oc_sample_actions", "oc_multi_agent_step_sample", "oc_multi_agent_step_sample_plan")
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
 
 
@@ -62,6 +64,11 @@ class OcEventSink(ctypes.Structure):
 
 class OcRecordSink(ctypes.Structure):
     _fields_ = [("d_actions", ctypes.c_void_p), ("d_states", ctypes.c_void_p), ("d_layout_ids", ctypes.c_void_p)]
+
+
+class OcActionSampler(ctypes.Structure):
+    _fields_ = [("d_logits", ctypes.c_void_p), ("d_actions_out", ctypes.c_void_p), ("d_logp_out", ctypes.c_void_p),
+                ("seed", ctypes.c_uint64), ("env_offset", ctypes.c_int64), ("step", ctypes.c_int64), ("mode", ctypes.c_uint32)]
 
 
 class OcAmdError(RuntimeError):
@@ -177,6 +184,14 @@ def load():
     L.oc_rollout_featurize_plan.argtypes = [bp, i32, i32, u32, i32, i32, i32, sp, ctypes.c_char_p, ctypes.c_size_t]
     L.oc_multi_agent_step_featurize_plan.restype = i32
     L.oc_multi_agent_step_featurize_plan.argtypes = [bp, i32, i32, i32, i32, i32, u32, i32, i32, sp, ctypes.c_char_p, ctypes.c_size_t]
+    smp = ctypes.POINTER(OcActionSampler)
+    L.oc_sample_actions.restype = i32
+    L.oc_sample_actions.argtypes = [bp, smp, vp]
+    L.oc_multi_agent_step_sample.restype = i32
+    L.oc_multi_agent_step_sample.argtypes = [bp, vp, smp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_double, vp, vp, vp, i32, i32,
+                                             vp, vp, vp, i32, u32, sp, ep, vp]
+    L.oc_multi_agent_step_sample_plan.restype = i32
+    L.oc_multi_agent_step_sample_plan.argtypes = [bp, i32, i32, i32, i32, i32, u32, i32, i32, sp, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

@@ -19,6 +19,8 @@
 //   shaping.hpp         OvercookedMultiAgent.step reward, rllib.py:306-329: k_shape_rewards
 //   train_obs.hpp       the training step with its observation in one kernel: k_train_step_obs
 //   train_feat.hpp      the training step with the featurize_state observation in one kernel: k_train_step_feat
+//   sample.hpp          both players' actions drawn from policy logits: sample_env, k_sample_actions
+//   train_sample.hpp    the training step that draws its actions: the SAMPLE = true launches, oc_sample_actions, oc_multi_agent_step_sample (+ _plan)
 //   stores_only.hpp     the output stores of a rollout and nothing else: k_output_stores_only (oc_output_stores_only)
 //   observation_plan.hpp  host only: the observation geometry and the plans of oc_encode_lossless / oc_rollout_encode / oc_rollout_featurize
 //   this file           launch dispatch and the extern "C" entry points declared in include/oc_amd.h: oc_rollout_random,
@@ -60,6 +62,7 @@ namespace {
 #include "featurize.hpp"
 #include "rollout_featurize.hpp"
 #include "potential.hpp"
+#include "sample.hpp"
 #include "shaping.hpp"
 #include "train_obs.hpp"
 #include "train_feat.hpp"
@@ -1264,8 +1267,8 @@ inline int64_t train_feat_fill() { return (simd_count() / 16) * BLOCK; }
 
 // feat_tables: both feature plan pointers are there; feat_aligned: d_features is 16-byte aligned
 TrainFeatPlan plan_train_step_featurize(const OcBatch* b, const TrainArrays& have, bool feat_tables, bool feat_aligned, int obs_dtype,
-                                        int horizon, int num_pots, uint32_t options, const OcStartSpec* start) {
-    const char* const who = "oc_multi_agent_step_featurize";
+                                        int horizon, int num_pots, uint32_t options, const OcStartSpec* start,
+                                        const char* who = "oc_multi_agent_step_featurize") {  // who: the entry point a refusal names
     TrainFeatPlan p;
     const auto refused = [&p](int rc) { p.rc = rc; return p; };
     p.step = plan_train_step(b, have, obs_dtype, horizon, start, who);
@@ -1330,6 +1333,8 @@ void describe_train_feat_plan(const OcBatch* b, const TrainFeatPlan& p, const Tr
     }
 }
 }  // namespace
+
+#include "train_sample.hpp"  // oc_sample_actions, oc_multi_agent_step_sample, oc_multi_agent_step_sample_plan
 
 extern "C" {
 

@@ -128,9 +128,10 @@ __global__ __launch_bounds__(BLOCK) void k_train_step(const OcLayout* __restrict
 // k_train_step1: k_train_step with the transition computed on the wire format itself (step_one.hpp): the potential
 // needs the players and the pots — registers the step has just produced — and nothing of the counters, so the env is never
 // unpacked; header + changed object bytes are written back, the planes only for envs that restart.  No event logging
-// (k_train_step then), grids of at most 64 cells.  Same outputs, bit for bit.
+// (k_train_step then), grids of at most 64 cells.  Same outputs, bit for bit.  SAMPLE (with one more argument, a SampleArgs): the
+// lane draws both actions from the policy's logits (sample.hpp) and stores them with their log-probabilities before it steps.
 // ------------------------------------------------------------------------------------------
-template <bool UNIFORM, int MAXP, bool LAY_LDS>
+template <bool UNIFORM, int MAXP, bool LAY_LDS, bool SAMPLE = false, typename... SMP>
 __global__ __launch_bounds__(BLOCK) void k_train_step1(const OcLayout* __restrict__ g_layouts, int n_layouts,
                                                        const uint16_t* layout_id, uint4* st,
                                                        const uint8_t* __restrict__ actions, float4* __restrict__ rewards,
@@ -140,7 +141,8 @@ __global__ __launch_bounds__(BLOCK) void k_train_step1(const OcLayout* __restric
                                                        const uint8_t* __restrict__ phi_tables, double* __restrict__ phi_next,
                                                        double* __restrict__ phi_cur, const double* __restrict__ phi_start,
                                                        double factor, double* __restrict__ shaped, uint8_t* __restrict__ done,
-                                                       int64_t n, int W, int H, int n_obj, int horizon, StartArgs sa) {
+                                                       int64_t n, int W, int H, int n_obj, int horizon, StartArgs sa,
+                                                       SMP... smp) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) uint4 s_rows1[];  // [n_obj][BLOCK]: the object planes, one 16-byte row per lane
     __shared__ uint4 s_lay[LAY_LDS ? (UNIFORM ? 16 : LDS_LAYOUT_MAX * 16) : 1];
@@ -148,7 +150,8 @@ __global__ __launch_bounds__(BLOCK) void k_train_step1(const OcLayout* __restric
     const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const bool active = e < n;
     const int64_t el = active ? e : n - 1;
-    const OneIn in = one_load(st, actions, ep_returns, n, el, n_obj);
+    OneIn in = one_load(st, actions, ep_returns, n, el, n_obj);
+    if constexpr (SAMPLE) in.a01 = sample_env(first_of(smp...), el, active);  // (`actions` is then where the draws go)
     const double phi_before = phi_tables ? phi_cur[el] : 0.0;
     for (int i = threadIdx.x; i < 2 * LUT_ENTRIES; i += BLOCK) s_lut[i] = reinterpret_cast<const uint2*>(&g_lut)[i];
     Lay L = stage_layouts<LAY_LDS>(g_layouts, n_layouts, layout_id, e, active, s_lay);  // contains the barrier

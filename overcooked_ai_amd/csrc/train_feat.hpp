@@ -22,6 +22,8 @@
 //     (k_featurize's odd-dword row stride), and the image is streamed to its place as contiguous 16-byte float4 stores, with
 //     wave-level fences only; owner w and helper w claim the sub-groups of owner w's envs from one LDS counter.
 // Same outputs, bit for bit, as k_train_step1 + k_featurize (tests/test_gpu_train_featurize.py compares the two).
+// SAMPLE (with one more argument, a SampleArgs): the owners draw both actions from the policy's logits (sample.hpp) and store them
+// with their log-probabilities before they step.
 // ------------------------------------------------------------------------------------------
 
 // The state of one env as the head leaves it in LDS: its new wire header and its 16-byte row of every object plane
@@ -46,14 +48,15 @@ __host__ __device__ constexpr size_t train_feat_lds(int n_obj, int group_envs, i
     return ((size_t)n_obj + 4) * BLOCK * 16 + (size_t)TF_WAVES * train_feat_image_shorts(group_envs, num_pots) * sizeof(int16_t);
 }
 
-template <int MAXP>
+template <int MAXP, bool SAMPLE = false, typename... SMP>
 __global__ __launch_bounds__(TF_WAVES * 64) void k_train_step_feat(
     const OcLayout* __restrict__ g_layouts, uint4* st, const uint8_t* __restrict__ actions, float4* __restrict__ rewards,
     uint8_t* __restrict__ flags, float4* ep_returns, float4* __restrict__ ep_out, const uint8_t* __restrict__ plan_blob,
     const uint32_t* __restrict__ plan_off, const uint8_t* __restrict__ phi_tables, double* __restrict__ phi_next,
     double* __restrict__ phi_cur, const double* __restrict__ phi_start, double factor, double* __restrict__ shaped,
     uint8_t* __restrict__ done, const uint8_t* __restrict__ feat_plan_blob, const uint32_t* __restrict__ feat_plan_off,
-    float* __restrict__ features, int64_t n, int W, int H, int n_obj, int num_pots, int horizon, int group_envs, StartArgs sa) {
+    float* __restrict__ features, int64_t n, int W, int H, int n_obj, int num_pots, int horizon, int group_envs, StartArgs sa,
+    SMP... smp) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) uint4 s_dyn[];  // rows | header | records | rewards | images
     __shared__ uint4 s_lay[16];
@@ -76,7 +79,10 @@ __global__ __launch_bounds__(TF_WAVES * 64) void k_train_step_feat(
     // ---- everything the step reads, requested before the first wait (owners); the helpers ask for phi(s)
     OneIn in;
     double phi_before = 0.0;
-    if (owner) in = one_load(st, actions, ep_returns, n, el, n_obj);
+    if (owner) {
+        in = one_load(st, actions, ep_returns, n, el, n_obj);
+        if constexpr (SAMPLE) in.a01 = sample_env(first_of(smp...), el, active);  // (`actions` is then where the draws go)
+    }
     else if (phi_tables) phi_before = phi_cur[el];
     for (int i = threadIdx.x; i < 2 * LUT_ENTRIES; i += TF_WAVES * 64) s_lut[i] = reinterpret_cast<const uint2*>(&g_lut)[i];
     if (threadIdx.x < 16) s_lay[threadIdx.x] = reinterpret_cast<const uint4*>(g_layouts)[threadIdx.x];

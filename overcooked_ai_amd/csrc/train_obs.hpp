@@ -59,14 +59,16 @@ __device__ uint32_t g_obs_dbg[4096 * 8 * 8];
 // grid costs: not bytes — 3.5 us until the second barrier, then per 14-env sub-group ~1 us of template copy, 0.4 players, 1.6
 // objects, 0.7 stream on a wavefront that shares its SIMD with ONE other (an instruction every ~8 clocks); a SIMD issues from up
 // to ~5 wavefronts at that latency, so more wavefronts per CU with smaller private images, not fewer instructions, is the lever.
-template <int MAXP, typename T, int NWV>
+// SAMPLE (with one more argument, a SampleArgs): the owners draw both actions from the policy's logits (sample.hpp) and store them
+// with their log-probabilities before they step.
+template <int MAXP, typename T, int NWV, bool SAMPLE = false, typename... SMP>
 __global__ __launch_bounds__(NWV * 64) void k_train_step_obs(
     const OcLayout* __restrict__ g_layouts, uint4* st, const uint8_t* __restrict__ actions, float4* __restrict__ rewards,
     uint8_t* __restrict__ flags, float4* ep_returns, float4* __restrict__ ep_out, const uint8_t* __restrict__ plan_blob,
     const uint32_t* __restrict__ plan_off, const uint8_t* __restrict__ phi_tables, double* __restrict__ phi_next,
     double* __restrict__ phi_cur, const double* __restrict__ phi_start, double factor, double* __restrict__ shaped,
     uint8_t* __restrict__ done, uint8_t* __restrict__ obs_bytes, int64_t n, int W, int H, int n_obj, int horizon, int unit,
-    int group_envs, StartArgs sa) {
+    int group_envs, StartArgs sa, SMP... smp) {
 #pragma clang fp contract(off)
     OBS_T(tm_start);
     extern __shared__ __attribute__((aligned(16))) uint4 s_dyn[];  // rows | template | header | records | rewards | images
@@ -99,7 +101,10 @@ __global__ __launch_bounds__(NWV * 64) void k_train_step_obs(
     // ---- everything the step reads, requested before the first wait (owners); the helpers ask for phi(s)
     OneIn in;
     double phi_before = 0.0;
-    if (owner) in = one_load(st, actions, ep_returns, n, el, n_obj);
+    if (owner) {
+        in = one_load(st, actions, ep_returns, n, el, n_obj);
+        if constexpr (SAMPLE) in.a01 = sample_env(first_of(smp...), el, active);  // (`actions` is then where the draws go)
+    }
     else if (wave < 8 && phi_tables) phi_before = phi_cur[el];
     for (int i = threadIdx.x; i < 2 * LUT_ENTRIES; i += NWV * 64) s_lut[i] = reinterpret_cast<const uint2*>(&g_lut)[i];
     if (threadIdx.x < 16) s_lay[threadIdx.x] = reinterpret_cast<const uint4*>(g_layouts)[threadIdx.x];

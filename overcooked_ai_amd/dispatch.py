@@ -65,6 +65,22 @@ def multi_agent_featurize_plan(table, n_envs, horizon=400, obs_dtype=_lib.OBS_F3
     return out.value.decode()
 
 
+def multi_agent_sample_plan(table, n_envs, horizon=400, obs_dtype=_lib.OBS_F32, with_obs=False, with_features=False, num_pots=2,
+                            options=0, use_phi=True, event_sink=0, start=None):
+    """What `oc_multi_agent_step_sample` runs for this table, batch size and set of arrays (text): the words of
+    multi_agent_featurize_plan for the same call with ", SAMPLE=true" as the last parameter of the step kernel where that kernel draws
+    the actions itself (k_train_step_obs, k_train_step_feat, k_train_step1), else behind "k_sample_actions + ".  The arguments as
+    for multi_agent_featurize_plan.  The library's refusal is an OcAmdError."""
+    L = _lib.load()
+    b = batch_for(table, n_envs)
+    out = ctypes.create_string_buffer(400)
+    rc = L.oc_multi_agent_step_sample_plan(ctypes.byref(b), int(horizon), int(bool(with_obs)), int(obs_dtype), int(bool(with_features)),
+                                           int(num_pots), int(options), int(bool(use_phi)), int(event_sink),
+                                           ctypes.byref(start) if start is not None else None, out, len(out))
+    _lib.check(rc, "oc_multi_agent_step_sample_plan")
+    return out.value.decode()
+
+
 def observation_plan(table, n_envs, n_steps=0, obs_dtype=_lib.OBS_U8, horizon=400, options=_lib.OPT_AUTO_RESET, with_actions=False,
                      with_outputs=True, start=None):
     """The kernel instance `oc_encode_lossless` (n_steps == 0) or `oc_rollout_encode` (n_steps >= 1) launches for this table and

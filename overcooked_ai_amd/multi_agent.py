@@ -219,6 +219,8 @@ class VecOvercookedMultiAgent:
         self._obs = None
         self._feat = None
         self._phi_args = None
+        self.sample_step = 0  # step_sampled / sample_actions: the counter of the next draw (reset() leaves it alone)
+        self._sampled = None
         if self.use_phi:
             # phi of each layout's STANDARD start state (what a standard reset carries into phi_cur), from a probe batch of
             # one env per layout — the training batch itself may already hold drawn start states (epoch 0)
@@ -309,6 +311,11 @@ class VecOvercookedMultiAgent:
         if actions.dtype != torch.uint8 or actions.shape != (self.n_envs, 2) or not actions.is_contiguous() \
                 or actions.device != v.state.device:
             raise ValueError("actions must be a contiguous uint8 [n_envs, 2] tensor on %s" % v.device)
+        return self._step(actions.data_ptr(), None)
+
+    def _step(self, actions_ptr, sampler):
+        """step() with the caller's actions (sampler None), or step_sampled() with an OcActionSampler in their place."""
+        v = self.venv
         obs, code, start, sink = self._call_args()
         if self.use_phi:
             if self._phi_args is None:
@@ -318,11 +325,19 @@ class VecOvercookedMultiAgent:
             plan, off, tables = self._phi_args
         else:
             plan = off = tables = None
-        args = (v._bref, v._state_ptr, actions.data_ptr(), v._rewards_ptr, v._flags_ptr, v._ep_ptr, self.ep_returns.data_ptr(), plan, off,
+        args = (v._bref, v._state_ptr, actions_ptr if sampler is None else sampler, v._rewards_ptr, v._flags_ptr, v._ep_ptr, self.ep_returns.data_ptr(), plan, off,
                 tables, self.phi_next.data_ptr(), self.phi_cur.data_ptr(), self.phi_start.data_ptr(), float(self.reward_shaping_factor),
                 self.shaped.data_ptr(), self.done.data_ptr(), obs.data_ptr() if obs is not None else None, code, self.horizon)
         feat = None
-        if self._with_features:
+        if sampler is not None:
+            fargs = (None, None, None)
+            if self._with_features:
+                feat = self._feat_buffer()
+                fblob, foffs = v._plan(self.counter_goals)
+                fargs = (fblob.data_ptr(), foffs.data_ptr(), feat.data_ptr())
+            rc = v._launch(v.lib.oc_multi_agent_step_sample, *args, *fargs, self.num_pots, self._feat_options, start, sink)
+            self._lib.check(rc, "oc_multi_agent_step_sample")
+        elif self._with_features:
             feat = self._feat_buffer()
             fblob, foffs = v._plan(self.counter_goals)
             rc = v._launch(v.lib.oc_multi_agent_step_featurize, *args, fblob.data_ptr(), foffs.data_ptr(), feat.data_ptr(), self.num_pots,
@@ -341,6 +356,60 @@ class VecOvercookedMultiAgent:
         else:
             out = obs if obs is not None else self.observations()
         return out, self.shaped, self.done, infos
+
+    def _sampler(self, logits, greedy):
+        """The OcActionSampler of the next draw (persistent, like its output buffers): this env's seed and env offset, the sample
+        counter as the step."""
+        import ctypes
+
+        v, torch = self.venv, self._torch
+        if logits.dtype != torch.float32 or logits.shape != (self.n_envs, 2, 6) or not logits.is_contiguous() \
+                or logits.device != v.state.device:
+            raise ValueError("logits must be a contiguous float32 [n_envs, 2, 6] tensor on %s" % v.device)
+        if self._sampled is None:
+            self._sampled = (torch.zeros((self.n_envs, 2), dtype=torch.uint8, device=v.device),
+                             torch.zeros((self.n_envs, 2), dtype=torch.float32, device=v.device), self._lib.OcActionSampler())
+        actions, logp, s = self._sampled
+        s.d_logits, s.d_actions_out, s.d_logp_out = logits.data_ptr(), actions.data_ptr(), logp.data_ptr()
+        s.seed, s.env_offset, s.step = v.seed, v.env_offset, self.sample_step
+        s.mode = self._lib.SAMPLE_ARGMAX if greedy else self._lib.SAMPLE_CATEGORICAL
+        self.sample_step += 1
+        return actions, logp, ctypes.byref(s)
+
+    def sample_actions(self, logits, greedy=False):
+        """Both players' actions drawn from policy logits (float32 [n_envs, 2, 6]) on the library's counter-based stream, by
+        oc_sample_actions alone: (actions uint8 [n_envs, 2], logp float32 [n_envs, 2]) in persistent buffers.  One draw of the
+        env's sample counter, as in step_sampled(): `step(sample_actions(logits)[0])` is `step_sampled(logits)` in two calls."""
+        v = self.venv
+        actions, logp, s = self._sampler(logits, greedy)
+        self._lib.check(v._launch(v.lib.oc_sample_actions, v._bref, s), "oc_sample_actions")
+        return actions, logp
+
+    def step_sampled(self, logits, greedy=False):
+        """step() for a policy in the loop: `logits` is its output, contiguous float32 [n_envs, 2, 6] (player, action index) on the
+        env's device; both players' actions are drawn from it (greedy: the lowest-index maximum) and stepped by a single C call
+        (oc_multi_agent_step_sample; one launch wherever step() is one kernel).  Returns what step() returns, with the drawn
+        actions (uint8 [n_envs, 2]) and their log-probabilities (float32 [n_envs, 2]) in infos["actions"] / infos["logp"],
+        persistent buffers.  The draws are a function of (the env's seed, its env offset + env, sample_step): `sample_step`
+        starts at 0, goes up by one per call, and reset() leaves it alone.  A row of logits with a NaN, a +inf or nothing but
+        -inf draws action 255 with logp NaN: the env is flagged OC_F_BAD_ACTION and stays as it is."""
+        actions, logp, s = self._sampler(logits, greedy)
+        out, shaped, done, infos = self._step(None, s)
+        infos["actions"], infos["logp"] = actions, logp
+        return out, shaped, done, infos
+
+    def plan_sampled(self):
+        """The path and kernel instance the next step_sampled() runs, in oc_multi_agent_step_sample_plan's words."""
+        import ctypes
+
+        v = self.venv
+        obs, code, start, sink = self._call_args()
+        out = ctypes.create_string_buffer(400)
+        rc = v.lib.oc_multi_agent_step_sample_plan(v._bref, self.horizon, int(obs is not None), code, int(self._with_features),
+                                                   self.num_pots, self._feat_options, int(self.use_phi), int(sink is not None), start,
+                                                   out, len(out))
+        self._lib.check(rc, "oc_multi_agent_step_sample_plan")
+        return out.value.decode()
 
     def anneal_reward_shaping_factor(self, timesteps):
         self.reward_shaping_factor = linear_anneal(self._initial_reward_shaping_factor, timesteps,
