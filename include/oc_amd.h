@@ -934,6 +934,74 @@ int oc_multi_agent_step_sample_plan(const OcBatch* batch, int horizon, int with_
                                     int num_pots, uint32_t options, int use_phi, int event_sink, const OcStartSpec* start,
                                     char* out, size_t out_size);
 
+/*
+ * The behaviour-cloning partner (ABI 6: entry points added beside the others; no existing signature, struct or option changes, so the
+ * version stays) — the "bc" agent of the reference's PPO-with-BC-partner training (human_aware_rl/rllib/rllib.py:262-281: per
+ * episode a bc_factor coin decides whether the env has a partner, a shuffle decides which player it plays) and its model, the small
+ * dense network on featurize_state of human_aware_rl/imitation/behavior_cloning_tf2.py (in_dim -> h1 -> h2 -> 6 logits, ReLU).
+ * oc_partner_logits seats the partners and writes their logits INTO the learner's logits array, so that the sampler that follows
+ * (oc_multi_agent_step_sample, oc_sample_actions) draws the partner's action from its own policy and the learner's from the
+ * learner's: one launch (k_partner_logits, csrc/partner.hpp) in front of the step, whose kernels stay as they are.
+ *
+ * Seating stream.  For global env g = env_offset + e and the caller's 64-bit step counter t = step:
+ *   r[0..3] = philox4x32_10(counter = {t_lo, g_lo, g_hi, t_hi}, key = {seed_lo, seed_hi ^ 0x53454154 ("SEAT")})
+ *   an env is reseated when d_done == NULL or d_done[e] != 0;
+ *   a reseated env gets a partner iff (float)(r[0] >> 8) * 2^-24 < bc_factor (the product is exact in f32, 0 <= u < 1: bc_factor 0
+ *   seats nobody, 1 everybody); the partner plays player r[1] & 1: d_seat[e] = r[1] & 1, and d_seat[e] = 255 without a partner;
+ *   every other env keeps its seat (any value above 1 reads as "no partner").  Words 2 and 3 are reserved.
+ * All counters are used in full 64-bit width, with a carry from g_lo into g_hi inside a batch, as for the other streams.
+ *
+ * Logits.  For every env with a seat p (0 or 1) AFTER the reseat of this same call, d_logits[e][p][0..5] receives the network's
+ * output on d_features[e][p][:].  Nothing else is written: the other player's six logits and an unseated env's twelve keep the
+ * caller's bytes.
+ *
+ * Arithmetic.  All f32.  With x the feature row, every unit is an fmaf chain over its inputs in ascending index that starts from
+ * the bias, every hidden unit followed by max(., 0):
+ *   a1_j = max(fmaf(x_{in_dim-1}, w1[in_dim-1][j], ... fmaf(x_1, w1[1][j], fmaf(x_0, w1[0][j], b1_j)) ...), 0)      j < h1
+ *   a2_j = max(the same chain over a1_0 .. a1_{h1-1} with w2, from b2_j, 0)                                         j < h2
+ *   logit_j = the same chain over a2_0 .. a2_{h2-1} with w3, from b3_j                                              j < 6
+ * one rounding per step, no wider accumulator.  This is what gfx950's f32-input MFMA computes bit for bit when the K steps are issued
+ * in order with the bias as the initial accumulator (v_mfma_f32_32x32x2_f32); the kernel pads the hidden widths to its tile of 32
+ * units with zero weights and zero biases, which add exact zeros to a chain.  (max(., 0) of a NaN is 0, as v_max_f32 gives it; a
+ * chain whose value is exactly -0 may come out as +0, since a padded step adds +0 to it.)
+ */
+typedef struct OcDensePolicy {     /* two hidden ReLU layers, 6 logits; all f32, row-major [in][out] (the Keras Dense layout) */
+    const float *d_w1, *d_b1;      /* [in_dim][h1], [h1] */
+    const float *d_w2, *d_b2;      /* [h1][h2], [h2] */
+    const float *d_w3, *d_b3;      /* [h2][6], [6] */
+    int in_dim, h1, h2;            /* in_dim = 2*(num_pots*10+26)+4 of the call; 1 <= h1, h2 <= 64 */
+} OcDensePolicy;
+
+typedef struct OcPartnerSeats {
+    uint8_t* d_seat;               /* [n_envs] in/out: 0 or 1 = the player the partner plays, 255 = no partner */
+    const uint8_t* d_done;         /* [n_envs] done mask of the previous step; NULL: every env is reseated */
+    float bc_factor;               /* in [0, 1] */
+    uint64_t seed; int64_t env_offset; int64_t step;
+} OcPartnerSeats;
+
+/*
+ * oc_partner_logits — the reseat and the partners' forward pass, one launch.  Of the batch only n_envs is read.
+ *   d_features  [n_envs][2][2 * (num_pots * 10 + 26) + 4] f32 as oc_featurize writes it (of the CURRENT states), 16-byte aligned
+ *   d_logits    [n_envs][2][6] f32, 8-byte aligned (a row of six is written as 8-byte stores; OcActionSampler, which reads the
+ *               array next, asks 16 of it); in/out as described under "Logits"
+ *   the six weight and bias arrays: 4-byte aligned; d_seat and d_done at any address
+ * OC_EINVAL, before any device call, with this entry point's name in front of the message: a NULL batch, policy, seats, d_features,
+ * d_logits, weight or bias array or d_seat; a misaligned array; policy.in_dim different from the call's feature length; h1 or h2
+ * outside 1..64; bc_factor outside [0, 1] or NaN; num_pots outside 0..4; n_envs < 0.
+ */
+int oc_partner_logits(const OcBatch* batch, const OcDensePolicy* policy, const OcPartnerSeats* seats, const float* d_features,
+                      int num_pots, float* d_logits, void* stream);
+
+/*
+ * oc_partner_logits_plan — what oc_partner_logits would launch, as text:
+ *   "k_partner_logits grid=256, 256 lanes (4 wavefronts x 64 envs), 32 x 32 x 2 f32 MFMA, K 96 -> 64 -> 64 -> 32 (h1 = 64, h2 = 64, 6 logits, zero-padded), 100224 B LDS"
+ *   "nothing to launch (no envs)"
+ * The checks that need no array apply (batch, policy: in_dim, h1, h2; num_pots); usable without a GPU, like the other plan calls;
+ * refusals carry oc_partner_logits's name.
+ *   out, out_size caller's text buffer (>= 256 bytes holds every answer)
+ */
+int oc_partner_logits_plan(const OcBatch* batch, const OcDensePolicy* policy, int num_pots, char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,8 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_observation_plan", "oc_step_plan", "oc_potential_plan", "oc_featurize_plan", "oc_rollout_featurize_plan", "oc_multi_agent_step_featurize_plan",
            "oc_step_server_open", "oc_step_server_requests", "oc_step_server_responses", "oc_step_server_resume",
            "oc_step_server_play", "oc_step_server_sync", "oc_step_server_steps", "oc_step_server_close",
-           "oc_sample_actions", "oc_multi_agent_step_sample", "oc_multi_agent_step_sample_plan")
+           "oc_sample_actions", "oc_multi_agent_step_sample", "oc_multi_agent_step_sample_plan",
+           "oc_partner_logits", "oc_partner_logits_plan")
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
 
 
@@ -69,6 +70,16 @@ class OcRecordSink(ctypes.Structure):
 class OcActionSampler(ctypes.Structure):
     _fields_ = [("d_logits", ctypes.c_void_p), ("d_actions_out", ctypes.c_void_p), ("d_logp_out", ctypes.c_void_p),
                 ("seed", ctypes.c_uint64), ("env_offset", ctypes.c_int64), ("step", ctypes.c_int64), ("mode", ctypes.c_uint32)]
+
+
+class OcDensePolicy(ctypes.Structure):
+    _fields_ = [("d_w1", ctypes.c_void_p), ("d_b1", ctypes.c_void_p), ("d_w2", ctypes.c_void_p), ("d_b2", ctypes.c_void_p),
+                ("d_w3", ctypes.c_void_p), ("d_b3", ctypes.c_void_p), ("in_dim", ctypes.c_int), ("h1", ctypes.c_int), ("h2", ctypes.c_int)]
+
+
+class OcPartnerSeats(ctypes.Structure):
+    _fields_ = [("d_seat", ctypes.c_void_p), ("d_done", ctypes.c_void_p), ("bc_factor", ctypes.c_float), ("seed", ctypes.c_uint64),
+                ("env_offset", ctypes.c_int64), ("step", ctypes.c_int64)]
 
 
 class OcAmdError(RuntimeError):
@@ -192,6 +203,11 @@ def load():
                                              vp, vp, vp, i32, u32, sp, ep, vp]
     L.oc_multi_agent_step_sample_plan.restype = i32
     L.oc_multi_agent_step_sample_plan.argtypes = [bp, i32, i32, i32, i32, i32, u32, i32, i32, sp, ctypes.c_char_p, ctypes.c_size_t]
+    dpp = ctypes.POINTER(OcDensePolicy)
+    L.oc_partner_logits.restype = i32
+    L.oc_partner_logits.argtypes = [bp, dpp, ctypes.POINTER(OcPartnerSeats), vp, i32, vp, vp]
+    L.oc_partner_logits_plan.restype = i32
+    L.oc_partner_logits_plan.argtypes = [bp, dpp, i32, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

@@ -3,9 +3,12 @@ human_aware_rl/rllib/rllib.py:112-438) on top of the accelerated path.
 
 `VecOvercookedMultiAgent` is that environment for N envs resident in HBM: per batched step one
 `oc_multi_agent_step` call (step -> phi(s') -> per-agent training reward sparse + factor * (phi(s') - phi(s) | shaped)
--> restart of finished envs -> observation), no host synchronisation.  Every env has two learning ("ppo") agents;
-`bc` partners need a behaviour-cloning model, which is outside this package — their observation (`featurize_state`)
-is available through `observations("bc")`.
+-> restart of finished envs -> observation), no host synchronisation.  By default every env has two learning ("ppo") agents.
+With `bc_policy` (a `partner.DensePolicy`: the reference's behaviour-cloning network on featurize_state) an env is seated like
+the reference's (rllib.py:262-281): at every episode start a `bc_factor` coin decides whether it has a "bc" partner and which
+player that partner plays — drawn on the library's counter-based stream, not np.random — and `step_sampled` evaluates the
+partners' network into the learner's logits array (`oc_partner_logits`, one launch in front of the step) before the actions are
+drawn.  The partner's observation alone is available through `observations("bc")`.
 
 With `obs="features"` the same call also returns featurize_state of the states the next step starts from (`obs="both"`: the
 lossless encoding and the features), through `oc_multi_agent_step_featurize` — one kernel for single-layout batches.
@@ -185,13 +188,22 @@ class VecOvercookedMultiAgent:
 
     def __init__(self, layouts, n_envs, horizon=400, reward_shaping_factor=0.0, reward_shaping_horizon=0, use_phi=True,
                  gamma=0.99, obs="ppo", obs_dtype=None, device="cuda", random_start_pos=False, rnd_obj_prob_thresh=0.0,
-                 num_pots=2, counter_goals="none", one_kernel=False, **venv_kwargs):
+                 num_pots=2, counter_goals="none", one_kernel=False, bc_policy=None, bc_schedule=None, **venv_kwargs):
         import torch
 
         from . import _lib
         from .vec_env import VecOvercookedEnv
 
         self._torch, self._lib = torch, _lib
+        # the partner (checked before anything is allocated): its network reads the feature buffer the step call writes
+        self.bc_policy = bc_policy
+        self.bc_schedule = _checked_schedule(bc_schedule or OvercookedMultiAgent.self_play_bc_schedule)
+        if bc_policy is not None:
+            if obs not in ("features", "both"):
+                raise ValueError("a bc_policy needs obs=\"features\" or \"both\" (its input is the feature buffer), not %r" % (obs,))
+            if bc_policy.in_dim != 2 * (int(num_pots) * 10 + 26) + 4:
+                raise ValueError("bc_policy.in_dim = %d, but this env's feature length (num_pots = %d) is %d"
+                                 % (bc_policy.in_dim, num_pots, 2 * (int(num_pots) * 10 + 26) + 4))
         venv_kwargs.pop("auto_reset", None)
         self.venv = VecOvercookedEnv(layouts, n_envs, horizon=horizon, device=device, auto_reset=False,
                                      random_start_pos=random_start_pos, rnd_obj_prob_thresh=rnd_obj_prob_thresh,
@@ -221,6 +233,12 @@ class VecOvercookedMultiAgent:
         self._phi_args = None
         self.sample_step = 0  # step_sampled / sample_actions: the counter of the next draw (reset() leaves it alone)
         self._sampled = None
+        # seat[e]: the player the bc partner of env e plays (0 / 1), 255 = no partner; drawn by partner_logits()
+        self.seat = torch.full((self.n_envs,), 255, dtype=torch.uint8, device=dev)
+        self._reseat_all = True  # construction and reset(): every env is seated anew at the next partner_logits()
+        self._feat_current = False  # the feature buffer holds featurize_state of the current states
+        self._seats = _lib.OcPartnerSeats()
+        self.anneal_bc_factor(0)
         if self.use_phi:
             # phi of each layout's STANDARD start state (what a standard reset carries into phi_cur), from a probe batch of
             # one env per layout — the training batch itself may already hold drawn start states (epoch 0)
@@ -257,16 +275,22 @@ class VecOvercookedMultiAgent:
         raise ValueError("Unsupported agent type {0}".format(kind))
 
     def reset(self):
+        self._reseat_all, self._feat_current = True, False
         if self._random_starts:
             self.venv.reset(random_start_pos=self.random_start_pos, rnd_obj_prob_thresh=self.rnd_obj_prob_thresh)
             if self.use_phi:
                 self.venv.potential(self.gamma, out=self.phi_cur)
-            return self.observations()
+            return self._observe()
         self.venv.reset()
         if self.use_phi:
             lid = self.venv.layout_id
             self.phi_cur.copy_(self.phi_start[lid.long() & 0xFFFF] if lid is not None else self.phi_start.expand(self.n_envs))
-        return self.observations()
+        return self._observe()
+
+    def _observe(self):
+        out = self.observations()
+        self._feat_current = self._with_features
+        return out
 
     def _call_args(self):
         """What step() hands to oc_multi_agent_step beside the arrays every call has: (observation buffer or None, obs_dtype
@@ -347,6 +371,7 @@ class VecOvercookedMultiAgent:
             rc = v._launch(v.lib.oc_multi_agent_step, *args, start, sink)
             self._lib.check(rc, "oc_multi_agent_step")
         v._advance(1)
+        self._feat_current = feat is not None
         infos = {"sparse_r_by_agent": v.rewards[:, 0:2], "shaped_r_by_agent": v.rewards[:, 2:4], "flags": v.flags,
                  "ep_returns": self.ep_returns}  # episode totals so far; final where done (the reset cleared the live ones)
         if self.use_phi:
@@ -392,11 +417,62 @@ class VecOvercookedMultiAgent:
         actions (uint8 [n_envs, 2]) and their log-probabilities (float32 [n_envs, 2]) in infos["actions"] / infos["logp"],
         persistent buffers.  The draws are a function of (the env's seed, its env offset + env, sample_step): `sample_step`
         starts at 0, goes up by one per call, and reset() leaves it alone.  A row of logits with a NaN, a +inf or nothing but
-        -inf draws action 255 with logp NaN: the env is flagged OC_F_BAD_ACTION and stays as it is."""
+        -inf draws action 255 with logp NaN: the env is flagged OC_F_BAD_ACTION and stays as it is.
+        With a bc_policy, partner_logits(logits) runs first: the caller's `logits` tensor is OVERWRITTEN at the partner seats
+        (logits[e, seat[e]] of every env with a partner) with the partner's own logits, the draw follows from those, and
+        infos["seat"] is the seat tensor, so that a learner can drop the partner's samples."""
+        if self.bc_policy is not None:
+            self.partner_logits(logits)
         actions, logp, s = self._sampler(logits, greedy)
         out, shaped, done, infos = self._step(None, s)
         infos["actions"], infos["logp"] = actions, logp
+        if self.bc_policy is not None:
+            infos["seat"] = self.seat
         return out, shaped, done, infos
+
+    def partner_logits(self, logits):
+        """The partners' part of step_sampled(), alone (oc_partner_logits, one launch): envs whose previous step was done — every
+        env at the first call and after reset() — are seated anew from the current `bc_factor` on the seating stream of
+        include/oc_amd.h at (the env's seed, its env offset + env, sample_step), and for every env with a partner the network's six
+        logits on featurize_state of the CURRENT state of the partner's player overwrite `logits[e, seat[e]]`; nothing else of
+        `logits` is written.  Does not advance `sample_step`.  Returns `seat` (uint8 [n_envs]: 0 / 1 the partner's player, 255 none)."""
+        import ctypes
+
+        v, torch = self.venv, self._torch
+        if self.bc_policy is None:
+            raise ValueError("partner_logits needs a bc_policy")
+        if logits.dtype != torch.float32 or logits.shape != (self.n_envs, 2, 6) or not logits.is_contiguous() \
+                or logits.device != v.state.device:
+            raise ValueError("logits must be a contiguous float32 [n_envs, 2, 6] tensor on %s" % v.device)
+        if not self._feat_current:  # (before the first step and after reset(): the step call itself keeps the buffer current)
+            self.observations("features")
+            self._feat_current = True
+        s = self._seats
+        s.d_seat, s.d_done = self.seat.data_ptr(), None if self._reseat_all else self.done.data_ptr()
+        s.bc_factor, s.seed, s.env_offset, s.step = float(self.bc_factor), v.seed, v.env_offset, self.sample_step
+        rc = v._launch(v.lib.oc_partner_logits, v._bref, self.bc_policy._ref, ctypes.byref(s), self._feat_buffer().data_ptr(),
+                       self.num_pots, logits.data_ptr())
+        self._lib.check(rc, "oc_partner_logits")
+        self._reseat_all = False
+        return self.seat
+
+    def plan_partner(self):
+        """What partner_logits() launches, in oc_partner_logits_plan's words."""
+        import ctypes
+
+        if self.bc_policy is None:
+            raise ValueError("plan_partner needs a bc_policy")
+        out = ctypes.create_string_buffer(320)
+        rc = self.venv.lib.oc_partner_logits_plan(self.venv._bref, self.bc_policy._ref, self.num_pots, out, len(out))
+        self._lib.check(rc, "oc_partner_logits_plan")
+        return out.value.decode()
+
+    def anneal_bc_factor(self, timesteps):
+        """bc_factor = the bc schedule at `timesteps` (rllib.py:369-384), as OvercookedMultiAgent.anneal_bc_factor"""
+        self.set_bc_factor(schedule_value(self.bc_schedule, timesteps))
+
+    def set_bc_factor(self, factor):
+        self.bc_factor = factor
 
     def plan_sampled(self):
         """The path and kernel instance the next step_sampled() runs, in oc_multi_agent_step_sample_plan's words."""
