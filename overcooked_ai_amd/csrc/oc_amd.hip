@@ -20,7 +20,8 @@
 //   train_obs.hpp       the training step with its observation in one kernel: k_train_step_obs
 //   train_feat.hpp      the training step with the featurize_state observation in one kernel: k_train_step_feat
 //   sample.hpp          both players' actions drawn from policy logits: sample_env, k_sample_actions
-//   train_sample.hpp    the training step that draws its actions: the SAMPLE = true launches, oc_sample_actions, oc_multi_agent_step_sample (+ _plan)
+//   train_dispatch.hpp  host only: the training-step family — one call record, one plan, one launch path; oc_multi_agent_step,
+//                       oc_multi_agent_step_featurize, oc_multi_agent_step_sample, their *_plan entry points and oc_sample_actions
 //   stores_only.hpp     the output stores of a rollout and nothing else: k_output_stores_only (oc_output_stores_only)
 //   observation_plan.hpp  host only: the observation geometry and the plans of oc_encode_lossless / oc_rollout_encode / oc_rollout_featurize
 //   this file           launch dispatch and the extern "C" entry points declared in include/oc_amd.h: oc_rollout_random,
@@ -968,459 +969,9 @@ int oc_reset(const OcBatch* b, void* d_state, const uint8_t* d_mask, float* d_ep
 
 }  // extern "C"
 
-namespace {
-// ---- oc_multi_agent_step: the call is planned first (plan_train_step: every check, then the path and its kernel instance;
-//      no launch, no device memory), then launched from that plan — or, by oc_multi_agent_plan, described.  The paths:
-//        k_train_step_obs<MAXP, T, NWV>          the step and its observation in one kernel (train_step_obs)
-//        k_train_step1<UNIFORM, MAXP, LAY_LDS>   the step in one kernel on the wire format, then oc_encode_lossless (train_step_fused)
-//        k_train_step<UNIFORM, EV>               the same with event counters or on 65..128 cells (train_step_fused)
-//        the sequence of entry points            any other table (train_step_general)
-struct TrainStep {
-    const OcBatch* b;
-    int n_obj;
-    void* d_state;
-    const uint8_t* d_actions;
-    float* d_rewards;
-    uint8_t* d_flags;
-    float *d_ep_returns, *d_ep_returns_out;
-    const uint8_t* d_plan_blob;  // the potential: plan tables, phi tables, phi(s'), phi(s), phi(start)
-    const uint32_t* d_plan_off;
-    const uint8_t* d_phi_tables;
-    double *d_phi_next, *d_phi_cur;
-    const double* d_phi_start;
-    double reward_shaping_factor, *d_shaped;
-    uint8_t* d_done;
-    void* d_obs;
-    int obs_dtype, horizon;
-    const OcStartSpec* start;
-    StartArgs sa;
-    EvArgs ea;
-    hipStream_t stream;
-};
-
-// How k_train_step_obs (train_obs.hpp) would run a call: envs per template, wavefronts per workgroup, envs per private image,
-// dynamic LDS.  nwv = 0: it does not apply.
-struct TrainObsShape {
-    int unit = 0, nwv = 0, gmax = 0;
-    size_t smem = 0;
-};
-// What a plan needs to know of a call's arrays: which ones are there, never where (oc_multi_agent_plan has no more than that
-// to give)
-struct TrainArrays {
-    bool state, actions, rewards, flags, shaped, shaped_aligned16, done;
-    bool phi_tables, phi_rest;  // use_phi: the phi tables / the plan tables and the three phi buffers
-    bool ep_returns, ep_returns_out;  // (no choice depends on them: read by describe_train_plan only, for the sequence's copy)
-    bool quads_aligned16 = true;      // d_rewards, d_ep_returns and d_ep_returns_out
-    bool obs, obs_aligned16;
-    bool events;  // an event sink with counters or masks
-};
-// The plan of one oc_multi_agent_step call: every check, every choice; no launch, no device memory
-struct TrainPlan {
-    int rc = OC_OK;  // the call is refused with this code (the message: oc_last_error)
-    enum Path { OBS, FUSED, GENERAL } path = GENERAL;  // k_train_step_obs / k_train_step1 or k_train_step, then the observation / the sequence
-    int n_obj = 0;
-    StartArgs sa = {};
-    TrainObsShape sh;    // OBS
-    bool lean = false;   // FUSED: k_train_step1 (else k_train_step)
-    bool uniform = false, lay_lds = false, ev = false;  // FUSED: the instance's UNIFORM, LAY_LDS (k_train_step1), EV (k_train_step)
-    int maxp = 2;        // OBS, FUSED: the instance's MAXP
-};
-// Round 5: the step AND its observation in one kernel for single-layout batches (at most two pots, two players, 64 cells, no
-// event sink) that give at least half of the CUs a workgroup of 256 envs (smaller batches: the observation kernel spreads
-// over all CUs)
-bool train_obs_wanted(const OcBatch* b, int n_obj, const TrainArrays& have, int obs_dtype) {
-    static const bool no_fused_obs = tuning_set("OC_TRAIN_NO_FUSED_OBS");
-    return have.obs && b->n_layouts == 1 && b->width * b->height <= 64 && !have.events && n_obj <= STEP1_MAX_PLANES && !step_no_lean() &&
-           !no_fused_obs && obs_dtype_ok(obs_dtype) && have.obs_aligned16 && b->n_envs >= (simd_count() / 8) * BLOCK;
-}
-TrainObsShape train_obs_shape(const OcBatch* b, int n_obj, const TrainArrays& have, int obs_dtype) {
-    TrainObsShape sh;
-    if (!train_obs_wanted(b, n_obj, have, obs_dtype)) return sh;
-    const ObsGeometry geo(b->width, b->height, obs_dtype);
-    const int unit = geo.unit;
-    const size_t fixed = (size_t)n_obj * BLOCK * 16 + geo.env_bytes * unit + (size_t)4 * BLOCK * 16;
-    const size_t budget = 150 * 1024;
-    // wavefronts per workgroup: 16 (4 owners, 4 helpers, 8 encoders; round 6) for u8 observations whose private images
-    // still hold >= 6 envs then (cramped_room-sized grids: the encode loop there is bound by what the wavefronts of a
-    // CU can issue, not by bytes), else 8
-    static const int forced_w = tuning_int("OC_TRAIN_OBS_WAVES", 0), forced_g = tuning_int("OC_TRAIN_OBS_G", 0);
-    for (int w : {16, 8}) {
-        if (forced_w && w != forced_w) continue;
-        if (!forced_w && w == 16 && obs_dtype != OC_OBS_U8) continue;
-        int g = geo.envs_per_image(fixed, budget, w);
-        if (forced_g > 0 && forced_g < g) g = forced_g;
-        g = geo.whole_units(g);
-        if (w == 16 && g < 6 && !forced_w) continue;  // (measured: 7-env images 22.0 -> 19.5 us, 3-env images 31.8 -> 37.6)
-        if (g >= unit && g >= 2) {  // (one env per image — 9x5 f32 — measured slower than the two kernels: 123-127 vs 116-122 us)
-            sh.unit = unit; sh.nwv = w; sh.gmax = g;
-            sh.smem = fixed + (size_t)w * g * geo.env_bytes;
-            break;
-        }
-    }
-    return sh;
-}
-
-// Which of oc_multi_agent_step's paths, and which kernel instance of it, serves a call: the one place that reads the batch
-// and the call for it.  The train_step_* functions below launch what it returns; oc_multi_agent_plan puts it into words.
-TrainPlan plan_train_step(const OcBatch* b, const TrainArrays& have, int obs_dtype, int horizon, const OcStartSpec* start,
-                          const char* who = "oc_multi_agent_step") {  // who: the entry point a refusal names
-    TrainPlan p;
-    const auto refused = [&p](int rc) { p.rc = rc; return p; };
-    if (!have.done) return refused(refuse(who, "d_done is required (it is the reset mask)"));
-    if (int rc = check_start(who, start, &p.sa, b)) return refused(rc);
-    if (int rc = check_batch(b, &p.n_obj)) return refused(rc);
-    // at most two pots and two players: the whole step in one kernel
-    const bool fused = b->max_pots >= 1 && b->max_pots <= 2 && (b->batch_flags & OC_BATCH_TWO_PLAYERS) != 0;
-    if (!have.state || !have.actions || !have.rewards || !have.flags || (fused && !have.shaped))
-        return refused(refuse(who, fused ? "NULL state/actions/rewards/flags/shaped pointer" : "NULL state/actions/rewards/flags pointer"));
-    if (fused && have.phi_tables && !have.phi_rest) return refused(refuse(who, "use_phi needs the plan tables and the three phi buffers"));
-    if (int rc = check_horizon(who, horizon)) return refused(rc);
-    if (fused && !have.shaped_aligned16) return refused(refuse(who, "d_shaped must be 16-byte aligned"));
-    if (!have.quads_aligned16) return refused(refuse(who, "d_rewards, d_ep_returns and d_ep_returns_out must be 16-byte aligned"));
-    if (!fused) return p;
-    p.path = TrainPlan::FUSED;
-    p.uniform = b->n_layouts == 1;
-    if (b->n_envs > 0) {
-        p.sh = train_obs_shape(b, p.n_obj, have, obs_dtype);
-        if (p.sh.nwv) {
-            p.path = TrainPlan::OBS;
-            p.maxp = b->max_pots == 1 ? 1 : 2;
-            return p;
-        }
-    }
-    p.lean = !have.events && p.n_obj <= STEP1_MAX_PLANES && !step_no_lean();  // the transition on the wire format itself (step_one.hpp)
-    if (p.lean) {
-        p.maxp = p.uniform && b->max_pots == 1 ? 1 : 2;
-        p.lay_lds = b->n_layouts <= LDS_LAYOUT_MAX;
-    } else {
-        p.ev = have.events;
-    }
-    return p;
-}
-
-// path 1: the step and its observation in one kernel (k_train_step_obs)
-int train_step_obs(const TrainStep& a, const TrainPlan& p) {
-    const OcBatch* b = a.b;
-    const TrainObsShape& sh = p.sh;
-    const dim3 grid(grid_for(b->n_envs));
-#define GOTO(MP, T, NW)                                                                                                 \
-    do {                                                                                                                \
-        if (!want_lds(k_train_step_obs<MP, T, NW>, sh.smem)) break;                                                     \
-        hipLaunchKernelGGL((k_train_step_obs<MP, T, NW>), grid, dim3(NW * 64), sh.smem, a.stream, b->d_layouts,         \
-                           (uint4*)a.d_state, a.d_actions, (float4*)a.d_rewards, a.d_flags, (float4*)a.d_ep_returns,    \
-                           (float4*)a.d_ep_returns_out, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_phi_next,      \
-                           a.d_phi_cur, a.d_phi_start, a.reward_shaping_factor, a.d_shaped, a.d_done, (uint8_t*)a.d_obs, \
-                           b->n_envs, b->width, b->height, a.n_obj, a.horizon, sh.unit, sh.gmax, a.sa);                 \
-    } while (0)
-#define GOTOW(MP, T) do { if (sh.nwv == 16) GOTO(MP, T, 16); else GOTO(MP, T, 8); } while (0)
-    if (a.obs_dtype == OC_OBS_U8) { if (p.maxp == 1) GOTOW(1, uint8_t); else GOTOW(2, uint8_t); }
-    else { if (p.maxp == 1) GOTOW(1, float); else GOTOW(2, float); }
-#undef GOTOW
-#undef GOTO
-    return check_launch("oc_multi_agent_step");
-}
-
-// path 2: the whole step in one kernel (k_train_step1; k_train_step with event counters or a grid above 64 cells), then the
-// observation
-int train_step_fused(const TrainStep& a, const TrainPlan& p) {
-    const OcBatch* b = a.b;
-    if (b->n_envs > 0) {
-        const dim3 grid(grid_for(b->n_envs)), block(BLOCK);
-        if (p.lean) {
-            const size_t smem1 = (size_t)a.n_obj * BLOCK * sizeof(uint4);
-#define GOT1(U, MP, LL)                                                                                                  \
-    hipLaunchKernelGGL((k_train_step1<U, MP, LL>), grid, block, smem1, a.stream, b->d_layouts, b->n_layouts, b->d_layout_id, \
-                       (uint4*)a.d_state, a.d_actions, (float4*)a.d_rewards, a.d_flags, (float4*)a.d_ep_returns,         \
-                       (float4*)a.d_ep_returns_out, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_phi_next,           \
-                       a.d_phi_cur, a.d_phi_start, a.reward_shaping_factor, a.d_shaped, a.d_done, b->n_envs, b->width,   \
-                       b->height, a.n_obj, a.horizon, a.sa)
-            if (p.uniform && p.maxp == 1) GOT1(true, 1, true);
-            else if (p.uniform) GOT1(true, 2, true);
-            else if (p.lay_lds) GOT1(false, 2, true);
-            else GOT1(false, 2, false);
-#undef GOT1
-        } else {
-            const size_t smem = (size_t)a.n_obj * 16 * BLOCK * sizeof(uint16_t);
-#define GOT(U, EV)                                                                                                    \
-    do {                                                                                                              \
-        if (!want_lds(k_train_step<U, 2, U, false, EV>, smem)) break;                                                 \
-        hipLaunchKernelGGL((k_train_step<U, 2, U, false, EV>), grid, block, smem, a.stream, b->d_layouts,             \
-                           b->n_layouts, b->d_layout_id, (uint4*)a.d_state, a.d_actions, (float4*)a.d_rewards,        \
-                           a.d_flags, (float4*)a.d_ep_returns, (float4*)a.d_ep_returns_out, a.d_plan_blob,            \
-                           a.d_plan_off, a.d_phi_tables, a.d_phi_next, a.d_phi_cur, a.d_phi_start,                    \
-                           a.reward_shaping_factor, a.d_shaped, a.d_done, b->n_envs, b->width, b->height, a.n_obj,    \
-                           a.horizon, a.sa, a.ea);                                                                    \
-    } while (0)
-            if (p.uniform) { if (p.ev) GOT(true, true); else GOT(true, false); }
-            else { if (p.ev) GOT(false, true); else GOT(false, false); }
-#undef GOT
-        }
-        if (int rc = check_launch("oc_multi_agent_step")) return rc;
-    }
-    if (a.d_obs) return oc_encode_lossless(b, a.d_state, a.d_obs, a.obs_dtype, a.horizon, a.stream);
-    return OC_OK;
-}
-
-// path 3, any table: oc_step (finished envs are restarted below: their counters clear at the DONE step), potential, shaping,
-// restart, observation
-int train_step_general(const TrainStep& a) {
-    const OcBatch* b = a.b;
-    if (b->n_envs > 0) {
-        StartArgs none;
-        start_args(nullptr, &none);
-        launch_step(b, a.n_obj, a.d_state, a.d_state, a.d_actions, a.d_rewards, a.d_flags, a.d_ep_returns, a.horizon, 0u, a.stream, none, a.ea);
-        if (int rc = check_launch("oc_multi_agent_step")) return rc;
-    }
-    if (a.d_phi_tables) {
-        if (int rc = oc_potential(b, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_state, a.d_phi_next, a.stream)) return rc;
-    }
-    if (int rc = oc_shape_rewards(b, a.d_rewards, a.d_flags, a.d_phi_tables ? a.d_phi_next : nullptr, a.d_phi_cur, a.d_phi_start,
-                                  a.reward_shaping_factor, a.d_shaped, a.d_done, a.stream))
-        return rc;
-    if (a.d_ep_returns && a.d_ep_returns_out && b->n_envs > 0) {
-        if (hipMemcpyAsync(a.d_ep_returns_out, a.d_ep_returns, (size_t)b->n_envs * 4 * sizeof(float), hipMemcpyDeviceToDevice,
-                           a.stream) != hipSuccess)
-            return fail(OC_ELAUNCH, "oc_multi_agent_step: copy of the episode returns failed");
-    }
-    if (const OcStartSpec* start = a.start) {  // finished envs restart from drawn states; d_phi_cur = the potential of what every env starts the next step from
-        if (start->regen_count && b->n_layouts > 1) {  // ... on layouts drawn for their new episodes
-            if (int rc = oc_regen_layouts(b, const_cast<uint16_t*>(b->d_layout_id), a.d_done, 0xFF, start, a.stream)) return rc;
-        }
-        if (int rc = oc_reset_random(b, a.d_state, a.d_done, a.d_ep_returns, start->seed, start->env_offset, start->epoch,
-                                     start->random_start_pos, start->rnd_obj_prob_thresh, a.stream))
-            return rc;
-        if (a.d_phi_tables) {
-            if (int rc = oc_potential(b, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_state, a.d_phi_cur, a.stream)) return rc;
-        }
-    } else {
-        if (int rc = oc_reset(b, a.d_state, a.d_done, a.d_ep_returns, a.stream)) return rc;
-    }
-    if (a.d_obs) return oc_encode_lossless(b, a.d_state, a.d_obs, a.obs_dtype, a.horizon, a.stream);
-    return OC_OK;
-}
-
-TrainArrays train_arrays_of(const void* d_state, const void* d_actions, const void* d_rewards, const void* d_flags, const void* d_ep_returns,
-                            const void* d_ep_returns_out, const void* d_plan_blob, const void* d_plan_off, const void* d_phi_tables,
-                            const void* d_phi_next, const void* d_phi_cur, const void* d_phi_start, const void* d_shaped,
-                            const void* d_done, const void* d_obs, bool events) {
-    TrainArrays have = {};
-    have.state = d_state != nullptr; have.actions = d_actions != nullptr; have.rewards = d_rewards != nullptr; have.flags = d_flags != nullptr;
-    have.shaped = d_shaped != nullptr; have.shaped_aligned16 = aligned16(d_shaped); have.done = d_done != nullptr;
-    have.phi_tables = d_phi_tables != nullptr;
-    have.phi_rest = d_plan_blob && d_plan_off && d_phi_next && d_phi_cur && d_phi_start;
-    have.ep_returns = d_ep_returns != nullptr; have.ep_returns_out = d_ep_returns_out != nullptr;
-    have.quads_aligned16 = aligned16(d_rewards) && aligned16(d_ep_returns) && aligned16(d_ep_returns_out);
-    have.obs = d_obs != nullptr; have.obs_aligned16 = aligned16(d_obs);
-    have.events = events;
-    return have;
-}
-
-// A plan in words (oc_multi_agent_plan): up to and including '>' the kernel instance, as tests match it
-void describe_train_plan(const OcBatch* b, const TrainPlan& p, const TrainArrays& have, int obs_dtype, const OcStartSpec* start, char* out,
-                         size_t out_size) {
-    const auto tf = [](bool v) { return v ? "true" : "false"; };
-    const char* const then_obs = have.obs ? " + oc_encode_lossless" : "";
-    if (p.path == TrainPlan::GENERAL) {  // what train_step_general enqueues, in its order
-        const bool regen = start && start->regen_count && b->n_layouts > 1;
-        snprintf(out, out_size, "sequence: oc_step%s, oc_shape_rewards%s%s, %s%s%s", have.phi_tables ? ", oc_potential" : "",
-                 have.ep_returns && have.ep_returns_out ? ", copy of the episode returns" : "", regen ? ", oc_regen_layouts" : "",
-                 start ? "oc_reset_random" : "oc_reset", start && have.phi_tables ? ", oc_potential" : "", have.obs ? ", oc_encode_lossless" : "");
-    } else if (b->n_envs == 0) {
-        snprintf(out, out_size, "nothing to launch (no envs)");
-    } else if (p.path == TrainPlan::OBS) {
-        snprintf(out, out_size, "k_train_step_obs<MAXP=%d, T=%s, NWV=%d> unit=%d, G=%d, %zu B LDS", p.maxp, obs_dtype == OC_OBS_U8 ? "u8" : "f32",
-                 p.sh.nwv, p.sh.unit, p.sh.gmax, p.sh.smem);
-    } else if (p.lean) {
-        snprintf(out, out_size, "k_train_step1<UNIFORM=%s, MAXP=%d, LAY_LDS=%s>%s", tf(p.uniform), p.maxp, tf(p.lay_lds), then_obs);
-    } else {
-        snprintf(out, out_size, "k_train_step<UNIFORM=%s, EV=%s>%s", tf(p.uniform), tf(p.ev), then_obs);
-    }
-}
-// the launches of a planned oc_multi_agent_step call
-int launch_train_step(const TrainStep& a, const TrainPlan& p) {
-    if (p.path == TrainPlan::GENERAL) return train_step_general(a);
-    if (p.path == TrainPlan::OBS) return train_step_obs(a, p);
-    return train_step_fused(a, p);
-}
-
-// ---- oc_multi_agent_step_featurize: oc_multi_agent_step with featurize_state of the states the next step starts from.  Planned
-//      first (plan_train_step_featurize: oc_multi_agent_step's checks and plan, oc_featurize's checks and plan, then the choice; no
-//      launch, no device memory), then launched from that plan — or, by oc_multi_agent_step_featurize_plan, described.  The paths:
-//        k_train_step_feat<MAXP>                                   the step and its features in one kernel (train_step_feat)
-//        oc_multi_agent_step's own path, then k_featurize<LAY_LDS>  every other call with features
-struct TrainFeatPlan {
-    int rc = OC_OK;
-    enum Path { NOTHING, ONE_KERNEL, TWO_LAUNCHES } path = TWO_LAUNCHES;
-    TrainPlan step;      // oc_multi_agent_step's plan of the call (ONE_KERNEL: its checks, n_obj and start arguments)
-    FeaturizePlan feat;  // TWO_LAUNCHES: oc_featurize's
-    int maxp = 2, g = 0;  // ONE_KERNEL: the instance's MAXP, envs per private image
-    size_t smem = 0;      // ONE_KERNEL: dynamic LDS
-};
-
-// The batch size from which k_train_step_feat is taken without OC_OPT_ONE_KERNEL: a quarter of the CUs get a workgroup of 256 envs
-// (16 384 envs on MI355X).  It started from k_train_step_obs's rule (half of the CUs) and was settled by run 1 of
-// profiles/train_step_feat.txt (tools/time_train_step_feat.py): at 16 384 envs, the smallest batch measured, a call takes 11.9 us
-// with the one kernel against 17.5 us for k_train_step1 + k_featurize on cramped_room and 12.1 against 17.4 us on
-// asymmetric_advantages (65 536 envs: 15.4 against 22.3 and 16.8 against 23.3 us).  Smaller batches are not measured and stay
-// with the two launches, whose k_featurize spreads over twice as many CUs.
-inline int64_t train_feat_fill() { return (simd_count() / 16) * BLOCK; }
-
-// feat_tables: both feature plan pointers are there; feat_aligned: d_features is 16-byte aligned
-TrainFeatPlan plan_train_step_featurize(const OcBatch* b, const TrainArrays& have, bool feat_tables, bool feat_aligned, int obs_dtype,
-                                        int horizon, int num_pots, uint32_t options, const OcStartSpec* start,
-                                        const char* who = "oc_multi_agent_step_featurize") {  // who: the entry point a refusal names
-    TrainFeatPlan p;
-    const auto refused = [&p](int rc) { p.rc = rc; return p; };
-    p.step = plan_train_step(b, have, obs_dtype, horizon, start, who);
-    if (p.step.rc != OC_OK) return refused(p.step.rc);
-    if (!feat_tables) return refused(refuse(who, "d_features needs the feature plan tables (d_feat_plan_blob, d_feat_plan_off)"));
-    if (num_pots < 0 || num_pots > 4) return refused(refuse(who, "num_pots must be in 0..4"));
-    if (!(b->batch_flags & OC_BATCH_TWO_PLAYERS)) return refused(refuse(who, "d_features needs 2-player layouts"));
-    if (!feat_aligned) return refused(refuse(who, "d_features must be 16-byte aligned"));
-    if (b->n_envs == 0) { p.path = TrainFeatPlan::NOTHING; return p; }
-    p.feat = plan_featurize(b, true, true, num_pots);  // (its checks were made above, under this entry point's name)
-    if (p.feat.rc != OC_OK) return refused(p.feat.rc);
-    // one kernel: no observation array, one layout of at most 64 cells with one or two pots on the wire-format step (no event
-    // sink), a batch that fills the device (or OC_OPT_ONE_KERNEL), and private images of at least 8 envs within the LDS budget
-    const TrainPlan& s = p.step;
-    if (have.obs || s.path != TrainPlan::FUSED || !s.lean || !s.uniform || b->width * b->height > 64) return p;
-    if (!(b->n_envs >= train_feat_fill() || (options & OC_OPT_ONE_KERNEL))) return p;
-    const size_t budget = 150 * 1024;
-    for (int g : {32, 16, 8}) {
-        if (train_feat_lds(s.n_obj, g, num_pots) > budget) continue;
-        p.path = TrainFeatPlan::ONE_KERNEL;
-        p.maxp = b->max_pots == 1 ? 1 : 2;
-        p.g = g;
-        p.smem = train_feat_lds(s.n_obj, g, num_pots);
-        break;
-    }
-    return p;
-}
-
-// the step and its features in one kernel (k_train_step_feat)
-int train_step_feat(const TrainStep& a, const TrainFeatPlan& p, const uint8_t* d_feat_plan_blob, const uint32_t* d_feat_plan_off,
-                    float* d_features, int num_pots) {
-    const OcBatch* b = a.b;
-    const dim3 grid(grid_for(b->n_envs));
-#define FEAT_GO(MP)                                                                                                      \
-    do {                                                                                                                 \
-        if (!want_lds(k_train_step_feat<MP>, p.smem)) break;                                                             \
-        hipLaunchKernelGGL((k_train_step_feat<MP>), grid, dim3(TF_WAVES * 64), p.smem, a.stream, b->d_layouts,           \
-                           (uint4*)a.d_state, a.d_actions, (float4*)a.d_rewards, a.d_flags, (float4*)a.d_ep_returns,     \
-                           (float4*)a.d_ep_returns_out, a.d_plan_blob, a.d_plan_off, a.d_phi_tables, a.d_phi_next,       \
-                           a.d_phi_cur, a.d_phi_start, a.reward_shaping_factor, a.d_shaped, a.d_done, d_feat_plan_blob,  \
-                           d_feat_plan_off, d_features, b->n_envs, b->width, b->height, a.n_obj, num_pots, a.horizon,    \
-                           p.g, a.sa);                                                                                   \
-    } while (0)
-    if (p.maxp == 1) FEAT_GO(1);
-    else FEAT_GO(2);
-#undef FEAT_GO
-    return check_launch("oc_multi_agent_step_featurize");
-}
-
-// A plan in words (oc_multi_agent_step_featurize_plan): up to and including '>' the kernel instance, as tests match it
-void describe_train_feat_plan(const OcBatch* b, const TrainFeatPlan& p, const TrainArrays& have, int obs_dtype, const OcStartSpec* start,
-                              char* out, size_t out_size) {
-    if (p.path == TrainFeatPlan::NOTHING) {
-        snprintf(out, out_size, "nothing to launch (no envs)");
-    } else if (p.path == TrainFeatPlan::ONE_KERNEL) {
-        snprintf(out, out_size, "k_train_step_feat<MAXP=%d> G=%d, grid=%u, %zu B LDS", p.maxp, p.g, grid_for(b->n_envs), p.smem);
-    } else {
-        char step[320];
-        describe_train_plan(b, p.step, have, obs_dtype, start, step, sizeof(step));
-        snprintf(out, out_size, "%s + k_featurize<LAY_LDS=%s> grid=%u, %zu B LDS", step, p.feat.lay_lds ? "true" : "false", p.feat.grid,
-                 p.feat.smem);
-    }
-}
-}  // namespace
-
-#include "train_sample.hpp"  // oc_sample_actions, oc_multi_agent_step_sample, oc_multi_agent_step_sample_plan
+#include "train_dispatch.hpp"  // oc_multi_agent_step, oc_multi_agent_step_featurize, oc_multi_agent_step_sample (+ their plans), oc_sample_actions
 
 extern "C" {
-
-int oc_multi_agent_step(const OcBatch* b, void* d_state, const uint8_t* d_actions, float* d_rewards, uint8_t* d_flags,
-                        float* d_ep_returns, float* d_ep_returns_out, const uint8_t* d_plan_blob,
-                        const uint32_t* d_plan_off, const uint8_t* d_phi_tables, double* d_phi_next, double* d_phi_cur,
-                        const double* d_phi_start, double reward_shaping_factor, double* d_shaped, uint8_t* d_done,
-                        void* d_obs, int obs_dtype, int horizon, const OcStartSpec* start, const OcEventSink* events,
-                        void* stream) {
-    const EvArgs ea = ev_args(events, nullptr, 1u);
-    const TrainArrays have = train_arrays_of(d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
-                                             d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, d_shaped, d_done, d_obs, ev_on(ea));
-    const TrainPlan p = plan_train_step(b, have, obs_dtype, horizon, start);
-    if (p.rc != OC_OK) return p.rc;
-    const TrainStep a = {b, p.n_obj, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
-                         d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, reward_shaping_factor, d_shaped, d_done, d_obs, obs_dtype,
-                         horizon, start, p.sa, ea, (hipStream_t)stream};
-    return launch_train_step(a, p);
-}
-
-int oc_multi_agent_plan(const OcBatch* b, int horizon, int with_obs, int obs_dtype, int use_phi, int event_sink, const OcStartSpec* start,
-                        char* out, size_t out_size) {
-    if (!out || out_size == 0) return fail(OC_EINVAL, "oc_multi_agent_plan: no output buffer");
-    out[0] = 0;
-    // the call VecOvercookedMultiAgent.step makes: every required array (aligned), the named optional ones
-    TrainArrays have = {};
-    have.state = have.actions = have.rewards = have.flags = have.shaped = have.shaped_aligned16 = have.done = true;
-    have.phi_tables = have.phi_rest = use_phi != 0;
-    have.ep_returns = have.ep_returns_out = true;
-    have.obs = with_obs != 0;
-    have.obs_aligned16 = true;
-    have.events = event_sink != 0;
-    const TrainPlan p = plan_train_step(b, have, obs_dtype, horizon, start);
-    if (p.rc != OC_OK) return p.rc;
-    describe_train_plan(b, p, have, obs_dtype, start, out, out_size);
-    return OC_OK;
-}
-
-int oc_multi_agent_step_featurize(const OcBatch* b, void* d_state, const uint8_t* d_actions, float* d_rewards, uint8_t* d_flags,
-                                  float* d_ep_returns, float* d_ep_returns_out, const uint8_t* d_plan_blob,
-                                  const uint32_t* d_plan_off, const uint8_t* d_phi_tables, double* d_phi_next, double* d_phi_cur,
-                                  const double* d_phi_start, double reward_shaping_factor, double* d_shaped, uint8_t* d_done,
-                                  void* d_obs, int obs_dtype, int horizon, const uint8_t* d_feat_plan_blob,
-                                  const uint32_t* d_feat_plan_off, float* d_features, int num_pots, uint32_t options,
-                                  const OcStartSpec* start, const OcEventSink* events, void* stream) {
-    if (options & ~(uint32_t)OC_OPT_ONE_KERNEL) return refuse("oc_multi_agent_step_featurize", "options other than OC_OPT_ONE_KERNEL");
-    if (!d_features)  // no features: the call is oc_multi_agent_step
-        return oc_multi_agent_step(b, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
-                                   d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, reward_shaping_factor, d_shaped, d_done, d_obs,
-                                   obs_dtype, horizon, start, events, stream);
-    const EvArgs ea = ev_args(events, nullptr, 1u);
-    const TrainArrays have = train_arrays_of(d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
-                                             d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, d_shaped, d_done, d_obs, ev_on(ea));
-    const TrainFeatPlan p = plan_train_step_featurize(b, have, d_feat_plan_blob && d_feat_plan_off, aligned16(d_features), obs_dtype, horizon,
-                                                      num_pots, options, start);
-    if (p.rc != OC_OK || p.path == TrainFeatPlan::NOTHING) return p.rc;
-    const TrainStep a = {b, p.step.n_obj, d_state, d_actions, d_rewards, d_flags, d_ep_returns, d_ep_returns_out, d_plan_blob, d_plan_off,
-                         d_phi_tables, d_phi_next, d_phi_cur, d_phi_start, reward_shaping_factor, d_shaped, d_done, d_obs, obs_dtype,
-                         horizon, start, p.step.sa, ea, (hipStream_t)stream};
-    if (p.path == TrainFeatPlan::ONE_KERNEL) return train_step_feat(a, p, d_feat_plan_blob, d_feat_plan_off, d_features, num_pots);
-    if (int rc = launch_train_step(a, p.step)) return rc;
-    if (p.feat.lay_lds) launch_featurize<true>(p.feat, b, d_feat_plan_blob, d_feat_plan_off, d_state, d_features, num_pots, a.stream);
-    else launch_featurize<false>(p.feat, b, d_feat_plan_blob, d_feat_plan_off, d_state, d_features, num_pots, a.stream);
-    return check_launch("oc_multi_agent_step_featurize");
-}
-
-int oc_multi_agent_step_featurize_plan(const OcBatch* b, int horizon, int with_obs, int obs_dtype, int with_features, int num_pots,
-                                       uint32_t options, int use_phi, int event_sink, const OcStartSpec* start, char* out,
-                                       size_t out_size) {
-    if (!out || out_size == 0) return fail(OC_EINVAL, "oc_multi_agent_step_featurize_plan: no output buffer");
-    out[0] = 0;
-    if (options & ~(uint32_t)OC_OPT_ONE_KERNEL) return refuse("oc_multi_agent_step_featurize", "options other than OC_OPT_ONE_KERNEL");
-    if (!with_features) return oc_multi_agent_plan(b, horizon, with_obs, obs_dtype, use_phi, event_sink, start, out, out_size);
-    // the call VecOvercookedMultiAgent.step makes: every required array (aligned), the named optional ones
-    TrainArrays have = {};
-    have.state = have.actions = have.rewards = have.flags = have.shaped = have.shaped_aligned16 = have.done = true;
-    have.phi_tables = have.phi_rest = use_phi != 0;
-    have.ep_returns = have.ep_returns_out = true;
-    have.obs = with_obs != 0;
-    have.obs_aligned16 = true;
-    have.events = event_sink != 0;
-    const TrainFeatPlan p = plan_train_step_featurize(b, have, true, true, obs_dtype, horizon, num_pots, options, start);
-    if (p.rc != OC_OK) return p.rc;
-    describe_train_feat_plan(b, p, have, obs_dtype, start, out, out_size);
-    return OC_OK;
-}
 
 int oc_regen_layouts(const OcBatch* b, uint16_t* d_layout_id, const uint8_t* d_mask, uint8_t mask_bits, const OcStartSpec* start,
                      void* stream) {

@@ -245,6 +245,42 @@ def function_body(src, name):
     return m.group(0)
 
 
+TRAIN_KERNELS = {"obs": "k_train_step_obs", "feat": "k_train_step_feat", "step1": "k_train_step1", "step": "k_train_step"}
+
+
+def train_selector(kind):
+    """The instances of one training-step kernel (a key of TRAIN_KERNELS) that csrc/train_dispatch.hpp launches -> (the template
+    arguments of every `return launch_train_<kind><...>(c, p);` line of select_train_<kind>, whether the last one is SAMPLE).  On
+    the way: launch_train_<kind> is used on those lines alone, it is the one function that names the kernel with template arguments,
+    and a selector over SAMPLE is instantiated for false and for true (the plain and the SAMPLE = true instances are the same lines)."""
+    with open(os.path.join(CSRC, "train_dispatch.hpp")) as f:
+        src = f.read()
+    lines = re.findall(r"\breturn launch_train_%s<([^>]*)>\(c, p\);" % kind, function_body(src, "select_train_" + kind))
+    assert lines and len(re.findall(r"\blaunch_train_%s<" % kind, src)) == len(lines), kind
+    sampled = lines[0].endswith(", SAMPLE")
+    assert all(("SAMPLE" in a) == a.endswith(", SAMPLE") == sampled for a in lines), lines
+    uses = re.findall(r"\bselect_train_%s(<\w+>)?\(c, p\);" % kind, src)  # launch_train_kernel<SAMPLE>, itself instantiated for both
+    assert uses == ["<SAMPLE>" if sampled else ""], (kind, uses)
+    assert "select_train_%s%s(c, p);" % (kind, uses[0]) in function_body(src, "launch_train_kernel"), kind
+    assert all("launch_train_kernel<%s>(c, p);" % flag in function_body(src, "launch_train") for flag in ("true", "false"))
+    named = re.findall(r"\b%s<[^>=]*>" % TRAIN_KERNELS[kind], function_body(src, "launch_train_" + kind))
+    assert len(named) == (2 if sampled else 1) and (", true, SampleArgs>" in " ".join(named)) == sampled, named
+    return [a.split(", ") for a in lines], sampled
+
+
+def train_kernels_named_in_launch_code():
+    """(file, `k_train_step...<template arguments>`) wherever csrc/ names a training-step kernel instance outside comments and plan
+    words (`<MAXP=...`): the launch templates of csrc/train_dispatch.hpp and nothing else, if each instance is listed once."""
+    from overcooked_ai_amd.build import strip_comments
+
+    found = []
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".hip", ".hpp")):
+            with open(os.path.join(CSRC, name)) as f:
+                found += [(name, m) for m in re.findall(r"\bk_train_step(?:_obs|_feat|1)?<[^>=]*>", strip_comments(f.read()))]
+    return found
+
+
 def pot_kinds(table, lid, state):
     """(idle, cooking, ready) pots and held soups somewhere in a batch of packed states"""
     idle = cooking = ready = 0

@@ -131,7 +131,7 @@ SITES = (
     (("train_obs.hpp", "k_train_step_obs: epoch"), ("obs_one_pot_u8_16_waves_smallest_batch@far",)),
     (("shaping.hpp", "k_train_step1: epoch"), ("train:step1_table_in_lds_regen@far",)),
     (("shaping.hpp", "k_train_step: epoch"), ("step_events_mix5_regen@far",)),
-    (("oc_amd.hip", "the oc_multi_agent_step sequence: oc_regen_layouts / oc_reset_random at the call's epoch"), ("sequence_seven_pots_drawn@far",)),
+    (("train_dispatch.hpp", "the oc_multi_agent_step sequence: oc_regen_layouts / oc_reset_random at the call's epoch"), ("sequence_seven_pots_drawn@far",)),
     (("reset.hpp", "k_reset_random and k_regen_layouts: the explicit reset"), ("explicit_reset_mix5_regen@far",)),
 )
 EXPLICIT_RESET = "explicit_reset_mix5_regen@far"

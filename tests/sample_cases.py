@@ -3,7 +3,7 @@ include/oc_amd.h (OcActionSampler) restated twice in numpy, and the logits of ev
 
 oc_multi_agent_step_sample draws both players' actions from policy logits and steps.  Wherever the same call with an actions array
 is planned as k_train_step_obs, k_train_step_feat or k_train_step1, the SAMPLE = true instance of that kernel draws the actions
-itself (one launch); every other plan runs k_sample_actions in front of the step's own path (csrc/train_sample.hpp).  Every case names
+itself (one launch); every other plan runs k_sample_actions in front of the step's own path (csrc/train_dispatch.hpp).  Every case names
 the words of oc_multi_agent_step_sample_plan it is there for (`expect`, a prefix that ends with a '>' or, for the sequence, with its
 first words).  tests/test_host_train_sample.py holds the list to the planner and to the instances the sources instantiate and shows
 on the references alone that each case contains what it claims; tests/test_gpu_train_sample.py steps every case.
@@ -146,10 +146,10 @@ def unfused(step_plan):
     return "k_sample_actions + " + step_plan
 
 
-# Every SAMPLE = true instance csrc/train_sample.hpp instantiates
+# Every SAMPLE = true instance csrc/train_dispatch.hpp instantiates
 INSTANCES = tuple([obs_k(p, t, w) for t in ("u8", "f32") for p in (1, 2) for w in (16, 8)]
                   + [step1(True, 1, True), step1(True, 2, True), step1(False, 2, True), step1(False, 2, False)] + [feat_k(1), feat_k(2)])
-# Instances no call reaches without a tuning knob, each with the condition of train_obs_shape (csrc/oc_amd.hip) that excludes it
+# Instances no call reaches without a tuning knob, each with the condition of train_obs_shape (csrc/train_dispatch.hpp) that excludes it
 UNREACHABLE = {obs_k(1, "f32", 16): "w == 16 && obs_dtype != OC_OBS_U8", obs_k(2, "f32", 16): "w == 16 && obs_dtype != OC_OBS_U8"}
 
 Case = namedtuple("Case", "id table n_envs expect steps horizon obs use_phi factor start events env_offset seed one_kernel greedy step0 "

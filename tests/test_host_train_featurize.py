@@ -1,5 +1,5 @@
 """tests/train_featurize_cases.py kept honest without a GPU: every case is planned (oc_multi_agent_step_featurize_plan) onto what it
-names, the k_train_step_feat instances csrc/oc_amd.hip instantiates are those the list covers, the entry point refuses what it must
+names, the k_train_step_feat instances csrc/train_dispatch.hpp instantiates are those the list covers, the entry point refuses what it must
 before any device call (this host has none to make), and on the oracle alone each case contains what it claims."""
 import ctypes
 import os
@@ -10,7 +10,7 @@ import pytest
 
 import train_cases as TC
 import train_featurize_cases as FC
-from case_support import CSRC, P, check_census, ledger, synthetic_batch, table_of
+from case_support import CSRC, P, check_census, ledger, synthetic_batch, table_of, train_selector
 
 ALL = FC.CASES + (FC.far_case(),)
 
@@ -66,10 +66,10 @@ def test_four_pot_blocks_get_smaller_images_and_the_plan_says_so():
 
 
 def test_the_instances_of_the_sources_are_those_the_list_covers():
-    with open(os.path.join(CSRC, "oc_amd.hip")) as f:
+    with open(os.path.join(CSRC, "train_dispatch.hpp")) as f:
         src = f.read()
     assert "k_train_step_feat<MP>" in src
-    found = [FC.feat_k(int(p)) for p in re.findall(r"\bFEAT_GO\((\d)\);", src)]
+    found = [FC.feat_k(int(p)) for p, _ in train_selector("feat")[0]]  # one line of select_train_feat each
     reached = {c.expect for c in ALL if c.expect.startswith("k_train_step_feat<")}
     check_census(found, FC.INSTANCES, {}, reached, 2, "k_train_step_feat instances")
     led = ledger(ALL, lambda c: c.expect)

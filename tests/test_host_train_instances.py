@@ -1,16 +1,15 @@
 """tests/train_cases.py kept honest without a GPU: every case is planned (oc_multi_agent_plan) onto the path or kernel instance it
-names, the cases and the named exclusions cover every training-step kernel instance csrc/oc_amd.hip instantiates, and on the
+names, the cases and the named exclusions cover every training-step kernel instance csrc/train_dispatch.hpp instantiates, and on the
 reference alone each case contains what it is there for — restarts, sparse and shaped rewards, a changing potential, illegal
-actions, event counters, re-drawn layouts.  A change to plan_train_step (csrc/oc_amd.hip) that moves a case to another kernel
+actions, event counters, re-drawn layouts.  A change to plan_train (csrc/train_dispatch.hpp) that moves a case to another kernel
 fails here, by the case's name, instead of silently changing what a GPU test runs."""
 import os
-import re
 
 import numpy as np
 import pytest
 
 import train_cases as TC
-from case_support import CSRC, check_census, ledger, print_ledger
+from case_support import CSRC, check_census, ledger, print_ledger, train_kernels_named_in_launch_code, train_selector
 
 
 def _ledger():
@@ -19,17 +18,16 @@ def _ledger():
 
 
 def _instantiated():
-    """The training-step kernel instances the launch macros of csrc/oc_amd.hip name, in oc_multi_agent_plan's words."""
-    with open(os.path.join(CSRC, "oc_amd.hip")) as f:
+    """The training-step kernel instances the selectors of csrc/train_dispatch.hpp name (one line each), in oc_multi_agent_plan's
+    words."""
+    with open(os.path.join(CSRC, "train_dispatch.hpp")) as f:
         src = f.read()
     kinds = {"uint8_t": "u8", "float": "f32"}
-    waves = [int(w) for w in re.findall(r"\bGOTO\(MP, T, (\d+)\)", src)]          # GOTOW's body: one GOTO per workgroup size
-    per_type = re.findall(r"\bGOTOW\((\d), (uint8_t|float)\)", src)               # its uses
-    lean = re.findall(r"\bGOT1\((true|false), (\d), (true|false)\)", src)
-    general = re.findall(r"\bGOT\((true|false), (true|false)\)", src)
+    (obs, _), (lean, _), (general, sampled) = train_selector("obs"), train_selector("step1"), train_selector("step")
+    assert not sampled  # k_train_step has no SAMPLE parameter
     assert "k_train_step<U, 2, U, false, EV>" in src and "k_train_step1<U, MP, LL>" in src and "k_train_step_obs<MP, T, NW>" in src
-    found = [TC.obs_k(int(p), kinds[t], w) for p, t in per_type for w in waves]
-    found += [TC.step1(u == "true", int(p), ll == "true") for u, p, ll in lean]
+    found = [TC.obs_k(int(p), kinds[t], int(w)) for p, t, w, _ in obs]
+    found += [TC.step1(u == "true", int(p), ll == "true") for u, p, ll, _ in lean]
     found += [TC.step_k(u == "true", ev == "true") for u, ev in general]
     return found
 
@@ -55,6 +53,17 @@ def test_every_training_step_instance_of_the_sources_has_a_case_or_a_named_exclu
     # the sequence: drawn and standard starts, and oc_regen_layouts inside it
     seq = [text for text in _ledger() if text.startswith("sequence:")]
     assert any("oc_regen_layouts" in t for t in seq) and any("oc_reset_random" in t for t in seq) and any(t.endswith("oc_reset, oc_encode_lossless") for t in seq)
+
+
+def test_each_training_step_instance_is_named_in_one_place():
+    """Outside the four launch templates of csrc/train_dispatch.hpp — each reached through its selector alone (train_selector) — no
+    source of the library names a training-step kernel with template arguments: nothing else can launch one."""
+    assert sorted(train_kernels_named_in_launch_code()) == sorted(("train_dispatch.hpp", k) for k in (
+        "k_train_step_obs<MP, T, NW>", "k_train_step_obs<MP, T, NW, true, SampleArgs>", "k_train_step_feat<MP>",
+        "k_train_step_feat<MP, true, SampleArgs>", "k_train_step1<U, MP, LL>", "k_train_step1<U, MP, LL, true, SampleArgs>",
+        "k_train_step<U, 2, U, false, EV>"))
+    for kind in ("obs", "feat", "step1", "step"):
+        train_selector(kind)
 
 
 def test_the_named_exclusions_hold():

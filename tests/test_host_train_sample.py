@@ -1,5 +1,5 @@
 """tests/sample_cases.py kept honest without a GPU: every case is planned (oc_multi_agent_step_sample_plan) onto what it names, the
-SAMPLE = true instances csrc/train_sample.hpp instantiates are those the list covers, the entry points refuse what they must before
+SAMPLE = true instances csrc/train_dispatch.hpp instantiates are those the list covers, the entry points refuse what they must before
 any device call (this host has none to make), the numpy Philox is the oracle's, each part of the far counters reaches a draw, and on
 the references alone each case contains what it claims and the float32 restatement of the sampler equals the float64 reference
 outside the boundary band."""
@@ -12,7 +12,7 @@ import pytest
 
 import sample_cases as SC
 import train_cases as TC
-from case_support import CSRC, P, check_census, synthetic_batch, table_of
+from case_support import CSRC, P, check_census, synthetic_batch, table_of, train_selector
 
 ALL = SC.CASES + (SC.far_case(),)
 EINVAL = -1  # OC_EINVAL
@@ -53,16 +53,17 @@ def test_the_planner_gives_the_case_what_it_names(case):
 
 
 def test_the_instances_of_the_sources_are_those_the_list_covers():
-    with open(os.path.join(CSRC, "train_sample.hpp")) as f:
+    with open(os.path.join(CSRC, "train_dispatch.hpp")) as f:
         src = f.read()
     assert "k_train_step_obs<MP, T, NW, true, SampleArgs>" in src and "k_train_step1<U, MP, LL, true, SampleArgs>" in src
     assert "k_train_step_feat<MP, true, SampleArgs>" in src
-    found = []
-    for mp, t in re.findall(r"\bSAMPLE_OBSW\((\d), (\w+)\);", src):
-        assert "SAMPLE_OBS(MP, T, 16); else SAMPLE_OBS(MP, T, 8)" in src
-        found += [SC.obs_k(int(mp), {"uint8_t": "u8", "float": "f32"}[t], w) for w in (16, 8)]
-    found += [SC.step1(u == "true", int(mp), ll == "true") for u, mp, ll in re.findall(r"\bSAMPLE_STEP1\((\w+), (\d), (\w+)\);", src)]
-    found += [SC.feat_k(int(mp)) for mp in re.findall(r"\bSAMPLE_FEAT\((\d)\);", src)]
+    # the selector lines the plain censuses read (tests/test_host_train_instances.py, tests/test_host_train_featurize.py), wherever
+    # their last template argument is SAMPLE: train_selector holds those selectors to be instantiated for SAMPLE = true as well
+    (obs, s_obs), (lean, s_lean), (feat, s_feat), (_, s_general) = (train_selector(k) for k in ("obs", "step1", "feat", "step"))
+    assert s_obs and s_lean and s_feat and not s_general
+    found = [SC.obs_k(int(mp), {"uint8_t": "u8", "float": "f32"}[t], int(w)) for mp, t, w, _ in obs]
+    found += [SC.step1(u == "true", int(mp), ll == "true") for u, mp, ll, _ in lean]
+    found += [SC.feat_k(int(mp)) for mp, _ in feat]
     reached = {SC.instance_of(c) for c in ALL} - {None}
     check_census(found, SC.INSTANCES, SC.UNREACHABLE, reached, 14, "SAMPLE = true instances")
     # each is the SAMPLE form of an instance the step's own launch code has (tests/train_cases.py, tests/train_featurize_cases.py)

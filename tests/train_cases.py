@@ -1,7 +1,7 @@
 """One list of VecOvercookedMultiAgent.step runs, each there for ONE path or kernel instance of oc_multi_agent_step, and the plain
 reference of such a step.
 
-`oc_multi_agent_step` is not one kernel: plan_train_step (csrc/oc_amd.hip) picks k_train_step_obs<MAXP, T, NWV> (the step and
+`oc_multi_agent_step` is not one kernel: plan_train (csrc/train_dispatch.hpp) picks k_train_step_obs<MAXP, T, NWV> (the step and
 its observation in one kernel), k_train_step1<UNIFORM, MAXP, LAY_LDS> or k_train_step<UNIFORM, EV> (the step in one kernel, then
 oc_encode_lossless), or the sequence of entry points, from the table's hints, the batch size, the observation array and its type
 and the event sink.  Every case below names what it is there for (`expect`: the words of oc_multi_agent_plan up to and including
@@ -50,7 +50,7 @@ def sequence(use_phi, start, obs=True):
     return "sequence: " + ", ".join(parts)
 
 
-# Every kernel instance csrc/oc_amd.hip instantiates for the training step; the sequence is a path, not an instance
+# Every kernel instance csrc/train_dispatch.hpp instantiates for the training step; the sequence is a path, not an instance
 INSTANCES = tuple([obs_k(p, t, w) for t in ("u8", "f32") for p in (1, 2) for w in (16, 8)]
                   + [step1(True, 1, True), step1(True, 2, True), step1(False, 2, True), step1(False, 2, False)]
                   + [step_k(u, ev) for u in (True, False) for ev in (True, False)])

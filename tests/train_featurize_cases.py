@@ -1,7 +1,7 @@
 """One list of VecOvercookedMultiAgent.step runs with the featurize_state observation (obs="features" / "both"), each there for ONE
 path of oc_multi_agent_step_featurize, and the reference of such a step.
 
-oc_multi_agent_step_featurize has two paths with identical results, chosen by plan_train_step_featurize (csrc/oc_amd.hip): the
+oc_multi_agent_step_featurize has two paths with identical results, chosen by plan_train (csrc/train_dispatch.hpp): the
 kernel k_train_step_feat<MAXP> (features without an observation array, one two-player layout of at most 64 cells with one or two
 pots, no event sink; `one_kernel`, or a batch from the launch-size threshold on), and oc_multi_agent_step's own planned path followed by
 k_featurize.  Every case names the words of oc_multi_agent_step_featurize_plan it is there for (`expect`, a prefix that ends with a
@@ -42,7 +42,7 @@ def two_launches(step_plan, lay_lds=True, obs=False):
     return "%s + k_featurize<LAY_LDS=%s>" % (step_plan, TC._tf(lay_lds))
 
 
-INSTANCES = (feat_k(1), feat_k(2))  # every k_train_step_feat instance csrc/oc_amd.hip instantiates
+INSTANCES = (feat_k(1), feat_k(2))  # every k_train_step_feat instance csrc/train_dispatch.hpp instantiates
 
 Case = namedtuple("Case", "id table n_envs expect steps horizon obs obs_dtype use_phi factor start events env_offset seed num_pots "
                           "counter_goals one_kernel claims")
