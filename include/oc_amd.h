@@ -1002,6 +1002,70 @@ int oc_partner_logits(const OcBatch* batch, const OcDensePolicy* policy, const O
  */
 int oc_partner_logits_plan(const OcBatch* batch, const OcDensePolicy* policy, int num_pots, char* out, size_t out_size);
 
+/*
+ * Advantages and value targets of a collected batch (ABI 6: entry points added beside the others; no existing signature, struct or
+ * option changes, so the version stays) — what PPO makes of the T steps it has collected: per-agent GAE(gamma, lambda) advantages
+ * and the value targets A + V, as the reference's PPO computes them (use_gae; gamma 0.99, lambda 0.98; the end of the horizon is a
+ * terminal done), in one launch (k_gae, csrc/gae.hpp) where a learner would run a reverse loop of small kernels over T.
+ *
+ * Layout.  Every array is time-major: row t is what step t of the collection left — T calls of oc_multi_agent_step_sample whose
+ * d_shaped, d_done, d_actions_out and d_logp_out point at row t of [T][n_envs]... arrays write exactly these.  d_values[t] is the
+ * policy's value estimate of the observation step t started from, d_last_values that of the observation after step T - 1.  A done
+ * step is followed, in the same row, by the first observation of the restarted episode: d_values[t + 1] belongs to ANOTHER episode
+ * then, and the chain does not reach across.  With a behaviour-cloning partner (oc_partner_logits) d_seat[t] is the seat array as
+ * it stood during step t: the partner's samples are no learner samples.
+ *
+ * Arithmetic.  Per env e and player p, for t = T - 1 down to 0; every operation is f32 with one rounding, in this order, with no
+ * contraction; the chain over t is sequential and is not re-associated:
+ *   g = gamma;  gl = gamma * lambda (one f32 product, formed on the host);  the carried A starts as 0
+ *   r = (float)d_rewards[t][e][p] (round to nearest);  v = d_values[t][e][p]
+ *   if d_done[t][e] != 0:  delta = r - v;  A = delta
+ *       (a select, not a multiplication by 0: neither d_values[t + 1][e] nor the carried A enters, so a NaN or a sentinel there
+ *        cannot reach step t)
+ *   otherwise:             vn = d_values[t + 1][e][p], at t = T - 1 d_last_values[e][p] (0 when that is NULL);
+ *                          delta = (r + g * vn) - v;  A = delta + gl * A_carried
+ *   target = A + v;  A is carried to t - 1
+ *   if d_seat != NULL and d_seat[t][e] == p, the sample is the partner's: d_advantages[t][e][p] = d_targets[t][e][p] = +0.0f, the
+ *   value carried on is 0, and the entry is left out of the moments; the other player's chain is unaffected.  (A seat that changes
+ *   inside an episode is read as it stands, step by step.)
+ * Moments (for the batch standardisation of the advantages).  d_partials[k] = {count, sum A, sum A^2} over the learner samples of
+ * envs [256 k, 256 k + 256), all steps and both players, accumulated in f64 with A widened before it is squared; d_moments is the
+ * sum of the partials in ascending k.  No floating-point atomics: the same call on the same inputs gives the same bits.
+ */
+typedef struct OcGaeBatch {
+    const double*  d_rewards;      /* [T][n_envs][2] f64: the step's d_shaped rows; 16-byte aligned; required */
+    const float*   d_values;       /* [T][n_envs][2] f32: V(observation step t started from); 8-byte aligned; required */
+    const float*   d_last_values;  /* [n_envs][2] f32: V(observation after step T-1); 8-byte aligned; NULL = 0 */
+    const uint8_t* d_done;         /* [T][n_envs] u8: the step's d_done rows; any address; required */
+    const uint8_t* d_seat;         /* [T][n_envs] u8: the partner's player during step t (0 / 1), else no partner; NULL = none */
+    float*         d_advantages;   /* [T][n_envs][2] f32 out; 8-byte aligned; required */
+    float*         d_targets;      /* [T][n_envs][2] f32 out; 8-byte aligned; required */
+    double*        d_partials;     /* [ceil(n_envs / 256)][3] f64 out, or NULL (then d_moments must be NULL too) */
+    double*        d_moments;      /* [3] f64 out: count, sum A, sum A^2 over learner samples; or NULL */
+    int64_t n_steps;               /* T >= 0 */
+    float gamma, lambda;
+} OcGaeBatch;
+
+/*
+ * oc_gae — the reverse pass: k_gae, one lane per env, and, with d_moments, k_gae_moments behind it (one wavefront adding the
+ * partials).  Of the batch only n_envs is read.  n_steps == 0 or n_envs == 0 launches nothing and returns 0; the moments asked for
+ * are then set to zeros.
+ * OC_EINVAL, before any device call, with this entry point's name in front of the message: a NULL batch, struct or required array;
+ * a misaligned array (d_partials and d_moments: 8 bytes); n_steps < 0 or n_envs < 0; gamma or lambda outside [0, 1] or NaN;
+ * d_moments without d_partials.
+ */
+int oc_gae(const OcBatch* batch, const OcGaeBatch* g, void* stream);
+
+/*
+ * oc_gae_plan — what oc_gae would launch, as text (with_seat: d_seat given; with_moments: d_partials and d_moments given):
+ *   "k_gae<SEAT=true, MOM=true> grid=256, 256 lanes (one per env, both players), 8 steps per prefetch block, 50 block(s) + k_gae_moments grid=1, 64 lanes"
+ *   "nothing to launch (no envs)"     "nothing to launch (no steps)"
+ * A prefetch block is the run of steps whose loads a lane issues before it needs the first of them.  The checks that need no array
+ * apply (batch, n_envs, n_steps); usable without a GPU, like the other plan calls; refusals carry oc_gae's name.
+ *   out, out_size caller's text buffer (>= 256 bytes holds every answer)
+ */
+int oc_gae_plan(const OcBatch* batch, int64_t n_steps, int with_seat, int with_moments, char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

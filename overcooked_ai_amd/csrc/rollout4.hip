@@ -3,7 +3,8 @@
 // workgroups and MODE 2, the pose one step ahead in one wavefront) and 2 (MODE 0: arithmetic movement), so that a clean build runs four hipcc processes side by side (overcooked_ai_amd/build.py) instead
 // of one 80-second compile.  oc_amd.hip (choose_rollout) picks the instance; the unit that compiles it launches it
 // (launch_rollout) or, for oc_rollout_plan, names it and its LDS bytes (describe_rollout).
-// The OC_R4_PART == 2 unit, the shortest of the four, also compiles partner.hpp: k_partner_logits and its two entry points.
+// The OC_R4_PART == 2 unit, the shortest of the four, also compiles partner.hpp (k_partner_logits and its two entry points) and
+// gae.hpp (k_gae, k_gae_moments and theirs).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -167,4 +168,5 @@ template void describe_rollout<OC_R4_PART>(const Rollout4Call& c, char* out, siz
 
 #if OC_R4_PART == 2
 #include "partner.hpp"  // k_partner_logits, oc_partner_logits, oc_partner_logits_plan
+#include "gae.hpp"      // k_gae, k_gae_moments, oc_gae, oc_gae_plan
 #endif

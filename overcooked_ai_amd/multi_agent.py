@@ -224,6 +224,7 @@ class VecOvercookedMultiAgent:
         dev = v.device
         self.shaped = torch.zeros((self.n_envs, 2), dtype=torch.float64, device=dev)
         self.done = torch.zeros((self.n_envs,), dtype=torch.uint8, device=dev)
+        self._last_done = self.done  # the tensor the last step wrote its done mask to (a TrajectoryBuffer row with `into`)
         self.phi_next = torch.zeros((self.n_envs,), dtype=torch.float64, device=dev)
         self.phi_cur = torch.zeros((self.n_envs,), dtype=torch.float64, device=dev)
         self.phi_start = torch.zeros((len(v.table),), dtype=torch.float64, device=dev)
@@ -337,9 +338,12 @@ class VecOvercookedMultiAgent:
             raise ValueError("actions must be a contiguous uint8 [n_envs, 2] tensor on %s" % v.device)
         return self._step(actions.data_ptr(), None)
 
-    def _step(self, actions_ptr, sampler):
-        """step() with the caller's actions (sampler None), or step_sampled() with an OcActionSampler in their place."""
+    def _step(self, actions_ptr, sampler, shaped=None, done=None):
+        """step() with the caller's actions (sampler None), or step_sampled() with an OcActionSampler in their place.  shaped, done:
+        the tensors that receive the training rewards and the done mask in place of the persistent buffers (step_sampled's `into`)."""
         v = self.venv
+        shaped = self.shaped if shaped is None else shaped
+        done = self.done if done is None else done
         obs, code, start, sink = self._call_args()
         if self.use_phi:
             if self._phi_args is None:
@@ -351,7 +355,7 @@ class VecOvercookedMultiAgent:
             plan = off = tables = None
         args = (v._bref, v._state_ptr, actions_ptr if sampler is None else sampler, v._rewards_ptr, v._flags_ptr, v._ep_ptr, self.ep_returns.data_ptr(), plan, off,
                 tables, self.phi_next.data_ptr(), self.phi_cur.data_ptr(), self.phi_start.data_ptr(), float(self.reward_shaping_factor),
-                self.shaped.data_ptr(), self.done.data_ptr(), obs.data_ptr() if obs is not None else None, code, self.horizon)
+                shaped.data_ptr(), done.data_ptr(), obs.data_ptr() if obs is not None else None, code, self.horizon)
         feat = None
         if sampler is not None:
             fargs = (None, None, None)
@@ -371,6 +375,7 @@ class VecOvercookedMultiAgent:
             rc = v._launch(v.lib.oc_multi_agent_step, *args, start, sink)
             self._lib.check(rc, "oc_multi_agent_step")
         v._advance(1)
+        self._last_done = done
         self._feat_current = feat is not None
         infos = {"sparse_r_by_agent": v.rewards[:, 0:2], "shaped_r_by_agent": v.rewards[:, 2:4], "flags": v.flags,
                  "ep_returns": self.ep_returns}  # episode totals so far; final where done (the reset cleared the live ones)
@@ -380,11 +385,11 @@ class VecOvercookedMultiAgent:
             out = feat if obs is None else (obs, feat)
         else:
             out = obs if obs is not None else self.observations()
-        return out, self.shaped, self.done, infos
+        return out, shaped, done, infos
 
-    def _sampler(self, logits, greedy):
+    def _sampler(self, logits, greedy, into=None):
         """The OcActionSampler of the next draw (persistent, like its output buffers): this env's seed and env offset, the sample
-        counter as the step."""
+        counter as the step.  into: the TrajectoryBuffer row whose actions and logp receive the draw in place of those buffers."""
         import ctypes
 
         v, torch = self.venv, self._torch
@@ -395,6 +400,8 @@ class VecOvercookedMultiAgent:
             self._sampled = (torch.zeros((self.n_envs, 2), dtype=torch.uint8, device=v.device),
                              torch.zeros((self.n_envs, 2), dtype=torch.float32, device=v.device), self._lib.OcActionSampler())
         actions, logp, s = self._sampled
+        if into is not None:
+            actions, logp = into.actions, into.logp
         s.d_logits, s.d_actions_out, s.d_logp_out = logits.data_ptr(), actions.data_ptr(), logp.data_ptr()
         s.seed, s.env_offset, s.step = v.seed, v.env_offset, self.sample_step
         s.mode = self._lib.SAMPLE_ARGMAX if greedy else self._lib.SAMPLE_CATEGORICAL
@@ -410,7 +417,20 @@ class VecOvercookedMultiAgent:
         self._lib.check(v._launch(v.lib.oc_sample_actions, v._bref, s), "oc_sample_actions")
         return actions, logp
 
-    def step_sampled(self, logits, greedy=False):
+    def _checked_row(self, into):
+        """step_sampled's `into`: a TrajectoryBuffer row of this env's batch size, on its device."""
+        torch, dev = self._torch, self.venv.state.device
+        n = self.n_envs
+        for name, dtype, shape in (("rewards", torch.float64, (n, 2)), ("done", torch.uint8, (n,)), ("actions", torch.uint8, (n, 2)),
+                                   ("logp", torch.float32, (n, 2))) + ((("seat", torch.uint8, (n,)),) if self.bc_policy is not None else ()):
+            t = getattr(into, name, None)
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise ValueError("into.%s must be a contiguous %s %s tensor on %s" % (name, str(dtype).replace("torch.", ""), list(shape), dev))
+        if into.rewards.data_ptr() % 16 or into.logp.data_ptr() % 8 or into.actions.data_ptr() % 2:
+            raise ValueError("into: rewards must be 16-byte, logp 8-byte and actions 2-byte aligned")
+        return into
+
+    def step_sampled(self, logits, greedy=False, into=None):
         """step() for a policy in the loop: `logits` is its output, contiguous float32 [n_envs, 2, 6] (player, action index) on the
         env's device; both players' actions are drawn from it (greedy: the lowest-index maximum) and stepped by a single C call
         (oc_multi_agent_step_sample; one launch wherever step() is one kernel).  Returns what step() returns, with the drawn
@@ -420,11 +440,23 @@ class VecOvercookedMultiAgent:
         -inf draws action 255 with logp NaN: the env is flagged OC_F_BAD_ACTION and stays as it is.
         With a bc_policy, partner_logits(logits) runs first: the caller's `logits` tensor is OVERWRITTEN at the partner seats
         (logits[e, seat[e]] of every env with a partner) with the partner's own logits, the draw follows from those, and
-        infos["seat"] is the seat tensor, so that a learner can drop the partner's samples."""
+        infos["seat"] is the seat tensor, so that a learner can drop the partner's samples.
+        into: a row of a trajectory_buffer.TrajectoryBuffer (`buf.row(t, values)`).  The same C call then writes the training
+        rewards, the done mask, the drawn actions and their log-probabilities into that row in place of the persistent buffers —
+        which this call leaves untouched — and returns the row's views; with a bc_policy the seats of this step are copied into
+        the row's seat (one copy).  The next call, with or without `into`, reseats by the done mask this call wrote.  Observations
+        stay in their persistent buffers: the policy's next forward pass reads them there."""
+        if into is not None:
+            self._checked_row(into)
         if self.bc_policy is not None:
             self.partner_logits(logits)
-        actions, logp, s = self._sampler(logits, greedy)
-        out, shaped, done, infos = self._step(None, s)
+            if into is not None:
+                into.seat.copy_(self.seat)
+        actions, logp, s = self._sampler(logits, greedy, into)
+        if into is None:
+            out, shaped, done, infos = self._step(None, s)
+        else:
+            out, shaped, done, infos = self._step(None, s, into.rewards, into.done)
         infos["actions"], infos["logp"] = actions, logp
         if self.bc_policy is not None:
             infos["seat"] = self.seat
@@ -448,7 +480,7 @@ class VecOvercookedMultiAgent:
             self.observations("features")
             self._feat_current = True
         s = self._seats
-        s.d_seat, s.d_done = self.seat.data_ptr(), None if self._reseat_all else self.done.data_ptr()
+        s.d_seat, s.d_done = self.seat.data_ptr(), None if self._reseat_all else self._last_done.data_ptr()
         s.bc_factor, s.seed, s.env_offset, s.step = float(self.bc_factor), v.seed, v.env_offset, self.sample_step
         rc = v._launch(v.lib.oc_partner_logits, v._bref, self.bc_policy._ref, ctypes.byref(s), self._feat_buffer().data_ptr(),
                        self.num_pots, logits.data_ptr())

@@ -1,0 +1,85 @@
+"""`TrajectoryBuffer`: the T steps of one PPO iteration on a `VecOvercookedMultiAgent`, time-major, written by the step itself.
+
+    buf = TrajectoryBuffer(tenv, T)
+    for t in range(T):
+        logits, values = policy(obs)
+        obs, _, _, infos = tenv.step_sampled(logits, into=buf.row(t, values))
+    buf.last_values.copy_(policy(obs)[1])
+    adv, targets, (n, s1, s2) = buf.advantages(0.99, 0.98)
+
+`row(t, values)` hands step t's slices to `step_sampled(into=...)`, whose C call then writes the training rewards, the done mask,
+the drawn actions and their log-probabilities there in place of the env's persistent buffers: no copy per step, and the rows are the
+step's own bytes.  `advantages` is `gae.gae` (oc_gae, one launch) over the whole buffer.
+
+Row t of every tensor meets the alignment the step and the sampler ask for whatever N is: rewards rows are 16 N bytes apart (16-byte
+aligned), logp and values rows 8 N (8), actions rows 2 N (2), done and seat rows N (any address) — a fresh allocation starts on a
+multiple of 256."""
+import collections
+
+TrajectoryRow = collections.namedtuple("TrajectoryRow", "rewards done actions logp seat")
+
+ROW_BYTES = {"rewards": 16, "done": 1, "actions": 2, "logp": 8, "values": 8, "seat": 1}  # bytes per env of a row
+ROW_ALIGN = {"rewards": 16, "done": 1, "actions": 2, "logp": 8, "values": 8, "seat": 1}  # what the C-ABI asks of a row's address
+
+
+def row_offsets(name, T, n_envs):
+    """Byte offsets of rows 0..T-1 of tensor `name` from its base."""
+    return [t * n_envs * ROW_BYTES[name] for t in range(T)]
+
+
+class TrajectoryBuffer:
+    """Time-major tensors on the env's device: rewards float64 [T, N, 2], done uint8 [T, N], actions uint8 [T, N, 2], logp float32
+    [T, N, 2], values float32 [T, N, 2], last_values float32 [N, 2] and, when the env has a bc_policy, seat uint8 [T, N] (else
+    None).  keep_obs: also obs [T, N, 2, W, H, 26] (the env's obs_dtype) and / or features float32 [T, N, 2, F], whichever the
+    env's observation kind has, copied by row() from the env's persistent observation buffers — the observation step t starts
+    from, which the policy has just read there."""
+
+    def __init__(self, tenv, T, keep_obs=False):
+        import torch
+
+        T = int(T)
+        if T < 1:
+            raise ValueError("TrajectoryBuffer: T must be at least 1, not %d" % T)
+        self.tenv, self.T, self.n_envs = tenv, T, tenv.n_envs
+        N, dev = tenv.n_envs, tenv.venv.device
+        self.rewards = torch.zeros((T, N, 2), dtype=torch.float64, device=dev)
+        self.done = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+        self.actions = torch.zeros((T, N, 2), dtype=torch.uint8, device=dev)
+        self.logp = torch.zeros((T, N, 2), dtype=torch.float32, device=dev)
+        self.values = torch.zeros((T, N, 2), dtype=torch.float32, device=dev)
+        self.last_values = torch.zeros((N, 2), dtype=torch.float32, device=dev)
+        self.seat = torch.full((T, N), 255, dtype=torch.uint8, device=dev) if tenv.bc_policy is not None else None
+        self.obs = self.features = None
+        if keep_obs:
+            if tenv.obs_kind == "bc":
+                raise ValueError("TrajectoryBuffer: keep_obs needs an env whose step writes its observation (obs \"ppo\", \"features\" or \"both\")")
+            if tenv.obs_kind in ("ppo", "both"):
+                self.obs = torch.zeros((T,) + tuple(tenv._obs_buffer().shape), dtype=tenv.obs_dtype, device=dev)
+            if tenv.obs_kind in ("features", "both"):
+                self.features = torch.zeros((T,) + tuple(tenv._feat_buffer().shape), dtype=torch.float32, device=dev)
+        self._rows = [TrajectoryRow(self.rewards[t], self.done[t], self.actions[t], self.logp[t],
+                                    self.seat[t] if self.seat is not None else None) for t in range(T)]
+
+    def row(self, t, values):
+        """The destinations of step t, for `step_sampled(into=...)`; `values` (float32 [N, 2], the policy's value estimates of the
+        observation step t starts from) is stored in values[t].  With keep_obs the env's current observation is copied too."""
+        torch = self.tenv._torch
+        if not 0 <= t < self.T:
+            raise ValueError("TrajectoryBuffer.row: t = %d outside 0..%d" % (t, self.T - 1))
+        if not isinstance(values, torch.Tensor) or tuple(values.shape) != (self.n_envs, 2) or values.device != self.values.device \
+                or not values.dtype.is_floating_point:
+            raise ValueError("TrajectoryBuffer.row: values must be a floating-point [n_envs, 2] tensor on %s" % self.values.device)
+        self.values[t].copy_(values)
+        if self.obs is not None:
+            self.obs[t].copy_(self.tenv._obs_buffer())
+        if self.features is not None:
+            self.features[t].copy_(self.tenv._feat_buffer())
+        return self._rows[t]
+
+    def advantages(self, gamma, lam, moments=True, out=None):
+        """gae.gae over the whole buffer: (advantages, targets) float32 [T, N, 2] and, with moments, the float64 [3] tensor
+        (count, sum A, sum A^2) over the learner samples."""
+        from .gae import gae
+
+        return gae(self.rewards, self.values, self.done, gamma, lam, last_values=self.last_values, seat=self.seat, moments=moments,
+                   out=out)
