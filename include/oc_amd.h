@@ -1066,6 +1066,85 @@ int oc_gae(const OcBatch* batch, const OcGaeBatch* g, void* stream);
  */
 int oc_gae_plan(const OcBatch* batch, int64_t n_steps, int with_seat, int with_moments, char* out, size_t out_size);
 
+/*
+ * The PPO loss head (ABI 6: entry points added beside the others) — the learner's call behind oc_gae: the clipped-surrogate loss of
+ * a minibatch, as the reference's trainer (RLlib's PPO) states it, and its gradients with respect to the policy's logits and
+ * values, in one launch (k_ppo_loss, csrc/ppo_loss.hpp) where a learner would run some 25 elementwise and reduction kernels forward
+ * and as many backward.
+ *
+ * Layout.  A sample is s = (t * n_envs + e) * 2 + p, the flat index into the time-major [T][n_envs][2] arrays of OcGaeBatch and of
+ * the collection; S = T * n_envs * 2.  The batch side is the whole buffer; the minibatch side — the policy's logits and values of
+ * M samples, in the order of its forward pass — names its samples through d_index, or is samples first_sample .. first_sample +
+ * M - 1.
+ *
+ * Arithmetic.  Per minibatch row, with a = d_actions[s], l = the row's logits, v its value; every operation is f32 with one
+ * rounding, in this order, with no contraction, expf and logf in full precision:
+ *   m = max l_i;  d_i = l_i - m;  w_i = expf(d_i);  S = ((((w_0 + w_1) + w_2) + w_3) + w_4) + w_5
+ *   lp_i = d_i - logf(S);  p_i = w_i / S;  logp = lp_a;  ratio = expf(logp - d_logp_old[s])
+ *   A^ = d_advantages[s], or with d_moments = {n, s1, s2} and n >= 1, in f64: mean = s1 / n;
+ *        std = max(sqrt(max(s2 / n - mean * mean, 0)), 1e-4);  A^ = (float)(((double)A - mean) / std)
+ *        (the moments of the whole batch, as RLlib standardises the train batch)
+ *   s1 = ratio * A^;  s2 = min(max(ratio, lo), hi) * A^ with lo = 1 - clip_param, hi = 1 + clip_param (one f32 operation each);
+ *   surr = min(s1, s2)
+ *   H = -(((((t_0 + t_1) + t_2) + t_3) + t_4) + t_5), t_i = p_i * lp_i, and t_i = 0 where p_i == 0
+ *   dv = v - d_targets[s];  vf = dv * dv;  vfc = min(vf, vf_clip_param)
+ *   kl, with d_logits_old (lq_i, q_i: the same softmax of the old row): the sum of u_i = q_i * (lq_i - lp_i), u_i = 0 where
+ *       q_i == 0, from u_0 on; without: the sample estimate d_logp_old[s] - logp, reported only (kl_coeff must be 0)
+ * Gradients of -surr + vf_loss_coeff * vfc - entropy_coeff * H + kl_coeff * kl, per sample, not divided by the count:
+ *   g = (s1 <= s2) ? -s1 : 0
+ *   d/dl_i = g * ([i == a] - p_i) + (entropy_coeff * p_i) * (lp_i + H), the second product 0 where p_i == 0,
+ *            and with d_logits_old + kl_coeff * (p_i - q_i)
+ *   d/dv = vf_loss_coeff * ((vf <= vf_clip_param) ? 2 * dv : 0)
+ * Left-out samples.  A row is left out when its index is outside 0 .. S - 1, when d_actions[s] > 5 (255: the sampler's invalid
+ * row, whose logp is NaN) or when d_seat[s >> 1] == (s & 1) (the partner's sample).  Its seven gradients and its terms are +0.0f,
+ * by a select, so that a NaN anywhere in its inputs reaches nothing, and it enters no sum.
+ * Sums.  d_partials[k] = {count, sum -surr, sum vfc, sum H, sum kl, number of ratios outside [lo, hi]} over the learner samples
+ * of minibatch rows [P k, P k + P), P = 1024 (oc_ppo_loss_plan states it): each term widened to f64 before it is added, in a fixed
+ * tree.  d_stats = {count, total, policy, vf, entropy, kl, clip_frac, 1 / count}: the partials added in ascending k, each of the
+ * five sums divided by count, total = ((policy + vf_loss_coeff * vf) - entropy_coeff * entropy) + kl_coeff * kl in f64 with
+ * the coefficients widened; all zeros when count == 0.  No floating-point atomics: the same call on the same inputs gives the same bits.
+ */
+typedef struct OcPpoLoss {
+    const uint8_t* d_actions;      /* [S] u8: the collection's actions; any address; required */
+    const float*   d_logp_old;     /* [S] f32: their log-probabilities under the collecting policy; 4-byte aligned; required */
+    const float*   d_advantages;   /* [S] f32: oc_gae's; 4-byte aligned; required */
+    const float*   d_targets;      /* [S] f32: oc_gae's; 4-byte aligned; required */
+    const uint8_t* d_seat;         /* [S / 2] u8: the partner's player of (t, e), else no partner; any address; NULL = none */
+    const float*   d_logits_old;   /* [S][6] f32: the collecting policy's logits, for the exact KL; 8-byte aligned; or NULL */
+    const double*  d_moments;      /* [3] f64: oc_gae's d_moments, for standardising the advantages; 8-byte aligned; or NULL */
+    int64_t n_samples;             /* S >= 0 */
+    const float*   d_logits;       /* [M][6] f32: the policy's logits of the minibatch; 16-byte aligned; required */
+    const float*   d_values;       /* [M] f32: its values; 4-byte aligned; required */
+    const int32_t* d_index;        /* [M] i32: the sample of every row; 4-byte aligned; NULL = first_sample + row */
+    int64_t first_sample;          /* read without d_index only */
+    int64_t n_minibatch;           /* M >= 0 */
+    float*         d_grad_logits;  /* [M][6] f32 out; 16-byte aligned; required */
+    float*         d_grad_values;  /* [M] f32 out; 4-byte aligned; required */
+    double*        d_partials;     /* [ceil(M / P)][6] f64 out; 8-byte aligned; or NULL (then d_stats must be NULL too) */
+    double*        d_stats;        /* [8] f64 out; 8-byte aligned; or NULL */
+    float*         d_terms_out;    /* [M][4] f32 out: surr, vfc, H, kl of every row; 16-byte aligned; or NULL */
+    float clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff;
+} OcPpoLoss;
+
+/*
+ * oc_ppo_loss — k_ppo_loss, one lane per minibatch row and four rows per lane, and, with d_stats, k_ppo_loss_stats behind it (one wavefront adding the
+ * partials).  n_minibatch == 0 launches nothing and returns 0; d_stats is then set to zeros.
+ * OC_EINVAL, before any device call, with this entry point's name in front of the message: a NULL struct or required array; a
+ * misaligned array; n_minibatch < 0 or n_samples < 0; an odd n_samples with d_seat; n_samples >= 2^31 with d_index; without d_index a first_sample < 0 or
+ * first_sample + n_minibatch > n_samples; clip_param or vf_clip_param not finite and positive; a negative or NaN coefficient;
+ * kl_coeff > 0 without d_logits_old; d_stats without d_partials.
+ */
+int oc_ppo_loss(const OcPpoLoss* q, void* stream);
+
+/*
+ * oc_ppo_loss_plan — what oc_ppo_loss would launch, as text (with_...: the optional array is given):
+ *   "k_ppo_loss<OLD=true> grid=4096, 256 lanes (one per sample, 4 tiles of 256), 1024 samples per partial, index=yes seat=yes moments=yes terms=no + k_ppo_loss_stats grid=1, 64 lanes, 4096 partial(s) (with d_stats)"
+ *   "nothing to launch (no samples)"
+ * Usable without a GPU, like the other plan calls; refusals carry oc_ppo_loss's name.
+ *   out, out_size caller's text buffer (>= 256 bytes holds every answer)
+ */
+int oc_ppo_loss_plan(int64_t n_minibatch, int with_index, int with_seat, int with_moments, int with_old_logits, int with_terms, char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

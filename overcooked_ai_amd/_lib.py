@@ -29,7 +29,7 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_step_server_open", "oc_step_server_requests", "oc_step_server_responses", "oc_step_server_resume",
            "oc_step_server_play", "oc_step_server_sync", "oc_step_server_steps", "oc_step_server_close",
            "oc_sample_actions", "oc_multi_agent_step_sample", "oc_multi_agent_step_sample_plan",
-           "oc_partner_logits", "oc_partner_logits_plan", "oc_gae", "oc_gae_plan")
+           "oc_partner_logits", "oc_partner_logits_plan", "oc_gae", "oc_gae_plan", "oc_ppo_loss", "oc_ppo_loss_plan")
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
 
 
@@ -86,6 +86,15 @@ class OcGaeBatch(ctypes.Structure):
     _fields_ = [("d_rewards", ctypes.c_void_p), ("d_values", ctypes.c_void_p), ("d_last_values", ctypes.c_void_p), ("d_done", ctypes.c_void_p),
                 ("d_seat", ctypes.c_void_p), ("d_advantages", ctypes.c_void_p), ("d_targets", ctypes.c_void_p), ("d_partials", ctypes.c_void_p),
                 ("d_moments", ctypes.c_void_p), ("n_steps", ctypes.c_int64), ("gamma", ctypes.c_float), ("lam", ctypes.c_float)]
+
+
+class OcPpoLoss(ctypes.Structure):
+    _fields_ = [("d_actions", ctypes.c_void_p), ("d_logp_old", ctypes.c_void_p), ("d_advantages", ctypes.c_void_p), ("d_targets", ctypes.c_void_p),
+                ("d_seat", ctypes.c_void_p), ("d_logits_old", ctypes.c_void_p), ("d_moments", ctypes.c_void_p), ("n_samples", ctypes.c_int64),
+                ("d_logits", ctypes.c_void_p), ("d_values", ctypes.c_void_p), ("d_index", ctypes.c_void_p), ("first_sample", ctypes.c_int64),
+                ("n_minibatch", ctypes.c_int64), ("d_grad_logits", ctypes.c_void_p), ("d_grad_values", ctypes.c_void_p),
+                ("d_partials", ctypes.c_void_p), ("d_stats", ctypes.c_void_p), ("d_terms_out", ctypes.c_void_p), ("clip_param", ctypes.c_float),
+                ("vf_clip_param", ctypes.c_float), ("vf_loss_coeff", ctypes.c_float), ("entropy_coeff", ctypes.c_float), ("kl_coeff", ctypes.c_float)]
 
 
 class OcAmdError(RuntimeError):
@@ -218,6 +227,10 @@ def load():
     L.oc_gae.argtypes = [bp, ctypes.POINTER(OcGaeBatch), vp]
     L.oc_gae_plan.restype = i32
     L.oc_gae_plan.argtypes = [bp, i64, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.oc_ppo_loss.restype = i32
+    L.oc_ppo_loss.argtypes = [ctypes.POINTER(OcPpoLoss), vp]
+    L.oc_ppo_loss_plan.restype = i32
+    L.oc_ppo_loss_plan.argtypes = [i64, i32, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

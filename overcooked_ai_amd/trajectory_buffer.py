@@ -5,11 +5,15 @@
         logits, values = policy(obs)
         obs, _, _, infos = tenv.step_sampled(logits, into=buf.row(t, values))
     buf.last_values.copy_(policy(obs)[1])
-    adv, targets, (n, s1, s2) = buf.advantages(0.99, 0.98)
+    adv, targets, moments = buf.advantages(0.99, 0.98)
+    batch = buf.learner_batch(adv, targets, moments)
+    for index in buf.minibatches(4096):
+        loss, stats = ppo_loss.ppo_loss(*policy(buf.features.view(-1, F)[index.long()]), batch, index, clip_param=0.05, ...)
 
 `row(t, values)` hands step t's slices to `step_sampled(into=...)`, whose C call then writes the training rewards, the done mask,
 the drawn actions and their log-probabilities there in place of the env's persistent buffers: no copy per step, and the rows are the
-step's own bytes.  `advantages` is `gae.gae` (oc_gae, one launch) over the whole buffer.
+step's own bytes.  `advantages` is `gae.gae` (oc_gae, one launch) over the whole buffer; `learner_batch` hands the buffer to
+`ppo_loss.ppo_loss` as flat [S] views, S = T * N * 2, and `minibatches` cuts a device permutation of the samples into index tensors.
 
 Row t of every tensor meets the alignment the step and the sampler ask for whatever N is: rewards rows are 16 N bytes apart (16-byte
 aligned), logp and values rows 8 N (8), actions rows 2 N (2), done and seat rows N (any address) — a fresh allocation starts on a
@@ -32,9 +36,10 @@ class TrajectoryBuffer:
     [T, N, 2], values float32 [T, N, 2], last_values float32 [N, 2] and, when the env has a bc_policy, seat uint8 [T, N] (else
     None).  keep_obs: also obs [T, N, 2, W, H, 26] (the env's obs_dtype) and / or features float32 [T, N, 2, F], whichever the
     env's observation kind has, copied by row() from the env's persistent observation buffers — the observation step t starts
-    from, which the policy has just read there."""
+    from, which the policy has just read there.  keep_logits: also logits float32 [T, N, 2, 6], the learner's logits that row()
+    is given (the exact KL of the loss needs them)."""
 
-    def __init__(self, tenv, T, keep_obs=False):
+    def __init__(self, tenv, T, keep_obs=False, keep_logits=False):
         import torch
 
         T = int(T)
@@ -49,6 +54,7 @@ class TrajectoryBuffer:
         self.values = torch.zeros((T, N, 2), dtype=torch.float32, device=dev)
         self.last_values = torch.zeros((N, 2), dtype=torch.float32, device=dev)
         self.seat = torch.full((T, N), 255, dtype=torch.uint8, device=dev) if tenv.bc_policy is not None else None
+        self.logits = torch.zeros((T, N, 2, 6), dtype=torch.float32, device=dev) if keep_logits else None
         self.obs = self.features = None
         if keep_obs:
             if tenv.obs_kind == "bc":
@@ -60,15 +66,23 @@ class TrajectoryBuffer:
         self._rows = [TrajectoryRow(self.rewards[t], self.done[t], self.actions[t], self.logp[t],
                                     self.seat[t] if self.seat is not None else None) for t in range(T)]
 
-    def row(self, t, values):
+    def row(self, t, values, logits=None):
         """The destinations of step t, for `step_sampled(into=...)`; `values` (float32 [N, 2], the policy's value estimates of the
-        observation step t starts from) is stored in values[t].  With keep_obs the env's current observation is copied too."""
+        observation step t starts from) is stored in values[t].  With keep_obs the env's current observation is copied too, with
+        keep_logits `logits` (floating-point [N, 2, 6], what step_sampled is about to draw from) is stored in logits[t]."""
         torch = self.tenv._torch
         if not 0 <= t < self.T:
             raise ValueError("TrajectoryBuffer.row: t = %d outside 0..%d" % (t, self.T - 1))
         if not isinstance(values, torch.Tensor) or tuple(values.shape) != (self.n_envs, 2) or values.device != self.values.device \
                 or not values.dtype.is_floating_point:
             raise ValueError("TrajectoryBuffer.row: values must be a floating-point [n_envs, 2] tensor on %s" % self.values.device)
+        if (logits is not None) != (self.logits is not None):
+            raise ValueError("TrajectoryBuffer.row: logits are stored by a buffer with keep_logits, and only by one")
+        if logits is not None:
+            if not isinstance(logits, torch.Tensor) or tuple(logits.shape) != (self.n_envs, 2, 6) or logits.device != self.values.device \
+                    or not logits.dtype.is_floating_point:
+                raise ValueError("TrajectoryBuffer.row: logits must be a floating-point [n_envs, 2, 6] tensor on %s" % self.values.device)
+            self.logits[t].copy_(logits)
         self.values[t].copy_(values)
         if self.obs is not None:
             self.obs[t].copy_(self.tenv._obs_buffer())
@@ -83,3 +97,35 @@ class TrajectoryBuffer:
 
         return gae(self.rewards, self.values, self.done, gamma, lam, last_values=self.last_values, seat=self.seat, moments=moments,
                    out=out)
+
+    def learner_batch(self, advantages, targets, moments=None):
+        """The buffer as `ppo_loss.ppo_loss` reads it: flat [S] views (S = T * N * 2, sample (t * N + e) * 2 + p) of the actions, logp
+        and the given advantages and targets (float32 [T, N, 2], `advantages()`'s), seat [S / 2] and the old logits [S, 6] where the
+        buffer has them, and `moments` (float64 [3], `advantages()`'s; None: the advantages are used as they are)."""
+        from .gae import _checked
+        from .ppo_loss import LearnerBatch
+
+        torch = self.tenv._torch
+        shape, dev = (self.T, self.n_envs, 2), self.values.device
+        _checked("advantages", advantages, torch.float32, shape, dev, torch)
+        _checked("targets", targets, torch.float32, shape, dev, torch)
+        if moments is not None:
+            _checked("moments", moments, torch.float64, (3,), dev, torch)
+        S = self.T * self.n_envs * 2
+        return LearnerBatch(self.actions.view(S), self.logp.view(S), advantages.view(S), targets.view(S),
+                            self.seat.view(S // 2) if self.seat is not None else None,
+                            self.logits.view(S, 6) if self.logits is not None else None, moments)
+
+    def minibatches(self, size, generator=None):
+        """Index tensors (int32 [size], the last one shorter) that cut one permutation of the samples 0 .. S - 1, drawn on the
+        buffer's device (generator: a torch.Generator of that device; None: the device's default one)."""
+        torch = self.tenv._torch
+        size = int(size)
+        if size < 1:
+            raise ValueError("TrajectoryBuffer.minibatches: size must be at least 1, not %d" % size)
+        S = self.T * self.n_envs * 2
+        if S >= 2 ** 31:
+            raise ValueError("TrajectoryBuffer.minibatches: %d samples do not fit an int32 index" % S)
+        perm = torch.randperm(S, dtype=torch.int32, device=self.values.device, generator=generator)
+        for lo in range(0, S, size):
+            yield perm[lo:lo + size]
