@@ -1145,6 +1145,105 @@ int oc_ppo_loss(const OcPpoLoss* q, void* stream);
  */
 int oc_ppo_loss_plan(int64_t n_minibatch, int with_index, int with_seat, int with_moments, int with_old_logits, int with_terms, char* out, size_t out_size);
 
+/*
+ * The learner's actor-critic on featurize_state rows (ABI 6: entry points added beside the others; no existing signature, struct or
+ * option changes, so the version stays) — the one stage of a PPO iteration that was still a torch module: the policy that is called
+ * once per collected step and, forward and backward, once per minibatch.  It is the partner's small dense network with a value
+ * output, a shared trunk:
+ *   a1 = relu(x W1 + b1),  a2 = relu(a1 W2 + b2),  logits = a2 Wp + bp (six),  value = a2 wv + bv (one)
+ * all f32, row-major [in][out] (the Keras Dense layout), in_dim = 2 * (num_pots * 10 + 26) + 4 for num_pots in 0..4 (56, 76, 96, 116
+ * or 136), 1 <= h1, h2 <= 64.  oc_policy_forward evaluates it for every row of a call in one launch, oc_policy_backward turns the
+ * gradients with respect to logits and values (oc_ppo_loss writes them) into the gradients of the eight weight arrays, in two
+ * launches and without saved activations: it reads the 4 * in_dim bytes of features per row again rather than 512 bytes of
+ * activations (csrc/policy.hpp).
+ *
+ * Forward arithmetic.  All f32.  With x the feature row, every unit is an fmaf chain over its inputs in ascending index that starts
+ * from the bias, every hidden unit followed by max(., 0) — OcDensePolicy's chain, so that the six logits equal oc_partner_logits'
+ * bit for bit on the same weights and row:
+ *   pre1_j = fmaf(x_{in_dim-1}, w1[in_dim-1][j], ... fmaf(x_1, w1[1][j], fmaf(x_0, w1[0][j], b1_j)) ...),  a1_j = max(pre1_j, 0)     j < h1
+ *   pre2_j = the same chain over a1_0 .. a1_{h1-1} with w2, from b2_j,  a2_j = max(pre2_j, 0)                                      j < h2
+ *   logit_j = the same chain over a2_0 .. a2_{h2-1} with wp, from bp_j (j < 6);  value = the same chain with wv, from bv
+ * one rounding per step, no wider accumulator (v_mfma_f32_32x32x2_f32, K steps in order from the bias; the value head is the seventh
+ * row of the last layer's tile).  (max(., 0) of a NaN is 0; a chain whose value is exactly -0 may come out as +0.)
+ *
+ * Backward arithmetic.  All f32.  With gl_0..5 and gv the row's upstream gradients (delta3_j = gl_j for j < 6, delta3_6 = gv):
+ *   delta2_u = pre2_u > 0 ? fmaf(wv[u], gv, fmaf(wp[u][5], gl_5, ... fmaf(wp[u][0], gl_0, +0) ...)) : 0          u < h2
+ *   delta1_i = pre1_i > 0 ? the fmaf chain over u = 0 .. h2-1 of w2[i][u] * delta2_u, from +0 : 0                   i < h1
+ * The ReLU derivative is 1 where the f32 pre-activation is > 0 and 0 elsewhere (0 at exactly 0 and at a NaN): torch's convention.
+ * Every weight gradient is the sum over the call's rows of input_i * delta_j — gw1[i][j] of x_i * delta1_j, gw2[i][j] of
+ * a1_i * delta2_j, gwp[i][j] of a2_i * delta3_j, gwv[i] of a2_i * gv — and every bias gradient the sum of delta_j.  The order of
+ * summation is fixed:
+ *   rows are taken in tiles of 32 consecutive rows of the call; tile k belongs to wavefront k % W of workgroup (k / W) % G, where W
+ *   is the number of wavefronts of a workgroup and G the grid (oc_policy_plan states both);
+ *   a wavefront adds its tiles in ascending order and the rows of a tile in ascending order into ONE f32 accumulator per element, by
+ *   fmaf for the weights (one rounding per row) and by addition for the biases, from +0;
+ *   a workgroup adds its wavefronts' accumulators in ascending order, ((w0 + w1) + w2) + w3, into d_partials[workgroup];
+ *   the gradient is d_partials[0] + d_partials[1] + ... in ascending order (k_policy_grad_sum).
+ * No floating-point atomics: a call repeats bit for bit.  A tile whose 32 rows have only zero upstream gradients is not computed (it
+ * would add +-0 to accumulators that are never -0); its features are not read.
+ *
+ * Rows.  Without d_index the call's row r is feature row first_row + r.  With d_index it is feature row d_index[r]; first_row is
+ * not read; an entry outside 0 .. n_feature_rows - 1 is an out-of-range row: nothing is read for it, oc_policy_forward writes
+ * +0.0f logits and value for it, and it contributes nothing to oc_policy_backward whatever its upstream gradients hold
+ * (oc_ppo_loss leaves such entries out too).  An index may name a row more than once.
+ */
+typedef struct OcActorCritic {     /* all f32, row-major [in][out]; read at every call: an optimiser may update them in place */
+    const float *d_w1, *d_b1;      /* [in_dim][h1], [h1] */
+    const float *d_w2, *d_b2;      /* [h1][h2], [h2] */
+    const float *d_wp, *d_bp;      /* [h2][6], [6] */
+    const float *d_wv, *d_bv;      /* [h2], [1] */
+    int in_dim, h1, h2;
+} OcActorCritic;
+
+typedef struct OcPolicyRows {
+    const float* d_features;       /* [n_feature_rows][in_dim] f32, 16-byte aligned (oc_featurize's [n_envs][2][in_dim] is 2 n_envs rows) */
+    int64_t n_feature_rows;
+    const int32_t* d_index;        /* [n_rows] or NULL; 4-byte aligned; needs n_feature_rows < 2^31 */
+    int64_t first_row;             /* without d_index: the first feature row of the call */
+    int64_t n_rows;
+} OcPolicyRows;
+
+typedef struct OcPolicyGrads {     /* the gradients of OcActorCritic's arrays, same shapes; 4-byte aligned; OVERWRITTEN */
+    float *d_w1, *d_b1, *d_w2, *d_b2, *d_wp, *d_bp, *d_wv, *d_bv;
+} OcPolicyGrads;
+
+/*
+ * oc_policy_forward — k_policy_forward, one launch: a persistent grid whose wavefronts take 32-row tiles.
+ *   d_logits [n_rows][6] f32, 8-byte aligned;  d_values [n_rows] f32, 4-byte aligned; the weight and bias arrays 4-byte aligned
+ * n_rows == 0 launches nothing.
+ * OC_EINVAL, before any device call, with this entry point's name in front of the message: a NULL policy, rows, array of either,
+ * d_logits or d_values (d_index may be NULL); a misaligned array; an in_dim that is no feature length; h1 or h2 outside 1..64;
+ * n_rows < 0 or above 2^40; n_feature_rows < 0; n_feature_rows >= 2^31 with d_index; without d_index a first_row < 0 or
+ * first_row + n_rows > n_feature_rows.
+ */
+int oc_policy_forward(const OcActorCritic* policy, const OcPolicyRows* rows, float* d_logits, float* d_values, void* stream);
+
+/*
+ * oc_policy_backward — k_policy_backward, which recomputes the hidden layers of every tile, and k_policy_grad_sum behind it.
+ *   d_grad_logits [n_rows][6] f32, 8-byte aligned;  d_grad_values [n_rows] f32, 4-byte aligned
+ *   grads         the eight gradient arrays: OVERWRITTEN, not accumulated into
+ *   d_partials    f32 scratch of the caller, 4-byte aligned: as many rows of as many floats as oc_policy_plan states for the call
+ *                 ("256 partial(s) of 10823 floats"; a row is the eight gradient arrays one behind the other, w1 b1 w2 b2 wp bp wv bv)
+ * n_rows == 0 launches k_policy_grad_sum alone, which zeroes the gradients.
+ * OC_EINVAL as oc_policy_forward, and for a NULL or misaligned d_grad_logits, d_grad_values, grads, gradient array or d_partials.
+ */
+int oc_policy_backward(const OcActorCritic* policy, const OcPolicyRows* rows, const float* d_grad_logits, const float* d_grad_values,
+                       const OcPolicyGrads* grads, float* d_partials, void* stream);
+
+/*
+ * oc_policy_plan — what oc_policy_forward (backward == 0) or oc_policy_backward would launch, as text:
+ *   "k_policy_forward grid=256, 256 lanes (4 wavefronts x 32-row tiles), 128 rows per workgroup per pass, 32 x 32 x 2 f32 MFMA, K 96 -> 64 -> 64 -> 32 (h1 = 64, h2 = 64, 6 logits + value, zero-padded), index=no, 99968 B LDS"
+ *   "k_policy_backward<F0=0,NF=3,REST> grid=256, 256 lanes (4 wavefronts x 32-row tiles), 128 rows per workgroup per pass, 32 x 32 x 2 f32 MFMA, 12 accumulator tiles per wavefront, index=yes, 147456 B LDS + k_policy_grad_sum grid=43, 256 lanes, 256 partial(s) of 10823 floats"
+ *   "nothing to launch (no rows)"
+ *   "k_policy_grad_sum grid=43, 256 lanes, 0 partial(s) of 10823 floats (no rows: the gradients are zeroed)"
+ * The grid is the number of workgroups, at most 256.  With 116 and 136 inputs a backward workgroup has three wavefronts (its LDS
+ * holds no more) and a second k_policy_backward launch ("+ k_policy_backward<F0=3,NF=2> grid=256 (feature rows 96.. of gw1)")
+ * accumulates the rows of gw1 that the first one's registers do not hold; the order of summation is the same.  The checks that need no array apply; usable without a GPU, like the other plan calls; refusals carry the name of the entry
+ * point the plan is for.
+ *   out, out_size caller's text buffer (>= 384 bytes holds every answer)
+ */
+int oc_policy_plan(int64_t n_rows, int with_index, int in_dim, int h1, int h2, int backward, char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

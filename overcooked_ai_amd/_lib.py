@@ -29,7 +29,8 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_step_server_open", "oc_step_server_requests", "oc_step_server_responses", "oc_step_server_resume",
            "oc_step_server_play", "oc_step_server_sync", "oc_step_server_steps", "oc_step_server_close",
            "oc_sample_actions", "oc_multi_agent_step_sample", "oc_multi_agent_step_sample_plan",
-           "oc_partner_logits", "oc_partner_logits_plan", "oc_gae", "oc_gae_plan", "oc_ppo_loss", "oc_ppo_loss_plan")
+           "oc_partner_logits", "oc_partner_logits_plan", "oc_gae", "oc_gae_plan", "oc_ppo_loss", "oc_ppo_loss_plan",
+           "oc_policy_forward", "oc_policy_backward", "oc_policy_plan")
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
 
 
@@ -95,6 +96,22 @@ class OcPpoLoss(ctypes.Structure):
                 ("n_minibatch", ctypes.c_int64), ("d_grad_logits", ctypes.c_void_p), ("d_grad_values", ctypes.c_void_p),
                 ("d_partials", ctypes.c_void_p), ("d_stats", ctypes.c_void_p), ("d_terms_out", ctypes.c_void_p), ("clip_param", ctypes.c_float),
                 ("vf_clip_param", ctypes.c_float), ("vf_loss_coeff", ctypes.c_float), ("entropy_coeff", ctypes.c_float), ("kl_coeff", ctypes.c_float)]
+
+
+class OcActorCritic(ctypes.Structure):
+    _fields_ = [("d_w1", ctypes.c_void_p), ("d_b1", ctypes.c_void_p), ("d_w2", ctypes.c_void_p), ("d_b2", ctypes.c_void_p),
+                ("d_wp", ctypes.c_void_p), ("d_bp", ctypes.c_void_p), ("d_wv", ctypes.c_void_p), ("d_bv", ctypes.c_void_p),
+                ("in_dim", ctypes.c_int), ("h1", ctypes.c_int), ("h2", ctypes.c_int)]
+
+
+class OcPolicyRows(ctypes.Structure):
+    _fields_ = [("d_features", ctypes.c_void_p), ("n_feature_rows", ctypes.c_int64), ("d_index", ctypes.c_void_p),
+                ("first_row", ctypes.c_int64), ("n_rows", ctypes.c_int64)]
+
+
+class OcPolicyGrads(ctypes.Structure):
+    _fields_ = [("d_w1", ctypes.c_void_p), ("d_b1", ctypes.c_void_p), ("d_w2", ctypes.c_void_p), ("d_b2", ctypes.c_void_p),
+                ("d_wp", ctypes.c_void_p), ("d_bp", ctypes.c_void_p), ("d_wv", ctypes.c_void_p), ("d_bv", ctypes.c_void_p)]
 
 
 class OcAmdError(RuntimeError):
@@ -231,6 +248,13 @@ def load():
     L.oc_ppo_loss.argtypes = [ctypes.POINTER(OcPpoLoss), vp]
     L.oc_ppo_loss_plan.restype = i32
     L.oc_ppo_loss_plan.argtypes = [i64, i32, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    acp, prp = ctypes.POINTER(OcActorCritic), ctypes.POINTER(OcPolicyRows)
+    L.oc_policy_forward.restype = i32
+    L.oc_policy_forward.argtypes = [acp, prp, vp, vp, vp]
+    L.oc_policy_backward.restype = i32
+    L.oc_policy_backward.argtypes = [acp, prp, vp, vp, ctypes.POINTER(OcPolicyGrads), vp, vp]
+    L.oc_policy_plan.restype = i32
+    L.oc_policy_plan.argtypes = [i64, i32, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

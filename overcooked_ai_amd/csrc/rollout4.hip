@@ -4,7 +4,8 @@
 // of one 80-second compile.  oc_amd.hip (choose_rollout) picks the instance; the unit that compiles it launches it
 // (launch_rollout) or, for oc_rollout_plan, names it and its LDS bytes (describe_rollout).
 // The OC_R4_PART == 2 unit, the shortest of the four, also compiles partner.hpp (k_partner_logits and its two entry points) and
-// gae.hpp (k_gae, k_gae_moments and theirs) and ppo_loss.hpp (k_ppo_loss, k_ppo_loss_stats and theirs).
+// gae.hpp (k_gae, k_gae_moments and theirs), ppo_loss.hpp (k_ppo_loss, k_ppo_loss_stats and theirs) and policy.hpp (k_policy_forward,
+// k_policy_backward, k_policy_grad_sum and theirs).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -170,4 +171,5 @@ template void describe_rollout<OC_R4_PART>(const Rollout4Call& c, char* out, siz
 #include "partner.hpp"  // k_partner_logits, oc_partner_logits, oc_partner_logits_plan
 #include "gae.hpp"      // k_gae, k_gae_moments, oc_gae, oc_gae_plan
 #include "ppo_loss.hpp" // k_ppo_loss, k_ppo_loss_stats, oc_ppo_loss, oc_ppo_loss_plan
+#include "policy.hpp"   // k_policy_forward, k_policy_backward, k_policy_grad_sum, oc_policy_forward, oc_policy_backward, oc_policy_plan
 #endif
