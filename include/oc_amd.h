@@ -1244,6 +1244,115 @@ int oc_policy_backward(const OcActorCritic* policy, const OcPolicyRows* rows, co
  */
 int oc_policy_plan(int64_t n_rows, int with_index, int in_dim, int h1, int h2, int backward, char* out, size_t out_size);
 
+/*
+ * The learner's optimiser step (ABI 6: entry points added beside the others; no existing signature, struct or option changes, so the
+ * version stays) — gradient clipping by global norm (torch's clip_grad_norm_) and Adam on the eight arrays of an OcActorCritic in
+ * ONE launch of one workgroup (k_adam_step, csrc/adam.hpp), where a learner would run clip_grad_norm_ and torch.optim.Adam: a
+ * dozen small launches.
+ *
+ * Flat order.  Element i runs over the concatenation w1, b1, w2, b2, wp, bp, wv, bv — the order of a partial row of
+ * oc_policy_backward; n = in_dim * h1 + h1 + h1 * h2 + h2 + h2 * 6 + 6 + h2 + 1 (73 for 56/1/1, 10 823 for 96/64/64, 13 383 for 136/64/64).
+ * Gradient scale.  gs = (float)*d_grad_scale where that f64 pointer is given (oc_ppo_loss's d_stats[7], 1 / count), else 1.0f;
+ *   g_i = graw_i * gs, one f32 rounding (with gs == 1 the product is exact).
+ * Norm.  q_i = (double)g_i * (double)g_i (exact).  Lane l of the ONE workgroup of 256 lanes adds the q_i with i % 256 == l in
+ *   ascending i, from +0, in f64; the 256 lane sums are added by the fixed tree s[l] += s[l + k] for k = 128, 64, ..., 1;
+ *   norm = (float)sqrt(s[0]).  The order of summation is part of the interface, which is why there is one workgroup.
+ * Clip.  With max_grad_norm finite and > 0: c = min(max_grad_norm / (norm + 1e-6f), 1.0f) in f32 and g_i = g_i * c (torch's
+ *   clip_grad_norm_); otherwise c = 1 and there is no multiply.
+ * Skipped steps.  The step is skipped if norm is not finite (a NaN or an infinity among the gradients, or a sum of squares beyond
+ *   f32), and if d_grad_scale is given and is 0 (oc_ppo_loss's count == 0: no learner sample in the minibatch).  A skipped step
+ *   writes nothing to parameters or moments, leaves steps and the beta powers alone and increments skipped: a NaN must not reach
+ *   the weights, and an empty minibatch must not move them by momentum.
+ * Clock.  d_clock = {steps, beta1^steps, beta2^steps, skipped} in f64; the caller initialises it to {0, 1, 1, 0}.  A step taken
+ *   sets steps += 1, p1 *= (double)beta1, p2 *= (double)beta2 — running products, not pow — and then, in f64,
+ *   bc1 = 1 - p1;  bc2s = sqrt(1 - p2);  step_size = (float)((double)lr / bc1);  rbc2s = (float)bc2s
+ * Update.  Every operation f32 with one rounding, in this order, with no contraction, sqrtf and / correctly rounded; 1 - beta is
+ *   computed once in f32:
+ *   m_i = m_i + (g_i - m_i) * (1 - beta1)
+ *   v_i = v_i * beta2 + (g_i * g_i) * (1 - beta2)
+ *   den = sqrtf(v_i) / rbc2s + eps
+ *   p_i = p_i - step_size * (m_i / den)
+ *   (torch.optim.Adam's update — bias-corrected, eps added to sqrt(v) / sqrt(1 - beta2^t) — in another order of operations)
+ * Info.  d_info = {norm before clipping, c, gs, 1 if skipped else 0} in f64; on a skipped step c is reported as 0, and a norm that
+ *   is a NaN is reported as a NaN (its sign and payload are not specified).
+ * No atomics: a call on the same inputs gives the same bits.  The gradients are read only.
+ */
+typedef struct OcAdam {
+    float *d_m[8], *d_v[8];      /* first and second moments, OcActorCritic's shapes and order; 4-byte aligned; updated in place */
+    double* d_clock;             /* [4] f64, 8-byte aligned */
+    const double* d_grad_scale;  /* f64 scalar on the device, or NULL */
+    double* d_info;              /* [4] f64 out, or NULL */
+    float lr, beta1, beta2, eps, max_grad_norm;
+} OcAdam;
+
+/*
+ * oc_adam_step — k_adam_step, one launch of one workgroup.  params' eight arrays are WRITTEN THROUGH (the struct declares them
+ * const for the forward and backward calls); grads' are read.
+ * OC_EINVAL, before any device call, with this entry point's name in front of the message: a NULL struct or array (d_grad_scale
+ * and d_info may be NULL); a misaligned array (weights, gradients and moments 4 bytes; d_clock, d_grad_scale, d_info 8); an in_dim
+ * that is no feature length; h1 or h2 outside 1..64; lr negative or not finite; a beta outside [0, 1); eps not positive;
+ * max_grad_norm NaN (an infinity, 0 or a negative number: no clipping).
+ */
+int oc_adam_step(const OcActorCritic* params, const OcPolicyGrads* grads, const OcAdam* adam, void* stream);
+
+/*
+ * oc_adam_plan — what oc_adam_step would launch, as text:
+ *   "k_adam_step grid=1, 256 lanes, 10823 elements (43 per lane), flat order w1 b1 w2 b2 wp bp wv bv, f64 norm in a fixed tree, 55580 B LDS"
+ * The checks of the shape apply; usable without a GPU, like the other plan calls; refusals carry oc_adam_step's name.
+ *   out, out_size caller's text buffer (>= 256 bytes holds every answer)
+ */
+int oc_adam_plan(int in_dim, int h1, int h2, char* out, size_t out_size);
+
+/*
+ * The learner's update (ABI 6: entry points added beside the others) — a run of minibatches in ONE C call: for minibatch k of the
+ * index, entries k M .. min((k + 1) M, n_index) - 1 (the last may be shorter), it enqueues on the caller's stream, with no host
+ * synchronisation, exactly what these four calls enqueue:
+ *   oc_policy_forward  rows d_index + k M of d_features -> d_logits, d_values
+ *   oc_ppo_loss        the batch side and the five coefficients of `loss`, the same index entries as samples (an entry names both
+ *                      the sample and its feature row) -> d_grad_logits, d_grad_values, d_loss_partials, d_stats[k]
+ *   oc_policy_backward on those RAW gradients (not divided by the count) -> grads, through d_policy_partials
+ *   oc_adam_step       with d_grad_scale = &d_stats[k][7] (1 / count; 0: the step is skipped) and d_info[k]
+ * (csrc/ppo_update.hpp: host code; the existing launch code, no kernel of its own).  The results are bit for bit those of the four
+ * calls made one by one.  The scratch is one minibatch's and is reused from minibatch to minibatch: the stream orders them.
+ * Of `loss`, d_logits, d_values, d_index, first_sample, n_minibatch, d_grad_logits, d_grad_values, d_partials, d_stats and d_terms_out
+ * are not read; of `adam`, d_grad_scale and d_info are not.
+ */
+typedef struct OcPpoUpdate {
+    const float*   d_features;         /* [n_feature_rows][in_dim] f32, 16-byte aligned (OcPolicyRows') */
+    int64_t n_feature_rows;
+    const int32_t* d_index;            /* [n_index] i32, 4-byte aligned; required */
+    int64_t n_index;                   /* >= 0, below 2^31 */
+    int64_t minibatch;                 /* M >= 1 */
+    float*         d_logits;           /* scratch [min(M, n_index)][6] f32, 16-byte aligned */
+    float*         d_values;           /* scratch [min(M, n_index)] f32, 4-byte aligned */
+    float*         d_grad_logits;      /* scratch [min(M, n_index)][6] f32, 16-byte aligned */
+    float*         d_grad_values;      /* scratch [min(M, n_index)] f32, 4-byte aligned */
+    double*        d_loss_partials;    /* scratch f64, 8-byte aligned: the rows oc_ppo_update_plan states */
+    float*         d_policy_partials;  /* scratch f32, 4-byte aligned: the rows oc_ppo_update_plan states */
+    OcPolicyGrads  grads;              /* scratch: the eight gradient arrays; they hold the last minibatch's raw gradients afterwards */
+    double*        d_stats;            /* [K][8] f64 out: oc_ppo_loss's d_stats of every minibatch; 8-byte aligned */
+    double*        d_info;             /* [K][4] f64 out: oc_adam_step's d_info of every minibatch; 8-byte aligned */
+} OcPpoUpdate;
+
+/*
+ * oc_ppo_update — K = ceil(n_index / M) minibatches.  n_index == 0 launches nothing.
+ * OC_EINVAL, before the FIRST launch of the call, with this entry point's name in front of the message: a NULL policy, loss, adam
+ * or update; n_index < 0 or >= 2^31; minibatch < 1; a NULL d_index, d_stats, d_info or d_loss_partials; and every refusal of the
+ * four calls above for every minibatch, in their words.
+ */
+int oc_ppo_update(const OcActorCritic* policy, const OcPpoLoss* loss, const OcAdam* adam, const OcPpoUpdate* update, void* stream);
+
+/*
+ * oc_ppo_update_plan — what oc_ppo_update would launch, as text: K, the kernels of one (the first, longest) minibatch in the words
+ * of oc_policy_plan, oc_ppo_loss_plan and oc_adam_plan, and the sizes of the scratch and of the outputs:
+ *   "16 minibatch(es) of 4096 rows (the last 4096), no host synchronisation, each: [k_policy_forward grid=32, ...] + [k_ppo_loss<OLD=false> grid=4, ...] + [k_policy_backward<F0=0,NF=3,REST> grid=32, ... + k_policy_grad_sum grid=43, ...] + [k_adam_step grid=1, ...]; scratch: logits 4096 x 6 f32, values 4096 f32, grad_logits 4096 x 6 f32, grad_values 4096 f32, loss partials 4 x 6 f64, policy partials 32 x 10823 f32, gradients 10823 f32; out: stats 16 x 8 f64, info 16 x 4 f64"
+ *   "nothing to launch (no index); scratch: ..."
+ * The checks that need no array apply; usable without a GPU, like the other plan calls; refusals carry oc_ppo_update's name.
+ *   out, out_size caller's text buffer (>= 2048 bytes holds every answer)
+ */
+int oc_ppo_update_plan(int64_t n_index, int64_t minibatch, int in_dim, int h1, int h2, int with_seat, int with_moments, int with_old_logits,
+                       char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

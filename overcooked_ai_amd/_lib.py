@@ -30,7 +30,7 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_step_server_play", "oc_step_server_sync", "oc_step_server_steps", "oc_step_server_close",
            "oc_sample_actions", "oc_multi_agent_step_sample", "oc_multi_agent_step_sample_plan",
            "oc_partner_logits", "oc_partner_logits_plan", "oc_gae", "oc_gae_plan", "oc_ppo_loss", "oc_ppo_loss_plan",
-           "oc_policy_forward", "oc_policy_backward", "oc_policy_plan")
+           "oc_policy_forward", "oc_policy_backward", "oc_policy_plan", "oc_adam_step", "oc_adam_plan", "oc_ppo_update", "oc_ppo_update_plan")
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
 
 
@@ -112,6 +112,19 @@ class OcPolicyRows(ctypes.Structure):
 class OcPolicyGrads(ctypes.Structure):
     _fields_ = [("d_w1", ctypes.c_void_p), ("d_b1", ctypes.c_void_p), ("d_w2", ctypes.c_void_p), ("d_b2", ctypes.c_void_p),
                 ("d_wp", ctypes.c_void_p), ("d_bp", ctypes.c_void_p), ("d_wv", ctypes.c_void_p), ("d_bv", ctypes.c_void_p)]
+
+
+class OcAdam(ctypes.Structure):
+    _fields_ = [("d_m", ctypes.c_void_p * 8), ("d_v", ctypes.c_void_p * 8), ("d_clock", ctypes.c_void_p), ("d_grad_scale", ctypes.c_void_p),
+                ("d_info", ctypes.c_void_p), ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("max_grad_norm", ctypes.c_float)]
+
+
+class OcPpoUpdate(ctypes.Structure):
+    _fields_ = [("d_features", ctypes.c_void_p), ("n_feature_rows", ctypes.c_int64), ("d_index", ctypes.c_void_p), ("n_index", ctypes.c_int64),
+                ("minibatch", ctypes.c_int64), ("d_logits", ctypes.c_void_p), ("d_values", ctypes.c_void_p), ("d_grad_logits", ctypes.c_void_p),
+                ("d_grad_values", ctypes.c_void_p), ("d_loss_partials", ctypes.c_void_p), ("d_policy_partials", ctypes.c_void_p),
+                ("grads", OcPolicyGrads), ("d_stats", ctypes.c_void_p), ("d_info", ctypes.c_void_p)]
 
 
 class OcAmdError(RuntimeError):
@@ -255,6 +268,15 @@ def load():
     L.oc_policy_backward.argtypes = [acp, prp, vp, vp, ctypes.POINTER(OcPolicyGrads), vp, vp]
     L.oc_policy_plan.restype = i32
     L.oc_policy_plan.argtypes = [i64, i32, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    adp = ctypes.POINTER(OcAdam)
+    L.oc_adam_step.restype = i32
+    L.oc_adam_step.argtypes = [acp, ctypes.POINTER(OcPolicyGrads), adp, vp]
+    L.oc_adam_plan.restype = i32
+    L.oc_adam_plan.argtypes = [i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.oc_ppo_update.restype = i32
+    L.oc_ppo_update.argtypes = [acp, ctypes.POINTER(OcPpoLoss), adp, ctypes.POINTER(OcPpoUpdate), vp]
+    L.oc_ppo_update_plan.restype = i32
+    L.oc_ppo_update_plan.argtypes = [i64, i64, i32, i32, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

@@ -579,28 +579,28 @@ const char* const POL_FORWARD_WHO = "oc_policy_forward";
 const char* const POL_BACKWARD_WHO = "oc_policy_backward";
 const char* const POL_PLAN_WHO = "oc_policy_plan";
 
-}  // namespace
-
-extern "C" {
-
-int oc_policy_forward(const OcActorCritic* pol, const OcPolicyRows* rows, float* d_logits, float* d_values, void* stream) {
-    const char* const who = POL_FORWARD_WHO;
+// ---- the two entry points in two halves each: every refusal (no device call), then the launches of a call that passed — so that a
+// caller of several stages (ppo_update.hpp) can make all its refusals before its first launch
+int pol_check_forward(const char* who, const OcActorCritic* pol, const OcPolicyRows* rows, const float* d_logits, const float* d_values) {
     if (int rc = pol_check(who, pol, rows)) return rc;
     if (!d_logits || !d_values) return pol_refuse(who, "NULL d_logits or d_values");
     if ((uintptr_t)d_logits & 7u) return pol_refuse(who, "d_logits must be 8-byte aligned");
     if ((uintptr_t)d_values & 3u) return pol_refuse(who, "d_values must be 4-byte aligned");
+    return OC_OK;
+}
+
+int pol_run_forward(const char* who, const OcActorCritic* pol, const OcPolicyRows* rows, float* d_logits, float* d_values, hipStream_t stream) {
     if (rows->n_rows == 0) return OC_OK;
     PolicyArgs a = pol_args(pol, rows);
     a.logits = d_logits; a.values = d_values;
     const size_t smem = pol_forward_lds(a.in_dim);
     if (want_lds(k_policy_forward, smem))
-        hipLaunchKernelGGL(k_policy_forward, dim3(pol_grid(a.n, PL_WAVES)), dim3(BLOCK), smem, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(k_policy_forward, dim3(pol_grid(a.n, PL_WAVES)), dim3(BLOCK), smem, stream, a);
     return check_launch(who);
 }
 
-int oc_policy_backward(const OcActorCritic* pol, const OcPolicyRows* rows, const float* d_grad_logits, const float* d_grad_values,
-                       const OcPolicyGrads* grads, float* d_partials, void* stream) {
-    const char* const who = POL_BACKWARD_WHO;
+int pol_check_backward(const char* who, const OcActorCritic* pol, const OcPolicyRows* rows, const float* d_grad_logits, const float* d_grad_values,
+                       const OcPolicyGrads* grads, const float* d_partials) {
     if (int rc = pol_check(who, pol, rows)) return rc;
     if (!d_grad_logits || !d_grad_values) return pol_refuse(who, "NULL d_grad_logits or d_grad_values");
     if ((uintptr_t)d_grad_logits & 7u) return pol_refuse(who, "d_grad_logits must be 8-byte aligned");
@@ -613,6 +613,11 @@ int oc_policy_backward(const OcActorCritic* pol, const OcPolicyRows* rows, const
         return pol_refuse(who, "gradient arrays must be 4-byte aligned");
     if (!d_partials) return pol_refuse(who, "d_partials is NULL");
     if ((uintptr_t)d_partials & 3u) return pol_refuse(who, "d_partials must be 4-byte aligned");
+    return OC_OK;
+}
+
+int pol_run_backward(const char* who, const OcActorCritic* pol, const OcPolicyRows* rows, const float* d_grad_logits, const float* d_grad_values,
+                     const OcPolicyGrads* grads, float* d_partials, hipStream_t stream) {
     PolicyArgs a = pol_args(pol, rows);
     a.grad_logits = d_grad_logits; a.grad_values = d_grad_values; a.partials = d_partials;
     const PolicyLayout o = pol_layout(a.in_dim, a.h1, a.h2);
@@ -622,16 +627,33 @@ int oc_policy_backward(const OcActorCritic* pol, const OcPolicyRows* rows, const
     const size_t smem = pol_backward_lds(a.in_dim, waves);
     if (grid > 0) {
         const int nf = pol_nf(a.in_dim);
-        if (nf == 2) pol_launch_backward<0, 2, true>(a, grid, waves, smem, (hipStream_t)stream);
-        else pol_launch_backward<0, 3, true>(a, grid, waves, smem, (hipStream_t)stream);
+        if (nf == 2) pol_launch_backward<0, 2, true>(a, grid, waves, smem, stream);
+        else pol_launch_backward<0, 3, true>(a, grid, waves, smem, stream);
         if (int rc = check_launch(who)) return rc;
-        if (nf == 4) pol_launch_backward<3, 1, false>(a, grid, waves, smem, (hipStream_t)stream);
-        if (nf == 5) pol_launch_backward<3, 2, false>(a, grid, waves, smem, (hipStream_t)stream);
+        if (nf == 4) pol_launch_backward<3, 1, false>(a, grid, waves, smem, stream);
+        if (nf == 5) pol_launch_backward<3, 2, false>(a, grid, waves, smem, stream);
         if (int rc = check_launch(who)) return rc;
     }
     PolicyGradPointers g = {{grads->d_w1, grads->d_b1, grads->d_w2, grads->d_b2, grads->d_wp, grads->d_bp, grads->d_wv, grads->d_bv}};
-    hipLaunchKernelGGL(k_policy_grad_sum, dim3((o.size + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)stream, (const float*)d_partials, (int)grid, o, g);
+    hipLaunchKernelGGL(k_policy_grad_sum, dim3((o.size + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, (const float*)d_partials, (int)grid, o, g);
     return check_launch(who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int oc_policy_forward(const OcActorCritic* pol, const OcPolicyRows* rows, float* d_logits, float* d_values, void* stream) {
+    const char* const who = POL_FORWARD_WHO;
+    if (int rc = pol_check_forward(who, pol, rows, d_logits, d_values)) return rc;
+    return pol_run_forward(who, pol, rows, d_logits, d_values, (hipStream_t)stream);
+}
+
+int oc_policy_backward(const OcActorCritic* pol, const OcPolicyRows* rows, const float* d_grad_logits, const float* d_grad_values,
+                       const OcPolicyGrads* grads, float* d_partials, void* stream) {
+    const char* const who = POL_BACKWARD_WHO;
+    if (int rc = pol_check_backward(who, pol, rows, d_grad_logits, d_grad_values, grads, d_partials)) return rc;
+    return pol_run_backward(who, pol, rows, d_grad_logits, d_grad_values, grads, d_partials, (hipStream_t)stream);
 }
 
 int oc_policy_plan(int64_t n_rows, int with_index, int in_dim, int h1, int h2, int backward, char* out, size_t out_size) {

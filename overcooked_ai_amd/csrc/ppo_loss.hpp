@@ -256,14 +256,15 @@ __global__ __launch_bounds__(64) void k_ppo_loss_stats(const double* __restrict_
 
 const char* const PPO_WHO = "oc_ppo_loss";
 
-int ppo_refuse(const char* why) {
+int ppo_refuse_as(const char* who, const char* why) {
     char msg[sizeof(g_err)];
-    snprintf(msg, sizeof(msg), "%s: %s", PPO_WHO, why);
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
     return fail(OC_EINVAL, msg);
 }
 
 // the check that needs no array (oc_ppo_loss_plan makes this one alone)
-int ppo_check_shape(int64_t n_minibatch) {
+int ppo_check_shape(int64_t n_minibatch, const char* who = PPO_WHO) {
+    auto ppo_refuse = [who](const char* why) { return ppo_refuse_as(who, why); };
     if (n_minibatch < 0) return ppo_refuse("n_minibatch < 0");
     if (n_minibatch > ((int64_t)1 << 38)) return ppo_refuse("n_minibatch above 2^38");
     return OC_OK;
@@ -271,7 +272,9 @@ int ppo_check_shape(int64_t n_minibatch) {
 
 bool ppo_positive(float x) { return x > 0.f && x < __builtin_inff(); }
 
-int ppo_check(const OcPpoLoss* q) {
+// (who: the entry point the refusals name — oc_ppo_loss, or the caller of several stages that makes them ahead of its launches)
+int ppo_check(const OcPpoLoss* q, const char* who = PPO_WHO) {
+    auto ppo_refuse = [who](const char* why) { return ppo_refuse_as(who, why); };
     if (!q) return ppo_refuse("loss is NULL");
     if (!q->d_actions || !q->d_logp_old || !q->d_advantages || !q->d_targets || !q->d_logits || !q->d_values || !q->d_grad_logits ||
         !q->d_grad_values)
@@ -283,7 +286,7 @@ int ppo_check(const OcPpoLoss* q) {
         return ppo_refuse("d_logits_old, d_moments, d_partials and d_stats must be 8-byte aligned");
     if (((uintptr_t)q->d_logits | (uintptr_t)q->d_grad_logits | (uintptr_t)q->d_terms_out) & 15u)
         return ppo_refuse("d_logits, d_grad_logits and d_terms_out must be 16-byte aligned");
-    if (int rc = ppo_check_shape(q->n_minibatch)) return rc;
+    if (int rc = ppo_check_shape(q->n_minibatch, who)) return rc;
     if (q->n_samples < 0) return ppo_refuse("n_samples < 0");
     if (q->d_seat && (q->n_samples & 1)) return ppo_refuse("n_samples must be even with d_seat");
     if (q->d_index) {
@@ -300,16 +303,12 @@ int ppo_check(const OcPpoLoss* q) {
     return OC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int oc_ppo_loss(const OcPpoLoss* q, void* stream) {
-    if (int rc = ppo_check(q)) return rc;
+// the launches of a call that ppo_check has passed
+int ppo_run(const OcPpoLoss* q, hipStream_t stream, const char* who = PPO_WHO) {
     const int64_t m = q->n_minibatch;
     if (m == 0) {  // no row: nothing to launch; the stats of no sample are zeros
-        if (q->d_stats && hipMemsetAsync(q->d_stats, 0, 8 * sizeof(double), (hipStream_t)stream) != hipSuccess) {
-            snprintf(g_err, sizeof(g_err), "%s: %s", PPO_WHO, hipGetErrorString(hipGetLastError()));
+        if (q->d_stats && hipMemsetAsync(q->d_stats, 0, 8 * sizeof(double), stream) != hipSuccess) {
+            snprintf(g_err, sizeof(g_err), "%s: %s", who, hipGetErrorString(hipGetLastError()));
             return OC_ELAUNCH;
         }
         return OC_OK;
@@ -323,12 +322,21 @@ int oc_ppo_loss(const OcPpoLoss* q, void* stream) {
     a.clip_hi = 1.f + q->clip_param;
     a.vf_clip = q->vf_clip_param; a.vf_coeff = q->vf_loss_coeff; a.ent_coeff = q->entropy_coeff; a.kl_coeff = q->kl_coeff;
     const unsigned grid = (unsigned)((m + PPO_P - 1) / PPO_P);
-    if (a.logits_old) hipLaunchKernelGGL((k_ppo_loss<true>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_ppo_loss<false>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, a);
+    if (a.logits_old) hipLaunchKernelGGL((k_ppo_loss<true>), dim3(grid), dim3(BLOCK), 0, stream, a);
+    else hipLaunchKernelGGL((k_ppo_loss<false>), dim3(grid), dim3(BLOCK), 0, stream, a);
     if (q->d_stats)
-        hipLaunchKernelGGL(k_ppo_loss_stats, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)q->d_partials, (int64_t)grid, q->d_stats,
+        hipLaunchKernelGGL(k_ppo_loss_stats, dim3(1), dim3(64), 0, stream, (const double*)q->d_partials, (int64_t)grid, q->d_stats,
                            a.vf_coeff, a.ent_coeff, a.kl_coeff);
-    return check_launch(PPO_WHO);
+    return check_launch(who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int oc_ppo_loss(const OcPpoLoss* q, void* stream) {
+    if (int rc = ppo_check(q)) return rc;
+    return ppo_run(q, (hipStream_t)stream);
 }
 
 int oc_ppo_loss_plan(int64_t n_minibatch, int with_index, int with_seat, int with_moments, int with_old_logits, int with_terms, char* out,

@@ -13,7 +13,8 @@
 `row(t, values)` hands step t's slices to `step_sampled(into=...)`, whose C call then writes the training rewards, the done mask,
 the drawn actions and their log-probabilities there in place of the env's persistent buffers: no copy per step, and the rows are the
 step's own bytes.  `advantages` is `gae.gae` (oc_gae, one launch) over the whole buffer; `learner_batch` hands the buffer to
-`ppo_loss.ppo_loss` as flat [S] views, S = T * N * 2, and `minibatches` cuts a device permutation of the samples into index tensors.
+`ppo_loss.ppo_loss` as flat [S] views, S = T * N * 2, and `minibatches` cuts a device permutation of the samples into index tensors
+(`permutation` hands it over whole, for `learner.PPOLearner.epoch`).
 
 Row t of every tensor meets the alignment the step and the sampler ask for whatever N is: rewards rows are 16 N bytes apart (16-byte
 aligned), logp and values rows 8 N (8), actions rows 2 N (2), done and seat rows N (any address) — a fresh allocation starts on a
@@ -115,6 +116,15 @@ class TrajectoryBuffer:
         return LearnerBatch(self.actions.view(S), self.logp.view(S), advantages.view(S), targets.view(S),
                             self.seat.view(S // 2) if self.seat is not None else None,
                             self.logits.view(S, 6) if self.logits is not None else None, moments)
+
+    def permutation(self, generator=None):
+        """One permutation of the samples 0 .. S - 1 as an int32 [S] tensor on the buffer's device — what `minibatches` cuts, whole:
+        `learner.PPOLearner.epoch` takes it and a minibatch size in ONE call (generator: as for `minibatches`)."""
+        torch = self.tenv._torch
+        S = self.T * self.n_envs * 2
+        if S >= 2 ** 31:
+            raise ValueError("TrajectoryBuffer.permutation: %d samples do not fit an int32 index" % S)
+        return torch.randperm(S, dtype=torch.int32, device=self.values.device, generator=generator)
 
     def minibatches(self, size, generator=None):
         """Index tensors (int32 [size], the last one shorter) that cut one permutation of the samples 0 .. S - 1, drawn on the
