@@ -1353,6 +1353,123 @@ int oc_ppo_update(const OcActorCritic* policy, const OcPpoLoss* loss, const OcAd
 int oc_ppo_update_plan(int64_t n_index, int64_t minibatch, int in_dim, int h1, int h2, int with_seat, int with_moments, int with_old_logits,
                        char* out, size_t out_size);
 
+/*
+ * The behaviour-cloning loss head (ABI 6: entry points added beside the others; no existing signature, struct or option changes, so
+ * the version stays) — the objective of the reference's BC partner (human_aware_rl/imitation/behavior_cloning_tf2.py: Keras's
+ * SparseCategoricalCrossentropy(from_logits=True) with optional class_weight and the sparse categorical accuracy metric) on the
+ * logits of a minibatch, with its gradients, in one launch (k_bc_loss, csrc/bc_loss.hpp).
+ *
+ * Layout.  The batch side is S samples: an action byte each (and, for oc_bc_update, a feature row each).  The minibatch side — the
+ * policy's logits of M samples, in the order of its forward pass — names its samples through d_index, or is samples first_sample ..
+ * first_sample + M - 1.
+ *
+ * Arithmetic.  Per minibatch row, with l = the row's logits; every operation is f32 with one rounding, in this order, with no
+ * contraction, expf and logf in full precision.  The softmax is OcPpoLoss's:
+ *   m = max l_i;  d_i = l_i - m;  w_i = expf(d_i);  S = ((((w_0 + w_1) + w_2) + w_3) + w_4) + w_5
+ *   lp_i = d_i - logf(S);  p_i = w_i / S
+ *   a = d_actions[s];  c = d_class_weights[a], or 1.0f without d_class_weights;  ce = -lp_a;  the row's loss is c * ce
+ *   correct = (a == the lowest i with l_i == m)     (ties go to the lowest index, as argmax does; a row with a NaN logit is never correct)
+ * Gradients of c * ce, per sample, not divided by the count:
+ *   d/dl_i = c * (p_i - [i == a])     (one subtraction, one multiply)
+ *   d/dv   = +0.0f     (d_grad_values is written so that oc_policy_backward runs unchanged: the value head gets zero gradients)
+ * A -inf logit at the taken action gives lp_a = -inf, ce = +inf and p_a = 0: the row's loss, the sum and d_stats[1] are +inf (with a zero
+ * class weight, 0 * inf: a NaN) while its gradient c * (p_i - [i == a]) stays finite.  A -inf logit elsewhere gives p_i = 0 there and
+ * changes nothing else.  Neither is hidden.
+ * Left-out rows.  A row is left out when its index is outside 0 .. S - 1 or when d_actions[s] > 5 (255: the sampler's invalid row).
+ * Its gradients and its loss are +0.0f, by a select, so that a NaN anywhere in its inputs reaches nothing, and it enters no sum.
+ * Class weights.  d_class_weights holds six f32 that must be finite and >= 0.  They are read on the device: the host checks the
+ * pointer's alignment and nothing else.
+ * Sums.  d_partials[k] = {count, sum c * ce, number correct, sum c} over the kept rows of minibatch rows [P k, P k + P), P = 1024
+ * (oc_bc_loss_plan states it): each term widened to f64 before it is added, in a fixed tree.  d_stats = {count, loss = sum c * ce /
+ * count, accuracy = number correct / count, mean weight = sum c / count, 0, 0, 0, 1 / count}: the partials added in ascending k; all zeros
+ * when count == 0.  Slot 7 is where oc_adam_step reads d_grad_scale, as it does behind oc_ppo_loss.  The loss divides by the count,
+ * not by the sum of the weights: Keras's class_weight convention.  No floating-point atomics: the same call on the same inputs gives
+ * the same bits.
+ */
+typedef struct OcBcLoss {
+    const uint8_t* d_actions;        /* [S] u8: the demonstrated actions; any address; required */
+    const float*   d_class_weights;  /* [6] f32: the weight of every action, finite and >= 0 (not checked); 4-byte aligned; NULL = all 1 */
+    int64_t n_samples;               /* S >= 0 */
+    const float*   d_logits;         /* [M][6] f32: the policy's logits of the minibatch; 8-byte aligned; required */
+    const int32_t* d_index;          /* [M] i32: the sample of every row; 4-byte aligned; NULL = first_sample + row */
+    int64_t first_sample;            /* read without d_index only */
+    int64_t n_minibatch;             /* M >= 0 */
+    float*         d_grad_logits;    /* [M][6] f32 out; 8-byte aligned; NULL together with d_grad_values: evaluation, no gradient stores */
+    float*         d_grad_values;    /* [M] f32 out: +0.0f everywhere; 4-byte aligned; NULL together with d_grad_logits */
+    float*         d_loss_out;       /* [M] f32 out: c * ce of every row; 4-byte aligned; or NULL */
+    double*        d_partials;       /* [ceil(M / P)][4] f64 out; 8-byte aligned; or NULL (then d_stats must be NULL too) */
+    double*        d_stats;          /* [8] f64 out; 8-byte aligned; or NULL */
+} OcBcLoss;
+
+/*
+ * oc_bc_loss — k_bc_loss, one lane per minibatch row and four rows per lane, and, with d_stats, k_bc_loss_stats behind it (one
+ * wavefront adding the partials).  n_minibatch == 0 launches nothing and returns 0; d_stats is then set to zeros.  With d_grad_logits
+ * and d_grad_values both NULL the call evaluates: sums, stats and d_loss_out only.
+ * OC_EINVAL, before any device call, with this entry point's name in front of the message: a NULL struct, d_actions or d_logits; one
+ * of d_grad_logits and d_grad_values without the other; a misaligned array; n_minibatch < 0 or n_samples < 0; n_samples >= 2^31 with
+ * d_index; without d_index a first_sample < 0 or first_sample + n_minibatch > n_samples; d_stats without d_partials.
+ */
+int oc_bc_loss(const OcBcLoss* q, void* stream);
+
+/*
+ * oc_bc_loss_plan — what oc_bc_loss would launch, as text (with_...: the optional array is given; with_gradients: d_grad_logits and d_grad_values are):
+ *   "k_bc_loss<GRAD=true> grid=4096, 256 lanes (one per sample, 4 tiles of 256), 1024 samples per partial, index=yes class_weights=yes loss_out=no + k_bc_loss_stats grid=1, 64 lanes, 4096 partial(s) (with d_stats)"
+ *   "nothing to launch (no samples)"
+ * Usable without a GPU, like the other plan calls; refusals carry oc_bc_loss's name.
+ *   out, out_size caller's text buffer (>= 256 bytes holds every answer)
+ */
+int oc_bc_loss_plan(int64_t n_minibatch, int with_index, int with_class_weights, int with_gradients, int with_loss_out, char* out, size_t out_size);
+
+/*
+ * The behaviour-cloning update (ABI 6: entry points added beside the others) — OcPpoUpdate's chain with the cross-entropy head: for
+ * minibatch k of the index, entries k M .. min((k + 1) M, n_index) - 1 (the last may be shorter), it enqueues on the caller's stream,
+ * with no host synchronisation, exactly what these four calls enqueue:
+ *   oc_policy_forward  rows d_index + k M of d_features -> d_logits, d_values
+ *   oc_bc_loss         the actions, n_samples and class weights of `loss`, the same index entries as samples (an entry names both the
+ *                      sample and its feature row) -> d_grad_logits, d_grad_values (zeros), d_loss_partials, d_stats[k]
+ *   oc_policy_backward on those RAW gradients (not divided by the count) -> grads, through d_policy_partials
+ *   oc_adam_step       with d_grad_scale = &d_stats[k][7] (1 / count; 0: the step is skipped) and d_info[k]
+ * (csrc/bc_update.hpp: host code; the existing launch code, no kernel of its own).  The results are bit for bit those of the four
+ * calls made one by one.  The scratch is one minibatch's and is reused from minibatch to minibatch: the stream orders them.
+ * Of `loss`, d_logits, d_index, first_sample, n_minibatch, d_grad_logits, d_grad_values, d_loss_out, d_partials and d_stats are not
+ * read; of `adam`, d_grad_scale and d_info are not.
+ */
+typedef struct OcBcUpdate {
+    const float*   d_features;         /* [n_feature_rows][in_dim] f32, 16-byte aligned (OcPolicyRows') */
+    int64_t n_feature_rows;
+    const int32_t* d_index;            /* [n_index] i32, 4-byte aligned; required */
+    int64_t n_index;                   /* >= 0, below 2^31 */
+    int64_t minibatch;                 /* M >= 1 */
+    float*         d_logits;           /* scratch [min(M, n_index)][6] f32, 8-byte aligned */
+    float*         d_values;           /* scratch [min(M, n_index)] f32, 4-byte aligned */
+    float*         d_grad_logits;      /* scratch [min(M, n_index)][6] f32, 8-byte aligned */
+    float*         d_grad_values;      /* scratch [min(M, n_index)] f32, 4-byte aligned */
+    double*        d_loss_partials;    /* scratch f64, 8-byte aligned: the rows oc_bc_update_plan states */
+    float*         d_policy_partials;  /* scratch f32, 4-byte aligned: the rows oc_bc_update_plan states */
+    OcPolicyGrads  grads;              /* scratch: the eight gradient arrays; they hold the last minibatch's raw gradients afterwards */
+    double*        d_stats;            /* [K][8] f64 out: oc_bc_loss's d_stats of every minibatch; 8-byte aligned */
+    double*        d_info;             /* [K][4] f64 out: oc_adam_step's d_info of every minibatch; 8-byte aligned */
+} OcBcUpdate;
+
+/*
+ * oc_bc_update — K = ceil(n_index / M) minibatches.  n_index == 0 launches nothing.
+ * OC_EINVAL, before the FIRST launch of the call, with this entry point's name in front of the message: a NULL policy, loss, adam
+ * or update; n_index < 0 or >= 2^31; minibatch < 1; a NULL d_index, d_stats, d_info or d_loss_partials; and every refusal of the
+ * four calls above for every minibatch, in their words (a NULL d_grad_logits or d_grad_values is oc_policy_backward's refusal here,
+ * not an evaluation).
+ */
+int oc_bc_update(const OcActorCritic* policy, const OcBcLoss* loss, const OcAdam* adam, const OcBcUpdate* update, void* stream);
+
+/*
+ * oc_bc_update_plan — what oc_bc_update would launch, as text: K, the kernels of one (the first, longest) minibatch in the words of
+ * oc_policy_plan, oc_bc_loss_plan and oc_adam_plan, and the sizes of the scratch and of the outputs:
+ *   "16 minibatch(es) of 4096 rows (the last 4096), no host synchronisation, each: [k_policy_forward grid=32, ...] + [k_bc_loss<GRAD=true> grid=4, ...] + [k_policy_backward<F0=0,NF=3,REST> grid=32, ... + k_policy_grad_sum grid=43, ...] + [k_adam_step grid=1, ...]; scratch: logits 4096 x 6 f32, values 4096 f32, grad_logits 4096 x 6 f32, grad_values 4096 f32, loss partials 4 x 4 f64, policy partials 32 x 10823 f32, gradients 10823 f32; out: stats 16 x 8 f64, info 16 x 4 f64"
+ *   "nothing to launch (no index); scratch: ..."
+ * The checks that need no array apply; usable without a GPU, like the other plan calls; refusals carry oc_bc_update's name.
+ *   out, out_size caller's text buffer (>= 2048 bytes holds every answer)
+ */
+int oc_bc_update_plan(int64_t n_index, int64_t minibatch, int in_dim, int h1, int h2, int with_class_weights, char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,8 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_step_server_play", "oc_step_server_sync", "oc_step_server_steps", "oc_step_server_close",
            "oc_sample_actions", "oc_multi_agent_step_sample", "oc_multi_agent_step_sample_plan",
            "oc_partner_logits", "oc_partner_logits_plan", "oc_gae", "oc_gae_plan", "oc_ppo_loss", "oc_ppo_loss_plan",
-           "oc_policy_forward", "oc_policy_backward", "oc_policy_plan", "oc_adam_step", "oc_adam_plan", "oc_ppo_update", "oc_ppo_update_plan")
+           "oc_policy_forward", "oc_policy_backward", "oc_policy_plan", "oc_adam_step", "oc_adam_plan", "oc_ppo_update", "oc_ppo_update_plan",
+           "oc_bc_loss", "oc_bc_loss_plan", "oc_bc_update", "oc_bc_update_plan")
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
 
 
@@ -125,6 +126,16 @@ class OcPpoUpdate(ctypes.Structure):
                 ("minibatch", ctypes.c_int64), ("d_logits", ctypes.c_void_p), ("d_values", ctypes.c_void_p), ("d_grad_logits", ctypes.c_void_p),
                 ("d_grad_values", ctypes.c_void_p), ("d_loss_partials", ctypes.c_void_p), ("d_policy_partials", ctypes.c_void_p),
                 ("grads", OcPolicyGrads), ("d_stats", ctypes.c_void_p), ("d_info", ctypes.c_void_p)]
+
+
+class OcBcLoss(ctypes.Structure):
+    _fields_ = [("d_actions", ctypes.c_void_p), ("d_class_weights", ctypes.c_void_p), ("n_samples", ctypes.c_int64), ("d_logits", ctypes.c_void_p),
+                ("d_index", ctypes.c_void_p), ("first_sample", ctypes.c_int64), ("n_minibatch", ctypes.c_int64), ("d_grad_logits", ctypes.c_void_p),
+                ("d_grad_values", ctypes.c_void_p), ("d_loss_out", ctypes.c_void_p), ("d_partials", ctypes.c_void_p), ("d_stats", ctypes.c_void_p)]
+
+
+class OcBcUpdate(ctypes.Structure):
+    _fields_ = OcPpoUpdate._fields_  # (the same scratch and outputs: the head alone differs)
 
 
 class OcAmdError(RuntimeError):
@@ -277,6 +288,15 @@ def load():
     L.oc_ppo_update.argtypes = [acp, ctypes.POINTER(OcPpoLoss), adp, ctypes.POINTER(OcPpoUpdate), vp]
     L.oc_ppo_update_plan.restype = i32
     L.oc_ppo_update_plan.argtypes = [i64, i64, i32, i32, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    bcp = ctypes.POINTER(OcBcLoss)
+    L.oc_bc_loss.restype = i32
+    L.oc_bc_loss.argtypes = [bcp, vp]
+    L.oc_bc_loss_plan.restype = i32
+    L.oc_bc_loss_plan.argtypes = [i64, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.oc_bc_update.restype = i32
+    L.oc_bc_update.argtypes = [acp, bcp, adp, ctypes.POINTER(OcBcUpdate), vp]
+    L.oc_bc_update_plan.restype = i32
+    L.oc_bc_update_plan.argtypes = [i64, i64, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

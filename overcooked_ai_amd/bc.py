@@ -1,0 +1,275 @@
+"""Behaviour cloning on the device: `bc_loss` (oc_bc_loss: sparse categorical cross-entropy from logits with optional class weights,
+its gradients and its accuracy in one launch) and `BCLearner` (oc_bc_update: forward, loss, backward and optimiser step of a run of
+minibatches in ONE C call) — the reference's BC objective (human_aware_rl/imitation/behavior_cloning_tf2.py) on the partner's network.
+
+    feats, actions = ...                                          # rollout_featurize's feats_out[:-1] with actions[1:], or human data
+    policy = ActorCritic(env.feature_length).to(device)
+    learner = BCLearner(policy, lr=1e-3, class_weights=None)
+    for _ in range(epochs):
+        perm = torch.randperm(n_train, device=device, dtype=torch.int32)
+        stats, info = learner.epoch(feats, actions, perm, 64)     # [K, 8] and [K, 4] on the device
+    held_out = learner.evaluate(feats, actions, validation_index) # BcStats: .loss, .accuracy
+    env = VecOvercookedMultiAgent(..., bc_policy=policy.dense_policy())
+
+or, with autograd and a network of one's own,
+
+    loss, stats = bc_loss(logits, actions, index)
+    loss.backward()
+
+The arithmetic is stated in include/oc_amd.h (OcBcLoss, OcBcUpdate): a row whose index names no sample or whose action is above 5 is
+left out; the loss is the sum of c * ce over the kept rows divided by their count (Keras's class_weight convention); a minibatch
+without a kept row is skipped (`info[..., 3]` is 1).  Nothing here synchronises with the host."""
+import collections
+import ctypes
+import re
+
+import torch
+
+from . import _lib
+from .gae import _checked, _stream
+from .learner import Adam
+from .policy import ActorCritic, _forward, shapes
+
+BcStats = collections.namedtuple("BcStats", "tensor count loss accuracy mean_weight inv_count")
+N_ACTIONS = 6
+
+_PARTIAL = None
+
+
+def plan_bc_loss(n_minibatch, index=False, class_weights=False, gradients=True, loss_out=False):
+    """What bc_loss() launches for M minibatch rows, in oc_bc_loss_plan's words (no device needed)."""
+    out = ctypes.create_string_buffer(320)
+    rc = _lib.load().oc_bc_loss_plan(int(n_minibatch), int(bool(index)), int(bool(class_weights)), int(bool(gradients)), int(bool(loss_out)),
+                                     out, len(out))
+    _lib.check(rc, "oc_bc_loss_plan")
+    return out.value.decode()
+
+
+def plan_bc_update(n_index, minibatch, in_dim=96, h1=64, h2=64, class_weights=False):
+    """What BCLearner.epoch() launches for an index of n_index entries cut into minibatches of `minibatch`, in oc_bc_update_plan's
+    words: K, the kernels of one minibatch and the sizes of the scratch (no device needed)."""
+    out = ctypes.create_string_buffer(2048)
+    rc = _lib.load().oc_bc_update_plan(int(n_index), int(minibatch), int(in_dim), int(h1), int(h2), int(bool(class_weights)), out, len(out))
+    _lib.check(rc, "oc_bc_update_plan")
+    return out.value.decode()
+
+
+def partial_samples():
+    """P, the minibatch rows per row of partial sums, read from oc_bc_loss_plan's words (no device needed)."""
+    global _PARTIAL
+    if _PARTIAL is None:
+        _PARTIAL = int(re.search(r"(\d+) samples per partial", plan_bc_loss(1)).group(1))
+    return _PARTIAL
+
+
+def scratch_rows(n_index, minibatch, in_dim, h1, h2):
+    """(rows of a minibatch, rows of the loss partials, rows of the policy partials, floats of a policy partial), read from the
+    plan's words."""
+    text = plan_bc_update(n_index, minibatch, in_dim, h1, h2)
+    m = re.search(r"scratch: logits (\d+) x 6 f32.*loss partials (\d+) x 4 f64, policy partials (\d+) x (\d+) f32", text)
+    return tuple(int(x) for x in m.groups())
+
+
+def _weights(class_weights):
+    """None, or the six class weights as a float32 [6] host tensor; ValueError for anything that is not six finite numbers >= 0."""
+    if class_weights is None:
+        return None
+    try:
+        w = torch.as_tensor(class_weights).detach().to("cpu", torch.float32).contiguous()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("class_weights must be six finite numbers >= 0 or None, not %r" % (class_weights,))
+    if tuple(w.shape) != (N_ACTIONS,) or not bool(torch.isfinite(w).all()) or not bool((w >= 0).all()):
+        raise ValueError("class_weights must be six finite numbers >= 0 or None, not %r" % (class_weights,))
+    return w
+
+
+def _checked_actions(actions, dev):
+    if not isinstance(actions, torch.Tensor) or actions.dtype != torch.uint8 or not actions.is_contiguous() or actions.device != dev:
+        raise ValueError("actions must be a contiguous uint8 tensor on %s" % dev)
+    return int(actions.numel())
+
+
+def _call(fn, dev, *args):
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        rc = getattr(L, fn)(*args, _stream(dev))
+    _lib.check(rc, fn)
+
+
+def _head(logits, actions, index, first, weights, gradients):
+    """One oc_bc_loss call on checked tensors: (grad_logits or None, stats)."""
+    M, dev = int(logits.shape[0]), logits.device
+    grad_logits = torch.empty((M, N_ACTIONS), dtype=torch.float32, device=dev) if gradients else None
+    grad_values = torch.empty((M,), dtype=torch.float32, device=dev) if gradients else None
+    P = partial_samples()
+    partials = torch.empty((max((M + P - 1) // P, 1), 4), dtype=torch.float64, device=dev)
+    stats = torch.empty((8,), dtype=torch.float64, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    q = _lib.OcBcLoss(ptr(actions), ptr(weights), int(actions.numel()), ptr(logits), ptr(index), int(first), M, ptr(grad_logits), ptr(grad_values),
+                      None, ptr(partials), ptr(stats))
+    _call("oc_bc_loss", dev, ctypes.byref(q))
+    return grad_logits, stats
+
+
+class _BcLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, actions, index, first, weights, box):
+        grad_logits, stats = _head(logits, actions, index, first, weights, True)
+        ctx.save_for_backward(grad_logits, stats)
+        box.append(stats)
+        return stats[1].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad_logits, stats = ctx.saved_tensors
+        scale = (grad_out.to(torch.float64) * stats[7]).to(torch.float32)  # a device scalar: grad_out / count
+        return grad_logits * scale, None, None, None, None, None
+
+
+def _stats(t):
+    return BcStats(t, t[0], t[1], t[2], t[3], t[7])
+
+
+def bc_loss(logits, actions, index=None, first=0, class_weights=None):
+    """(loss, stats) of the policy's logits float32 [M, 6] on the demonstrated actions, a contiguous uint8 tensor of S elements, that
+    index int32 [M] names (None: samples first .. first + M - 1).  loss: a 0-dim float32 tensor, the sum over the kept rows of
+    class_weights[a] * cross-entropy divided by their count, whose backward() hands the logits the gradients the same launch computed.
+    stats: BcStats — the float64 [8] tensor on the device and 0-dim views of it (count, loss, accuracy, mean_weight, inv_count).
+    class_weights: six finite numbers >= 0, or None.  Raises ValueError for a tensor of another dtype, shape, device or layout and for
+    a tensor on the host (there is no CPU fallback)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[1] != N_ACTIONS:
+        raise ValueError("logits must be a contiguous float32 [M, 6] tensor")
+    M, dev = int(logits.shape[0]), logits.device
+    _checked("logits", logits, torch.float32, (M, N_ACTIONS), dev, torch)
+    S = _checked_actions(actions, dev)
+    if index is not None:
+        _checked("index", index, torch.int32, (M,), dev, torch)
+        if S >= 2 ** 31:
+            raise ValueError("an index names samples below 2^31, there are %d" % S)
+        first = 0
+    else:
+        first = int(first)
+        if first < 0 or first + M > S:
+            raise ValueError("samples %d .. %d lie outside the actions' 0 .. %d" % (first, first + M - 1, S - 1))
+    weights = _weights(class_weights)
+    if dev.type != "cuda":
+        raise ValueError("bc_loss works on device tensors, not on %s (there is no CPU fallback)" % dev)
+    if weights is not None:
+        weights = weights.to(dev)
+    box = []
+    loss = _BcLossFunction.apply(logits, actions, index, first, weights, box)
+    return loss, _stats(box[0])
+
+
+class BCLearner:
+    """The whole update of a behaviour-cloning minibatch — policy forward, weighted cross-entropy, backward to the weights, clipped
+    Adam step — as stream-ordered kernels behind ONE C call (oc_bc_update), for one minibatch (`update`) or a whole pass over a
+    permutation (`epoch`), and `evaluate`, the loss and accuracy of held-out samples.  The optimiser's hyperparameters are Adam's
+    (`self.adam`, whose state_dict holds the moments).  The value head gets zero gradients.  No autograd: the parameters' `.grad`s are
+    not touched."""
+
+    def __init__(self, policy, lr=1e-3, class_weights=None, max_grad_norm=None, betas=(0.9, 0.999), eps=1e-8):
+        if not isinstance(policy, ActorCritic):
+            raise ValueError("BCLearner: policy must be an ActorCritic")
+        self.adam = Adam(policy, lr, betas, eps, max_grad_norm)
+        self.policy = policy
+        self.class_weights = _weights(class_weights)
+        self._weights_on = None  # the class weights on the parameters' device
+        self._scratch = {}       # (rows of a minibatch) -> the tensors of one minibatch
+        self._calls = {}         # the addresses and sizes of a call -> its ctypes structs
+
+    def scratch(self, rows):
+        """The scratch of minibatches of up to `rows` rows, as a dict of tensors: logits, values, grad_logits, grad_values, the loss
+        and policy partials and `grads`, the eight RAW gradient arrays (a sum over the minibatch, not divided by its count)."""
+        return self._scratch[rows]
+
+    def _device_weights(self, dev):
+        if self.class_weights is None:
+            return None
+        if self._weights_on is None or self._weights_on.device != dev:
+            self._weights_on = self.class_weights.to(dev)
+        return self._weights_on
+
+    def _check_batch(self, features, actions, index, dev):
+        pol = self.policy
+        if not isinstance(features, torch.Tensor) or features.dim() < 2 or features.shape[-1] != pol.in_dim or features.dtype != torch.float32 \
+                or not features.is_contiguous() or features.device != dev:
+            raise ValueError("features must be a contiguous float32 [..., %d] tensor on %s" % (pol.in_dim, dev))
+        if features.data_ptr() % 16:
+            raise ValueError("features must be 16-byte aligned")
+        S = _checked_actions(actions, dev)
+        if S != features.numel() // pol.in_dim:
+            raise ValueError("actions must have one element per feature row: %d, not %d" % (features.numel() // pol.in_dim, S))
+        if index is not None:
+            if not isinstance(index, torch.Tensor) or index.dim() != 1:
+                raise ValueError("index must be a contiguous int32 [n] tensor")
+            _checked("index", index, torch.int32, (int(index.shape[0]),), dev, torch)
+            if S >= 2 ** 31:
+                raise ValueError("an index names samples and feature rows below 2^31")
+        return S
+
+    def _run(self, features, actions, index, minibatch):
+        params, dev = self.adam._device_params()
+        if index is None:
+            raise ValueError("index must be a contiguous int32 [n] tensor")
+        S = self._check_batch(features, actions, index, dev)
+        n = int(index.shape[0])
+        minibatch = int(minibatch)
+        if minibatch < 1:
+            raise ValueError("minibatch must be at least 1, not %d" % minibatch)
+        self.adam._state(dev)
+        weights = self._device_weights(dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        key = (n, minibatch, ptr(features), S, ptr(index), ptr(actions), ptr(weights)) + tuple(ptr(p) for p in params) \
+            + tuple(ptr(t) for t in self.adam.m) + (ptr(self.adam.clock),)  # (load_state_dict brings new moments and a new clock)
+        call = self._calls.get(key)
+        if call is None:
+            pol = self.policy
+            dims = (pol.in_dim, pol.h1, pol.h2)
+            rows, loss_rows, pol_rows, size = scratch_rows(n, minibatch, *dims)
+            s = self._scratch.get(rows)
+            if s is None or s["logits"].device != dev:
+                f32 = dict(dtype=torch.float32, device=dev)
+                s = dict(logits=torch.empty((max(rows, 1), 6), **f32), values=torch.empty((max(rows, 1),), **f32),
+                         grad_logits=torch.empty((max(rows, 1), 6), **f32), grad_values=torch.empty((max(rows, 1),), **f32),
+                         loss_partials=torch.empty((loss_rows, 4), dtype=torch.float64, device=dev),
+                         policy_partials=torch.empty((pol_rows, size), **f32), grads=[torch.empty(sh, **f32) for sh in shapes(*dims)])
+                self._scratch[rows] = s
+            K = (n + minibatch - 1) // minibatch
+            u = _lib.OcBcUpdate(ptr(features), S, ptr(index), n, minibatch, ptr(s["logits"]), ptr(s["values"]), ptr(s["grad_logits"]),
+                                ptr(s["grad_values"]), ptr(s["loss_partials"]), ptr(s["policy_partials"]),
+                                _lib.OcPolicyGrads(*[ptr(t) for t in s["grads"]]), None, None)
+            q = _lib.OcBcLoss(ptr(actions), ptr(weights), S, None, None, 0, 0, None, None, None, None, None)
+            if len(self._calls) >= 64:
+                self._calls.clear()
+            call = self._calls[key] = (_lib.OcActorCritic(*[ptr(p) for p in params], *dims), q, self.adam._struct(), u, K)
+        polc, q, ad, u, K = call
+        stats = torch.empty((K, 8), dtype=torch.float64, device=dev)
+        info = torch.empty((K, 4), dtype=torch.float64, device=dev)
+        u.d_stats, u.d_info = stats.data_ptr(), info.data_ptr()
+        ad.lr, ad.max_grad_norm = self.adam.lr, self.adam.max_grad_norm if self.adam.max_grad_norm is not None else 0.0
+        _call("oc_bc_update", dev, ctypes.byref(polc), ctypes.byref(q), ctypes.byref(ad), ctypes.byref(u))
+        return stats, info
+
+    def update(self, features, actions, index):
+        """One minibatch: the rows of `features` (any contiguous float32 [..., in_dim] tensor) and the elements of `actions` (a
+        contiguous uint8 tensor, one element per feature row) that index int32 [M] names.  (stats float64 [1, 8] — bc_loss's
+        BcStats.tensor —, info float64 [1, 4] — Adam's), on the device."""
+        rows = int(index.shape[0]) if isinstance(index, torch.Tensor) and index.dim() == 1 else 1  # (_run refuses what is no index)
+        return self._run(features, actions, index, max(rows, 1))
+
+    def epoch(self, features, actions, permutation, minibatch):
+        """One pass: the index int32 [n] cut into K = ceil(n / minibatch) minibatches, the last one shorter, each updated from the
+        weights the one before left — ONE C call.  (stats [K, 8], info [K, 4]) on the device."""
+        return self._run(features, actions, permutation, minibatch)
+
+    def evaluate(self, features, actions, index=None):
+        """The loss and accuracy of the samples index int32 [M] names (None: all of them) under the current weights: the forward
+        pass and the head without gradient stores.  BcStats on the device; no weight, moment or `.grad` is touched."""
+        params, dev = self.adam._device_params()
+        self._check_batch(features, actions, index, dev)
+        params, n_rows, first = self.policy._checked_call(features, index, 0)
+        with torch.no_grad():
+            logits, _ = _forward([p.detach() for p in params], (self.policy.in_dim, self.policy.h1, self.policy.h2), features, index, first, n_rows)
+        _, stats = _head(logits, actions, index, 0, self._device_weights(dev), False)
+        return _stats(stats)
