@@ -1470,6 +1470,50 @@ int oc_bc_update(const OcActorCritic* policy, const OcBcLoss* loss, const OcAdam
  */
 int oc_bc_update_plan(int64_t n_index, int64_t minibatch, int in_dim, int h1, int h2, int with_class_weights, char* out, size_t out_size);
 
+/*
+ * The behaviour-cloning update of small minibatches in ONE kernel (ABI 6: entry points added beside the others) — what oc_bc_update
+ * computes, for the shapes in which every stage of its chain is one workgroup, by k_bc_epoch_fused (csrc/bc_fused.hpp): ONE workgroup
+ * of 256 lanes that walks the minibatches of the index in order, each from the weights the one before left, with no intermediate
+ * array — logits, upstream gradients, partial sums and weight gradients stay in LDS and registers.
+ * Shapes served: minibatch 1..128; in_dim 56, 76 or 96; h1 and h2 in 1..64.  For these the parameters, the moments, the clock,
+ * d_stats and d_info after the call are oc_bc_update's BIT FOR BIT: the arithmetic and every order of summation are those stated for
+ * OcActorCritic, OcBcLoss and OcAdam above.  (A NaN norm in d_info is "a NaN" in both, its payload unspecified.)
+ * Its own argument block rather than OcBcUpdate with six members ignored: the call takes NO scratch, and a block without scratch
+ * members cannot be handed a stale or missing one.  Of `loss`, d_actions, d_class_weights and n_samples are read (an index entry names
+ * both the sample and its feature row); of `adam`, d_grad_scale and d_info are not read.
+ * Launches: the epoch is cut into launches of at most 64 minibatches (oc_bc_epoch_fused_plan states the number), chained on the
+ * caller's stream without synchronising.
+ */
+typedef struct OcBcEpochFused {
+    const float*   d_features;      /* [n_feature_rows][in_dim] f32, 16-byte aligned (OcPolicyRows') */
+    int64_t n_feature_rows;
+    const int32_t* d_index;         /* [n_index] i32, 4-byte aligned; required */
+    int64_t n_index;                /* >= 0, below 2^31 */
+    int64_t minibatch;              /* M in 1..128 */
+    double*        d_stats;         /* [K][8] f64 out: oc_bc_loss's d_stats of every minibatch; 8-byte aligned */
+    double*        d_info;          /* [K][4] f64 out: oc_adam_step's d_info of every minibatch; 8-byte aligned */
+} OcBcEpochFused;
+
+/*
+ * oc_bc_epoch_fused — K = ceil(n_index / M) minibatches, the last one shorter.  n_index == 0 launches nothing.  params' eight arrays
+ * and the moments are WRITTEN THROUGH, as by oc_adam_step.
+ * OC_EINVAL, before the FIRST launch of the call, with this entry point's name in front of the message: a NULL policy, loss, adam or
+ * epoch; n_index < 0 or >= 2^31; a minibatch outside 1..128 and an in_dim other than 56, 76 or 96 (the messages say what is served
+ * and that oc_bc_update serves the rest); h1 or h2 outside 1..64; a NULL d_index, d_stats or d_info; misaligned d_stats or d_info;
+ * oc_policy_forward's refusals of the weights, the feature rows and the index; a NULL d_actions, a misaligned d_class_weights,
+ * n_samples < 0 or >= 2^31; oc_adam_step's refusals of the moments, the clock and the hyperparameters.
+ */
+int oc_bc_epoch_fused(const OcActorCritic* policy, const OcBcLoss* loss, const OcAdam* adam, const OcBcEpochFused* epoch, void* stream);
+
+/*
+ * oc_bc_epoch_fused_plan — what oc_bc_epoch_fused would launch, as text:
+ *   "k_bc_epoch_fused<NF=3> grid=1, 256 lanes (4 wavefronts x one 32-row tile), 400 minibatch(es) of 64 rows (the last 64), at most 64 minibatches per launch: 7 launch(es), no host synchronisation, 32 x 32 x 2 f32 MFMA, 12 accumulator tiles per wavefront, 10823 elements (43 per lane) in Adam's phases, class_weights=no, 158016 B LDS; no scratch; out: stats 400 x 8 f64, info 400 x 4 f64"
+ *   "nothing to launch (no index); no scratch; out: stats 0 x 8 f64, info 0 x 4 f64"
+ * The checks that need no array apply; usable without a GPU, like the other plan calls; refusals carry oc_bc_epoch_fused's name.
+ *   out, out_size caller's text buffer (>= 1024 bytes holds every answer)
+ */
+int oc_bc_epoch_fused_plan(int64_t n_index, int64_t minibatch, int in_dim, int h1, int h2, int with_class_weights, char* out, size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

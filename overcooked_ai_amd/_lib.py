@@ -31,7 +31,7 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_sample_actions", "oc_multi_agent_step_sample", "oc_multi_agent_step_sample_plan",
            "oc_partner_logits", "oc_partner_logits_plan", "oc_gae", "oc_gae_plan", "oc_ppo_loss", "oc_ppo_loss_plan",
            "oc_policy_forward", "oc_policy_backward", "oc_policy_plan", "oc_adam_step", "oc_adam_plan", "oc_ppo_update", "oc_ppo_update_plan",
-           "oc_bc_loss", "oc_bc_loss_plan", "oc_bc_update", "oc_bc_update_plan")
+           "oc_bc_loss", "oc_bc_loss_plan", "oc_bc_update", "oc_bc_update_plan", "oc_bc_epoch_fused", "oc_bc_epoch_fused_plan")
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
 
 
@@ -136,6 +136,11 @@ class OcBcLoss(ctypes.Structure):
 
 class OcBcUpdate(ctypes.Structure):
     _fields_ = OcPpoUpdate._fields_  # (the same scratch and outputs: the head alone differs)
+
+
+class OcBcEpochFused(ctypes.Structure):
+    _fields_ = [("d_features", ctypes.c_void_p), ("n_feature_rows", ctypes.c_int64), ("d_index", ctypes.c_void_p), ("n_index", ctypes.c_int64),
+                ("minibatch", ctypes.c_int64), ("d_stats", ctypes.c_void_p), ("d_info", ctypes.c_void_p)]
 
 
 class OcAmdError(RuntimeError):
@@ -297,6 +302,10 @@ def load():
     L.oc_bc_update.argtypes = [acp, bcp, adp, ctypes.POINTER(OcBcUpdate), vp]
     L.oc_bc_update_plan.restype = i32
     L.oc_bc_update_plan.argtypes = [i64, i64, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.oc_bc_epoch_fused.restype = i32
+    L.oc_bc_epoch_fused.argtypes = [acp, bcp, adp, ctypes.POINTER(OcBcEpochFused), vp]
+    L.oc_bc_epoch_fused_plan.restype = i32
+    L.oc_bc_epoch_fused_plan.argtypes = [i64, i64, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

@@ -1,13 +1,14 @@
 """Behaviour cloning on the device: `bc_loss` (oc_bc_loss: sparse categorical cross-entropy from logits with optional class weights,
 its gradients and its accuracy in one launch) and `BCLearner` (oc_bc_update: forward, loss, backward and optimiser step of a run of
-minibatches in ONE C call) — the reference's BC objective (human_aware_rl/imitation/behavior_cloning_tf2.py) on the partner's network.
+minibatches in ONE C call; with fused=True oc_bc_epoch_fused: the same run in ONE kernel of one workgroup, for minibatches of at most
+128 rows, bit for bit the same result) — the reference's BC objective (human_aware_rl/imitation/behavior_cloning_tf2.py) on the partner's network.
 
     feats, actions = ...                                          # rollout_featurize's feats_out[:-1] with actions[1:], or human data
     policy = ActorCritic(env.feature_length).to(device)
     learner = BCLearner(policy, lr=1e-3, class_weights=None)
     for _ in range(epochs):
         perm = torch.randperm(n_train, device=device, dtype=torch.int32)
-        stats, info = learner.epoch(feats, actions, perm, 64)     # [K, 8] and [K, 4] on the device
+        stats, info = learner.epoch(feats, actions, perm, 64)     # [K, 8] and [K, 4] on the device; fused=True: one kernel
     held_out = learner.evaluate(feats, actions, validation_index) # BcStats: .loss, .accuracy
     env = VecOvercookedMultiAgent(..., bc_policy=policy.dense_policy())
 
@@ -51,6 +52,18 @@ def plan_bc_update(n_index, minibatch, in_dim=96, h1=64, h2=64, class_weights=Fa
     out = ctypes.create_string_buffer(2048)
     rc = _lib.load().oc_bc_update_plan(int(n_index), int(minibatch), int(in_dim), int(h1), int(h2), int(bool(class_weights)), out, len(out))
     _lib.check(rc, "oc_bc_update_plan")
+    return out.value.decode()
+
+
+def plan_bc_epoch_fused(n_index, minibatch, in_dim=96, h1=64, h2=64, class_weights=False):
+    """What BCLearner.epoch(..., fused=True) launches, in oc_bc_epoch_fused_plan's words: the kernel instance, the minibatches, the
+    launches and the LDS (no device needed).  ValueError with the library's message for a shape the fused kernel does not serve (a
+    minibatch above 128 rows, an in_dim other than 56, 76 or 96)."""
+    out = ctypes.create_string_buffer(1024)
+    L = _lib.load()
+    rc = L.oc_bc_epoch_fused_plan(int(n_index), int(minibatch), int(in_dim), int(h1), int(h2), int(bool(class_weights)), out, len(out))
+    if rc != 0:
+        raise ValueError(L.oc_last_error().decode(errors="replace"))
     return out.value.decode()
 
 
@@ -208,18 +221,23 @@ class BCLearner:
                 raise ValueError("an index names samples and feature rows below 2^31")
         return S
 
-    def _run(self, features, actions, index, minibatch):
+    def _run(self, features, actions, index, minibatch, fused=False):
+        minibatch = int(minibatch)
+        if fused and minibatch >= 1:  # the shapes oc_bc_epoch_fused serves, in the library's words, ahead of everything that needs a device
+            rows = int(index.shape[0]) if isinstance(index, torch.Tensor) and index.dim() == 1 else 0
+            plan_bc_epoch_fused(rows, minibatch, self.policy.in_dim, self.policy.h1, self.policy.h2)
         params, dev = self.adam._device_params()
         if index is None:
             raise ValueError("index must be a contiguous int32 [n] tensor")
         S = self._check_batch(features, actions, index, dev)
         n = int(index.shape[0])
-        minibatch = int(minibatch)
         if minibatch < 1:
             raise ValueError("minibatch must be at least 1, not %d" % minibatch)
         self.adam._state(dev)
         weights = self._device_weights(dev)
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        if fused:
+            return self._run_fused(features, actions, index, minibatch, params, dev, S, n, weights)
         key = (n, minibatch, ptr(features), S, ptr(index), ptr(actions), ptr(weights)) + tuple(ptr(p) for p in params) \
             + tuple(ptr(t) for t in self.adam.m) + (ptr(self.adam.clock),)  # (load_state_dict brings new moments and a new clock)
         call = self._calls.get(key)
@@ -251,17 +269,48 @@ class BCLearner:
         _call("oc_bc_update", dev, ctypes.byref(polc), ctypes.byref(q), ctypes.byref(ad), ctypes.byref(u))
         return stats, info
 
-    def update(self, features, actions, index):
+    def _run_fused(self, features, actions, index, minibatch, params, dev, S, n, weights):
+        """oc_bc_epoch_fused on checked tensors: no scratch (self._scratch is not touched), the optimiser's moments and clock"""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        pol = self.policy
+        K = (n + minibatch - 1) // minibatch
+        stats = torch.empty((K, 8), dtype=torch.float64, device=dev)
+        info = torch.empty((K, 4), dtype=torch.float64, device=dev)
+        key = ("fused", n, minibatch, ptr(features), S, ptr(index), ptr(actions), ptr(weights)) + tuple(ptr(p) for p in params) \
+            + tuple(ptr(t) for t in self.adam.m) + (ptr(self.adam.clock),)
+        call = self._calls.get(key)
+        if call is None:
+            if len(self._calls) >= 64:
+                self._calls.clear()
+            call = self._calls[key] = (_lib.OcActorCritic(*[ptr(p) for p in params], pol.in_dim, pol.h1, pol.h2),
+                                       _lib.OcBcLoss(ptr(actions), ptr(weights), S, None, None, 0, 0, None, None, None, None, None),
+                                       _lib.OcBcEpochFused(ptr(features), S, ptr(index), n, minibatch, None, None), self.adam._struct())
+        polc, q, e, ad = call
+        e.d_stats, e.d_info = stats.data_ptr(), info.data_ptr()
+        ad.lr, ad.max_grad_norm = self.adam.lr, self.adam.max_grad_norm if self.adam.max_grad_norm is not None else 0.0
+        L = _lib.load()
+        with torch.cuda.device(dev):
+            rc = L.oc_bc_epoch_fused(ctypes.byref(polc), ctypes.byref(q), ctypes.byref(ad), ctypes.byref(e), _stream(dev))
+        if rc == -1:  # (OC_EINVAL: a shape or an array the library does not serve)
+            raise ValueError(L.oc_last_error().decode(errors="replace"))
+        _lib.check(rc, "oc_bc_epoch_fused")
+        return stats, info
+
+    def update(self, features, actions, index, fused=False):
         """One minibatch: the rows of `features` (any contiguous float32 [..., in_dim] tensor) and the elements of `actions` (a
         contiguous uint8 tensor, one element per feature row) that index int32 [M] names.  (stats float64 [1, 8] — bc_loss's
-        BcStats.tensor —, info float64 [1, 4] — Adam's), on the device."""
+        BcStats.tensor —, info float64 [1, 4] — Adam's), on the device.  fused: see epoch()."""
         rows = int(index.shape[0]) if isinstance(index, torch.Tensor) and index.dim() == 1 else 1  # (_run refuses what is no index)
-        return self._run(features, actions, index, max(rows, 1))
+        return self._run(features, actions, index, max(rows, 1), fused)
 
-    def epoch(self, features, actions, permutation, minibatch):
+    def epoch(self, features, actions, permutation, minibatch, fused=False):
         """One pass: the index int32 [n] cut into K = ceil(n / minibatch) minibatches, the last one shorter, each updated from the
-        weights the one before left — ONE C call.  (stats [K, 8], info [K, 4]) on the device."""
-        return self._run(features, actions, permutation, minibatch)
+        weights the one before left — ONE C call.  (stats [K, 8], info [K, 4]) on the device.
+        fused=True: the pass runs in ONE kernel of one workgroup (oc_bc_epoch_fused) instead of six launches per minibatch; the
+        results are the same bit for bit, no scratch is used, and the optimiser's state is shared, so fused and staged calls may
+        alternate.  It serves minibatches of 1..128 rows and in_dim 56, 76 or 96 and raises ValueError, with the library's message,
+        for anything else."""
+        return self._run(features, actions, permutation, minibatch, fused)
 
     def evaluate(self, features, actions, index=None):
         """The loss and accuracy of the samples index int32 [M] names (None: all of them) under the current weights: the forward

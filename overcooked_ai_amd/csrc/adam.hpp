@@ -47,6 +47,39 @@ __device__ __forceinline__ void adam_arrays(F f) {
     }
 }
 
+// what every lane derives from the norm, the clock's beta powers and the hyperparameters: the clip factor and the scalars of a step taken
+struct AdamStep {
+    bool clip;
+    float c, step_size, rbc2s, omb1, omb2, beta2, eps;
+    double p1n, p2n;
+};
+__device__ __forceinline__ AdamStep adam_step_of(float norm, double p1, double p2, float lr, float beta1, float beta2, float eps, float max_grad_norm) {
+#pragma clang fp contract(off)
+    AdamStep st;
+    st.clip = max_grad_norm > 0.f && max_grad_norm < __builtin_inff();
+    st.c = 1.f;
+    if (st.clip) {
+        const float q = max_grad_norm / (norm + 1e-6f);
+        st.c = q < 1.f ? q : 1.f;
+    }
+    st.p1n = p1 * (double)beta1, st.p2n = p2 * (double)beta2;
+    const double bc1 = 1.0 - st.p1n, bc2s = sqrt(1.0 - st.p2n);
+    st.step_size = (float)((double)lr / bc1), st.rbc2s = (float)bc2s;
+    st.omb1 = 1.f - beta1, st.omb2 = 1.f - beta2;
+    st.beta2 = beta2, st.eps = eps;
+    return st;
+}
+
+// the header's update of one element from its scaled gradient g
+__device__ __forceinline__ void adam_element(float g, float m, float v, float p, const AdamStep& st, float& mn, float& vn, float& pn) {
+#pragma clang fp contract(off)
+    if (st.clip) g = g * st.c;
+    mn = m + (g - m) * st.omb1;
+    vn = v * st.beta2 + (g * g) * st.omb2;
+    const float den = sqrtf(vn) / st.rbc2s + st.eps;
+    pn = p - st.step_size * (mn / den);
+}
+
 __global__ __launch_bounds__(ADAM_LANES) void k_adam_step(AdamArgs a) {
 #pragma clang fp contract(off)
     __shared__ float sg[ADAM_MAX];
@@ -88,12 +121,8 @@ __global__ __launch_bounds__(ADAM_LANES) void k_adam_step(AdamArgs a) {
     // ---- what every lane derives from the norm and the clock (uniform)
     const bool finite = norm - norm == 0.f;  // neither NaN nor an infinity
     const bool skip = !finite || (scaled && gs64 == 0.0);
-    const bool clip = a.max_grad_norm > 0.f && a.max_grad_norm < __builtin_inff();
-    float c = 1.f;
-    if (clip) {
-        const float q = a.max_grad_norm / (norm + 1e-6f);
-        c = q < 1.f ? q : 1.f;
-    }
+    const AdamStep st = adam_step_of(norm, p1, p2, a.lr, a.beta1, a.beta2, a.eps, a.max_grad_norm);
+    const float c = st.c;
     if (skip) {  // nothing is written to parameters or moments; steps and the powers stay
         if (tid == 0) {
             a.clock[3] = skipped + 1.0;
@@ -101,11 +130,7 @@ __global__ __launch_bounds__(ADAM_LANES) void k_adam_step(AdamArgs a) {
         }
         return;
     }
-    const double p1n = p1 * (double)a.beta1, p2n = p2 * (double)a.beta2;
-    const double bc1 = 1.0 - p1n, bc2s = sqrt(1.0 - p2n);
-    const float step_size = (float)((double)a.lr / bc1), rbc2s = (float)bc2s;
-    const float omb1 = 1.f - a.beta1, omb2 = 1.f - a.beta2;
-    const float beta2 = a.beta2, eps = a.eps;
+    const double p1n = st.p1n, p2n = st.p2n;
 
     // ---- pass 2: the update
     adam_arrays([&](auto K) {
@@ -128,12 +153,8 @@ __global__ __launch_bounds__(ADAM_LANES) void k_adam_step(AdamArgs a) {
             for (int j = 0; j < ADAM_B2; ++j) {
                 const int at = off + j * ADAM_LANES;
                 if (at < len) {
-                    float g = sg[s + at];
-                    if (clip) g = g * c;
-                    const float mn = mi[j] + (g - mi[j]) * omb1;
-                    const float vn = vi[j] * beta2 + (g * g) * omb2;
-                    const float den = sqrtf(vn) / rbc2s + eps;
-                    const float pn = pi[j] - step_size * (mn / den);
+                    float mn, vn, pn;
+                    adam_element(sg[s + at], mi[j], vi[j], pi[j], st, mn, vn, pn);
                     M[at] = mn;
                     V[at] = vn;
                     P[at] = pn;
@@ -154,6 +175,29 @@ const char* const ADAM_WHO = "oc_adam_step";
 // the checks of the shape alone (oc_adam_plan makes these)
 int adam_check_shape(const char* who, int in_dim, int h1, int h2) { return pol_check_shape(who, 0, in_dim, h1, h2); }
 
+// the moments and the clock
+int adam_check_arrays(const char* who, const OcAdam* ad) {
+    uintptr_t bits = 0;
+    for (int k = 0; k < 8; ++k) {
+        if (!ad->d_m[k] || !ad->d_v[k]) return pol_refuse(who, "NULL moment array");
+        bits |= (uintptr_t)ad->d_m[k] | (uintptr_t)ad->d_v[k];
+    }
+    if (bits & 3u) return pol_refuse(who, "moment arrays must be 4-byte aligned");
+    if (!ad->d_clock) return pol_refuse(who, "adam.d_clock is NULL");
+    if (((uintptr_t)ad->d_clock | (uintptr_t)ad->d_grad_scale | (uintptr_t)ad->d_info) & 7u)
+        return pol_refuse(who, "adam.d_clock, adam.d_grad_scale and adam.d_info must be 8-byte aligned");
+    return OC_OK;
+}
+
+// the hyperparameters
+int adam_check_hyper(const char* who, const OcAdam* ad) {
+    if (!(ad->lr >= 0.f) || !(ad->lr < __builtin_inff())) return pol_refuse(who, "adam.lr must be finite and >= 0");
+    if (!(ad->beta1 >= 0.f && ad->beta1 < 1.f) || !(ad->beta2 >= 0.f && ad->beta2 < 1.f)) return pol_refuse(who, "adam.beta1 and adam.beta2 must be in [0, 1)");
+    if (!(ad->eps > 0.f)) return pol_refuse(who, "adam.eps must be positive");
+    if (ad->max_grad_norm != ad->max_grad_norm) return pol_refuse(who, "adam.max_grad_norm is NaN");
+    return OC_OK;
+}
+
 // every refusal of oc_adam_step; no device call
 int adam_check(const char* who, const OcActorCritic* pol, const OcPolicyGrads* grads, const OcAdam* ad) {
     if (!pol) return pol_refuse(who, "params is NULL");
@@ -169,21 +213,15 @@ int adam_check(const char* who, const OcActorCritic* pol, const OcPolicyGrads* g
     if (((uintptr_t)grads->d_w1 | (uintptr_t)grads->d_b1 | (uintptr_t)grads->d_w2 | (uintptr_t)grads->d_b2 | (uintptr_t)grads->d_wp |
          (uintptr_t)grads->d_bp | (uintptr_t)grads->d_wv | (uintptr_t)grads->d_bv) & 3u)
         return pol_refuse(who, "gradient arrays must be 4-byte aligned");
-    uintptr_t bits = 0;
-    for (int k = 0; k < 8; ++k) {
-        if (!ad->d_m[k] || !ad->d_v[k]) return pol_refuse(who, "NULL moment array");
-        bits |= (uintptr_t)ad->d_m[k] | (uintptr_t)ad->d_v[k];
-    }
-    if (bits & 3u) return pol_refuse(who, "moment arrays must be 4-byte aligned");
-    if (!ad->d_clock) return pol_refuse(who, "adam.d_clock is NULL");
-    if (((uintptr_t)ad->d_clock | (uintptr_t)ad->d_grad_scale | (uintptr_t)ad->d_info) & 7u)
-        return pol_refuse(who, "adam.d_clock, adam.d_grad_scale and adam.d_info must be 8-byte aligned");
+    if (int rc = adam_check_arrays(who, ad)) return rc;
     if (int rc = adam_check_shape(who, pol->in_dim, pol->h1, pol->h2)) return rc;
-    if (!(ad->lr >= 0.f) || !(ad->lr < __builtin_inff())) return pol_refuse(who, "adam.lr must be finite and >= 0");
-    if (!(ad->beta1 >= 0.f && ad->beta1 < 1.f) || !(ad->beta2 >= 0.f && ad->beta2 < 1.f)) return pol_refuse(who, "adam.beta1 and adam.beta2 must be in [0, 1)");
-    if (!(ad->eps > 0.f)) return pol_refuse(who, "adam.eps must be positive");
-    if (ad->max_grad_norm != ad->max_grad_norm) return pol_refuse(who, "adam.max_grad_norm is NaN");
-    return OC_OK;
+    return adam_check_hyper(who, ad);
+}
+
+// the optimiser's own arrays and numbers, for a caller that has checked the weights and the shape itself (bc_fused.hpp)
+int adam_check_state(const char* who, const OcAdam* ad) {
+    if (int rc = adam_check_arrays(who, ad)) return rc;
+    return adam_check_hyper(who, ad);
 }
 
 // the launch of a call that adam_check has passed

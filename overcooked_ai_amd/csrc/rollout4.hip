@@ -177,4 +177,5 @@ template void describe_rollout<OC_R4_PART>(const Rollout4Call& c, char* out, siz
 #include "ppo_update.hpp"  // oc_ppo_update, oc_ppo_update_plan (host code: the launches of the four files above, minibatch after minibatch)
 #include "bc_loss.hpp"     // k_bc_loss, k_bc_loss_stats, oc_bc_loss, oc_bc_loss_plan
 #include "bc_update.hpp"   // oc_bc_update, oc_bc_update_plan (host code: ppo_update.hpp's chain with the cross-entropy head)
+#include "bc_fused.hpp"    // k_bc_epoch_fused, oc_bc_epoch_fused, oc_bc_epoch_fused_plan (that chain for minibatches of one workgroup, in one kernel)
 #endif
