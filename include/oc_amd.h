@@ -1312,7 +1312,7 @@ int oc_adam_plan(int in_dim, int h1, int h2, char* out, size_t out_size);
  *                      the sample and its feature row) -> d_grad_logits, d_grad_values, d_loss_partials, d_stats[k]
  *   oc_policy_backward on those RAW gradients (not divided by the count) -> grads, through d_policy_partials
  *   oc_adam_step       with d_grad_scale = &d_stats[k][7] (1 / count; 0: the step is skipped) and d_info[k]
- * (csrc/ppo_update.hpp: host code; the existing launch code, no kernel of its own).  The results are bit for bit those of the four
+ * (csrc/update_chain.hpp: host code; the existing launch code, no kernel of its own).  The results are bit for bit those of the four
  * calls made one by one.  The scratch is one minibatch's and is reused from minibatch to minibatch: the stream orders them.
  * Of `loss`, d_logits, d_values, d_index, first_sample, n_minibatch, d_grad_logits, d_grad_values, d_partials, d_stats and d_terms_out
  * are not read; of `adam`, d_grad_scale and d_info are not.
@@ -1429,7 +1429,7 @@ int oc_bc_loss_plan(int64_t n_minibatch, int with_index, int with_class_weights,
  *                      sample and its feature row) -> d_grad_logits, d_grad_values (zeros), d_loss_partials, d_stats[k]
  *   oc_policy_backward on those RAW gradients (not divided by the count) -> grads, through d_policy_partials
  *   oc_adam_step       with d_grad_scale = &d_stats[k][7] (1 / count; 0: the step is skipped) and d_info[k]
- * (csrc/bc_update.hpp: host code; the existing launch code, no kernel of its own).  The results are bit for bit those of the four
+ * (csrc/update_chain.hpp: host code; the existing launch code, no kernel of its own).  The results are bit for bit those of the four
  * calls made one by one.  The scratch is one minibatch's and is reused from minibatch to minibatch: the stream orders them.
  * Of `loss`, d_logits, d_index, first_sample, n_minibatch, d_grad_logits, d_grad_values, d_loss_out, d_partials and d_stats are not
  * read; of `adam`, d_grad_scale and d_info are not.

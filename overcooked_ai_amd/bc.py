@@ -28,8 +28,8 @@ import torch
 
 from . import _lib
 from .gae import _checked, _stream
-from .learner import Adam
-from .policy import ActorCritic, _forward, shapes
+from .learner import _ChainLearner, _ptr, _scratch_rows
+from .policy import ActorCritic, _forward
 
 BcStats = collections.namedtuple("BcStats", "tensor count loss accuracy mean_weight inv_count")
 N_ACTIONS = 6
@@ -78,9 +78,7 @@ def partial_samples():
 def scratch_rows(n_index, minibatch, in_dim, h1, h2):
     """(rows of a minibatch, rows of the loss partials, rows of the policy partials, floats of a policy partial), read from the
     plan's words."""
-    text = plan_bc_update(n_index, minibatch, in_dim, h1, h2)
-    m = re.search(r"scratch: logits (\d+) x 6 f32.*loss partials (\d+) x 4 f64, policy partials (\d+) x (\d+) f32", text)
-    return tuple(int(x) for x in m.groups())
+    return _scratch_rows(plan_bc_update(n_index, minibatch, in_dim, h1, h2), 4)
 
 
 def _weights(class_weights):
@@ -174,27 +172,21 @@ def bc_loss(logits, actions, index=None, first=0, class_weights=None):
     return loss, _stats(box[0])
 
 
-class BCLearner:
+class BCLearner(_ChainLearner):
     """The whole update of a behaviour-cloning minibatch — policy forward, weighted cross-entropy, backward to the weights, clipped
     Adam step — as stream-ordered kernels behind ONE C call (oc_bc_update), for one minibatch (`update`) or a whole pass over a
     permutation (`epoch`), and `evaluate`, the loss and accuracy of held-out samples.  The optimiser's hyperparameters are Adam's
     (`self.adam`, whose state_dict holds the moments).  The value head gets zero gradients.  No autograd: the parameters' `.grad`s are
     not touched."""
 
+    _plan, _WIDTH, _UPDATE, _ENTRY = staticmethod(plan_bc_update), 4, _lib.OcBcUpdate, "oc_bc_update"
+
     def __init__(self, policy, lr=1e-3, class_weights=None, max_grad_norm=None, betas=(0.9, 0.999), eps=1e-8):
         if not isinstance(policy, ActorCritic):
             raise ValueError("BCLearner: policy must be an ActorCritic")
-        self.adam = Adam(policy, lr, betas, eps, max_grad_norm)
-        self.policy = policy
+        super().__init__(policy, lr, betas, eps, max_grad_norm)
         self.class_weights = _weights(class_weights)
         self._weights_on = None  # the class weights on the parameters' device
-        self._scratch = {}       # (rows of a minibatch) -> the tensors of one minibatch
-        self._calls = {}         # the addresses and sizes of a call -> its ctypes structs
-
-    def scratch(self, rows):
-        """The scratch of minibatches of up to `rows` rows, as a dict of tensors: logits, values, grad_logits, grad_values, the loss
-        and policy partials and `grads`, the eight RAW gradient arrays (a sum over the minibatch, not divided by its count)."""
-        return self._scratch[rows]
 
     def _device_weights(self, dev):
         if self.class_weights is None:
@@ -205,18 +197,12 @@ class BCLearner:
 
     def _check_batch(self, features, actions, index, dev):
         pol = self.policy
-        if not isinstance(features, torch.Tensor) or features.dim() < 2 or features.shape[-1] != pol.in_dim or features.dtype != torch.float32 \
-                or not features.is_contiguous() or features.device != dev:
-            raise ValueError("features must be a contiguous float32 [..., %d] tensor on %s" % (pol.in_dim, dev))
-        if features.data_ptr() % 16:
-            raise ValueError("features must be 16-byte aligned")
+        self._check_features(features, dev)
         S = _checked_actions(actions, dev)
         if S != features.numel() // pol.in_dim:
             raise ValueError("actions must have one element per feature row: %d, not %d" % (features.numel() // pol.in_dim, S))
         if index is not None:
-            if not isinstance(index, torch.Tensor) or index.dim() != 1:
-                raise ValueError("index must be a contiguous int32 [n] tensor")
-            _checked("index", index, torch.int32, (int(index.shape[0]),), dev, torch)
+            self._check_index(index, dev)
             if S >= 2 ** 31:
                 raise ValueError("an index names samples and feature rows below 2^31")
         return S
@@ -230,64 +216,20 @@ class BCLearner:
         if index is None:
             raise ValueError("index must be a contiguous int32 [n] tensor")
         S = self._check_batch(features, actions, index, dev)
-        n = int(index.shape[0])
-        if minibatch < 1:
-            raise ValueError("minibatch must be at least 1, not %d" % minibatch)
+        self._check_minibatch(minibatch)
         self.adam._state(dev)
         weights = self._device_weights(dev)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        key = (int(index.shape[0]), minibatch, _ptr(features), S, _ptr(index), _ptr(actions), _ptr(weights))
+        loss = lambda: _lib.OcBcLoss(_ptr(actions), _ptr(weights), S, None, None, 0, 0, None, None, None, None, None)  # noqa: E731
         if fused:
-            return self._run_fused(features, actions, index, minibatch, params, dev, S, n, weights)
-        key = (n, minibatch, ptr(features), S, ptr(index), ptr(actions), ptr(weights)) + tuple(ptr(p) for p in params) \
-            + tuple(ptr(t) for t in self.adam.m) + (ptr(self.adam.clock),)  # (load_state_dict brings new moments and a new clock)
-        call = self._calls.get(key)
-        if call is None:
-            pol = self.policy
-            dims = (pol.in_dim, pol.h1, pol.h2)
-            rows, loss_rows, pol_rows, size = scratch_rows(n, minibatch, *dims)
-            s = self._scratch.get(rows)
-            if s is None or s["logits"].device != dev:
-                f32 = dict(dtype=torch.float32, device=dev)
-                s = dict(logits=torch.empty((max(rows, 1), 6), **f32), values=torch.empty((max(rows, 1),), **f32),
-                         grad_logits=torch.empty((max(rows, 1), 6), **f32), grad_values=torch.empty((max(rows, 1),), **f32),
-                         loss_partials=torch.empty((loss_rows, 4), dtype=torch.float64, device=dev),
-                         policy_partials=torch.empty((pol_rows, size), **f32), grads=[torch.empty(sh, **f32) for sh in shapes(*dims)])
-                self._scratch[rows] = s
-            K = (n + minibatch - 1) // minibatch
-            u = _lib.OcBcUpdate(ptr(features), S, ptr(index), n, minibatch, ptr(s["logits"]), ptr(s["values"]), ptr(s["grad_logits"]),
-                                ptr(s["grad_values"]), ptr(s["loss_partials"]), ptr(s["policy_partials"]),
-                                _lib.OcPolicyGrads(*[ptr(t) for t in s["grads"]]), None, None)
-            q = _lib.OcBcLoss(ptr(actions), ptr(weights), S, None, None, 0, 0, None, None, None, None, None)
-            if len(self._calls) >= 64:
-                self._calls.clear()
-            call = self._calls[key] = (_lib.OcActorCritic(*[ptr(p) for p in params], *dims), q, self.adam._struct(), u, K)
-        polc, q, ad, u, K = call
-        stats = torch.empty((K, 8), dtype=torch.float64, device=dev)
-        info = torch.empty((K, 4), dtype=torch.float64, device=dev)
-        u.d_stats, u.d_info = stats.data_ptr(), info.data_ptr()
-        ad.lr, ad.max_grad_norm = self.adam.lr, self.adam.max_grad_norm if self.adam.max_grad_norm is not None else 0.0
-        _call("oc_bc_update", dev, ctypes.byref(polc), ctypes.byref(q), ctypes.byref(ad), ctypes.byref(u))
-        return stats, info
+            return self._run_fused(key, loss, features, index, minibatch, params, dev, S)
+        return self._chain(key, loss, features, S, index, minibatch, params, dev)
 
-    def _run_fused(self, features, actions, index, minibatch, params, dev, S, n, weights):
+    def _run_fused(self, key, loss, features, index, minibatch, params, dev, S):
         """oc_bc_epoch_fused on checked tensors: no scratch (self._scratch is not touched), the optimiser's moments and clock"""
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        pol = self.policy
-        K = (n + minibatch - 1) // minibatch
-        stats = torch.empty((K, 8), dtype=torch.float64, device=dev)
-        info = torch.empty((K, 4), dtype=torch.float64, device=dev)
-        key = ("fused", n, minibatch, ptr(features), S, ptr(index), ptr(actions), ptr(weights)) + tuple(ptr(p) for p in params) \
-            + tuple(ptr(t) for t in self.adam.m) + (ptr(self.adam.clock),)
-        call = self._calls.get(key)
-        if call is None:
-            if len(self._calls) >= 64:
-                self._calls.clear()
-            call = self._calls[key] = (_lib.OcActorCritic(*[ptr(p) for p in params], pol.in_dim, pol.h1, pol.h2),
-                                       _lib.OcBcLoss(ptr(actions), ptr(weights), S, None, None, 0, 0, None, None, None, None, None),
-                                       _lib.OcBcEpochFused(ptr(features), S, ptr(index), n, minibatch, None, None), self.adam._struct())
-        polc, q, e, ad = call
-        e.d_stats, e.d_info = stats.data_ptr(), info.data_ptr()
-        ad.lr, ad.max_grad_norm = self.adam.lr, self.adam.max_grad_norm if self.adam.max_grad_norm is not None else 0.0
+        n = int(index.shape[0])
+        polc, q, ad, e = self._cached(("fused",) + key, params, loss, lambda: _lib.OcBcEpochFused(_ptr(features), S, _ptr(index), n, minibatch, None, None))
+        stats, info = self._outputs(n, minibatch, dev, e, ad)
         L = _lib.load()
         with torch.cuda.device(dev):
             rc = L.oc_bc_epoch_fused(ctypes.byref(polc), ctypes.byref(q), ctypes.byref(ad), ctypes.byref(e), _stream(dev))

@@ -1,6 +1,6 @@
 // bc_fused.hpp — a run of behaviour-cloning minibatches of at most 128 rows in ONE kernel of ONE workgroup: k_bc_epoch_fused,
 // oc_bc_epoch_fused, oc_bc_epoch_fused_plan (include/oc_amd.h: OcBcEpochFused)
-// Part of liboc_amd.so: included at file scope by rollout4.hip in its OC_R4_PART == 2 unit, behind bc_update.hpp.  It computes what
+// Part of liboc_amd.so: included at file scope by rollout4.hip in its OC_R4_PART == 2 unit, behind update_chain.hpp.  It computes what
 // oc_bc_update computes, bit for bit, for the shapes in which every stage of that chain is itself one workgroup — a minibatch of at
 // most BCF_ROWS = 128 rows (pol_grid returns 1, k_policy_grad_sum is the identity over one partial, k_bc_loss writes one partial) and
 // in_dim 56, 76 or 96 (two or three feature tiles: the instances NF = 2 and NF = 3) — without the six dependent launches of a minibatch
@@ -575,8 +575,7 @@ const char* const BCF_WHO = "oc_bc_epoch_fused";
 // the checks that need no array (oc_bc_epoch_fused_plan makes these alone)
 int bcf_check_shape(int64_t n_index, int64_t minibatch, int in_dim, int h1, int h2) {
     const char* const who = BCF_WHO;
-    if (n_index < 0) return pol_refuse(who, "n_index < 0");
-    if (n_index >= ((int64_t)1 << 31)) return pol_refuse(who, "n_index must be below 2^31");
+    if (int rc = upd_check_index(who, n_index)) return rc;  // (update_chain.hpp)
     if (minibatch < 1 || minibatch > BCF_ROWS)
         return pol_refuse(who, "minibatch must be in 1..128: a 32-row tile for each of the workgroup's four wavefronts (oc_bc_update serves every size)");
     if (in_dim != 56 && in_dim != 76 && in_dim != 96)
@@ -661,7 +660,7 @@ int oc_bc_epoch_fused_plan(int64_t n_index, int64_t minibatch, int in_dim, int h
     if (!out || out_size == 0) return fail(OC_EINVAL, "oc_bc_epoch_fused_plan: no output buffer");
     out[0] = 0;
     if (int rc = bcf_check_shape(n_index, minibatch, in_dim, h1, h2)) return rc;
-    const int64_t K = upd_count(n_index, minibatch), m = n_index < minibatch ? n_index : minibatch, last = n_index - (K - 1) * minibatch;
+    const auto [K, m, last] = upd_split(n_index, minibatch);  // (update_chain.hpp)
     if (K == 0) {
         snprintf(out, out_size, "nothing to launch (no index); no scratch; out: stats 0 x 8 f64, info 0 x 4 f64");
         return OC_OK;

@@ -1,7 +1,7 @@
 // bc_loss.hpp — the behaviour-cloning loss of a minibatch, sparse categorical cross-entropy from logits with optional class weights,
 // its gradients with respect to the policy's logits and its accuracy: k_bc_loss, k_bc_loss_stats, oc_bc_loss, oc_bc_loss_plan
 // (include/oc_amd.h: OcBcLoss)
-// Part of liboc_amd.so: included at file scope by rollout4.hip in its OC_R4_PART == 2 unit, behind ppo_update.hpp.  Of ppo_loss.hpp
+// Part of liboc_amd.so: included at file scope by rollout4.hip in its OC_R4_PART == 2 unit, behind adam.hpp.  Of ppo_loss.hpp
 // it calls ppo_softmax (the header's softmax of a row), PPO_TILES / PPO_P (the shape of a workgroup's walk), ppo_refuse_as and
 // ppo_check_shape; no kernel or entry point there knows of this file.
 //

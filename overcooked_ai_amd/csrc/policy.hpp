@@ -580,7 +580,7 @@ const char* const POL_BACKWARD_WHO = "oc_policy_backward";
 const char* const POL_PLAN_WHO = "oc_policy_plan";
 
 // ---- the two entry points in two halves each: every refusal (no device call), then the launches of a call that passed — so that a
-// caller of several stages (ppo_update.hpp) can make all its refusals before its first launch
+// caller of several stages (update_chain.hpp) can make all its refusals before its first launch
 int pol_check_forward(const char* who, const OcActorCritic* pol, const OcPolicyRows* rows, const float* d_logits, const float* d_values) {
     if (int rc = pol_check(who, pol, rows)) return rc;
     if (!d_logits || !d_values) return pol_refuse(who, "NULL d_logits or d_values");

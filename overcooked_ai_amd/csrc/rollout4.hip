@@ -5,8 +5,8 @@
 // (launch_rollout) or, for oc_rollout_plan, names it and its LDS bytes (describe_rollout).
 // The OC_R4_PART == 2 unit, the shortest of the four, also compiles partner.hpp (k_partner_logits and its two entry points) and
 // gae.hpp (k_gae, k_gae_moments and theirs), ppo_loss.hpp (k_ppo_loss, k_ppo_loss_stats and theirs) and policy.hpp (k_policy_forward,
-// k_policy_backward, k_policy_grad_sum and theirs), adam.hpp (k_adam_step and its two), ppo_update.hpp (host code only), bc_loss.hpp
-// (k_bc_loss, k_bc_loss_stats and theirs) and bc_update.hpp (host code only).
+// k_policy_backward, k_policy_grad_sum and theirs), adam.hpp (k_adam_step and its two), bc_loss.hpp (k_bc_loss, k_bc_loss_stats and theirs),
+// update_chain.hpp (host code only: oc_ppo_update and oc_bc_update) and bc_fused.hpp (k_bc_epoch_fused and its two).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -174,8 +174,7 @@ template void describe_rollout<OC_R4_PART>(const Rollout4Call& c, char* out, siz
 #include "ppo_loss.hpp" // k_ppo_loss, k_ppo_loss_stats, oc_ppo_loss, oc_ppo_loss_plan
 #include "policy.hpp"   // k_policy_forward, k_policy_backward, k_policy_grad_sum, oc_policy_forward, oc_policy_backward, oc_policy_plan
 #include "adam.hpp"     // k_adam_step, oc_adam_step, oc_adam_plan
-#include "ppo_update.hpp"  // oc_ppo_update, oc_ppo_update_plan (host code: the launches of the four files above, minibatch after minibatch)
-#include "bc_loss.hpp"     // k_bc_loss, k_bc_loss_stats, oc_bc_loss, oc_bc_loss_plan
-#include "bc_update.hpp"   // oc_bc_update, oc_bc_update_plan (host code: ppo_update.hpp's chain with the cross-entropy head)
-#include "bc_fused.hpp"    // k_bc_epoch_fused, oc_bc_epoch_fused, oc_bc_epoch_fused_plan (that chain for minibatches of one workgroup, in one kernel)
+#include "bc_loss.hpp"  // k_bc_loss, k_bc_loss_stats, oc_bc_loss, oc_bc_loss_plan
+#include "update_chain.hpp"  // oc_ppo_update, oc_bc_update and their plans (host code: the launches of the files above, minibatch after minibatch)
+#include "bc_fused.hpp"      // k_bc_epoch_fused, oc_bc_epoch_fused, oc_bc_epoch_fused_plan (oc_bc_update's chain for minibatches of one workgroup, in one kernel)
 #endif

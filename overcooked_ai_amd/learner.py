@@ -49,8 +49,12 @@ def plan_update(n_index, minibatch, in_dim=96, h1=64, h2=64, seat=False, moments
 def scratch_rows(n_index, minibatch, in_dim, h1, h2):
     """(rows of a minibatch, rows of the loss partials, rows of the policy partials, floats of a policy partial), read from the
     plan's words."""
-    text = plan_update(n_index, minibatch, in_dim, h1, h2)
-    m = re.search(r"scratch: logits (\d+) x 6 f32.*loss partials (\d+) x 6 f64, policy partials (\d+) x (\d+) f32", text)
+    return _scratch_rows(plan_update(n_index, minibatch, in_dim, h1, h2), 6)
+
+
+def _scratch_rows(text, width):
+    """scratch_rows() of an update plan's words whose loss partials are `width` f64 wide."""
+    m = re.search(r"scratch: logits (\d+) x 6 f32.*loss partials (\d+) x %d f64, policy partials (\d+) x (\d+) f32" % width, text)
     return tuple(int(x) for x in m.groups())
 
 
@@ -165,38 +169,120 @@ class Adam:
         self._call = None
 
 
-class PPOLearner:
-    """The whole update of a PPO minibatch — policy forward, clipped-surrogate loss, backward to the weights, clipped Adam step — as
-    stream-ordered kernels behind ONE C call (oc_ppo_update), for one minibatch (`update`) or a whole pass over a permutation
-    (`epoch`).  The loss's hyperparameters are ppo_loss()'s, the optimiser's are Adam's (`self.adam`, whose state_dict holds the
-    moments).  No autograd: the parameters' `.grad`s are not touched."""
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
 
-    def __init__(self, policy, lr, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff=0.0, max_grad_norm=None,
-                 betas=(0.9, 0.999), eps=1e-8):
-        import math
 
+class _ChainLearner:
+    """What the learners of the update chain (csrc/update_chain.hpp) share: the optimiser, the scratch of a minibatch, the cache of a
+    call's ctypes structs (rebuilt only when an address changes) and the call itself.  A learner supplies its batch checks, the head of
+    its cache key, its loss struct and
+        _plan     its plan call, (n_index, minibatch, in_dim, h1, h2) -> text
+        _WIDTH    the f64 of a row of its loss partials
+        _UPDATE   its update struct
+        _ENTRY    its entry point's name"""
+
+    def __init__(self, policy, lr, betas, eps, max_grad_norm):
         self.adam = Adam(policy, lr, betas, eps, max_grad_norm)
         self.policy = policy
-        self.hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff))
-        if not all(math.isfinite(x) and x > 0 for x in self.hyper[:2]):
-            raise ValueError("clip_param and vf_clip_param must be finite and positive, not %r and %r" % self.hyper[:2])
-        if not all(x >= 0 for x in self.hyper[2:]):
-            raise ValueError("vf_loss_coeff, entropy_coeff and kl_coeff must be >= 0, not %r, %r and %r" % self.hyper[2:])
         self._scratch = {}   # (rows of a minibatch) -> the tensors of one minibatch
-        self._calls = {}     # the addresses and sizes of a call -> its ctypes structs and output tensors' shapes
+        self._calls = {}     # the addresses and sizes of a call -> its ctypes structs
 
     def scratch(self, rows):
         """The scratch of minibatches of up to `rows` rows, as a dict of tensors: logits, values, grad_logits, grad_values, the loss
         and policy partials and `grads`, the eight RAW gradient arrays (a sum over the minibatch, not divided by its count)."""
         return self._scratch[rows]
 
-    def _check_batch(self, features, batch, index, dev):
+    def _check_features(self, features, dev):
         pol = self.policy
         if not isinstance(features, torch.Tensor) or features.dim() < 2 or features.shape[-1] != pol.in_dim or features.dtype != torch.float32 \
                 or not features.is_contiguous() or features.device != dev:
             raise ValueError("features must be a contiguous float32 [..., %d] tensor on %s" % (pol.in_dim, dev))
         if features.data_ptr() % 16:
             raise ValueError("features must be 16-byte aligned")
+
+    @staticmethod
+    def _check_index(index, dev):
+        if not isinstance(index, torch.Tensor) or index.dim() != 1:
+            raise ValueError("index must be a contiguous int32 [n] tensor")
+        _checked("index", index, torch.int32, (int(index.shape[0]),), dev, torch)
+
+    @staticmethod
+    def _check_minibatch(minibatch):
+        if minibatch < 1:
+            raise ValueError("minibatch must be at least 1, not %d" % minibatch)
+
+    def _cached(self, key_head, params, loss, update):
+        """The policy, loss, optimiser and update structs of the call `key_head` names on these parameters, moments and clock
+        (load_state_dict brings new moments and a new clock); loss() and update() build the second and the fourth.  Up to 64 are kept."""
+        key = key_head + tuple(_ptr(p) for p in params) + tuple(_ptr(t) for t in self.adam.m) + (_ptr(self.adam.clock),)
+        call = self._calls.get(key)
+        if call is None:
+            pol = self.policy
+            call = (_lib.OcActorCritic(*[_ptr(p) for p in params], pol.in_dim, pol.h1, pol.h2), loss(), self.adam._struct(), update())
+            if len(self._calls) >= 64:
+                self._calls.clear()
+            self._calls[key] = call
+        return call
+
+    def _outputs(self, n, minibatch, dev, u, ad):
+        """New stats [K, 8] and info [K, 4], bound to the update struct `u`; the optimiser's struct with today's lr and max_grad_norm."""
+        K = (n + minibatch - 1) // minibatch
+        stats = torch.empty((K, 8), dtype=torch.float64, device=dev)
+        info = torch.empty((K, 4), dtype=torch.float64, device=dev)
+        u.d_stats, u.d_info = stats.data_ptr(), info.data_ptr()
+        ad.lr, ad.max_grad_norm = self.adam.lr, self.adam.max_grad_norm if self.adam.max_grad_norm is not None else 0.0
+        return stats, info
+
+    def _chain(self, key_head, loss, features, n_feature_rows, index, minibatch, params, dev):
+        """The entry point on checked tensors.  key_head: what names the call beside parameters, moments and clock; loss: () -> the
+        loss struct of a call that is not in the cache."""
+        n = int(index.shape[0])
+
+        def update():
+            dims = (self.policy.in_dim, self.policy.h1, self.policy.h2)
+            rows, loss_rows, pol_rows, size = _scratch_rows(self._plan(n, minibatch, *dims), self._WIDTH)
+            s = self._scratch.get(rows)
+            if s is None or s["logits"].device != dev:
+                f32 = dict(dtype=torch.float32, device=dev)
+                s = dict(logits=torch.empty((max(rows, 1), 6), **f32), values=torch.empty((max(rows, 1),), **f32),
+                         grad_logits=torch.empty((max(rows, 1), 6), **f32), grad_values=torch.empty((max(rows, 1),), **f32),
+                         loss_partials=torch.empty((loss_rows, self._WIDTH), dtype=torch.float64, device=dev),
+                         policy_partials=torch.empty((pol_rows, size), **f32), grads=[torch.empty(sh, **f32) for sh in shapes(*dims)])
+                self._scratch[rows] = s
+            return self._UPDATE(_ptr(features), n_feature_rows, _ptr(index), n, minibatch, _ptr(s["logits"]), _ptr(s["values"]),
+                                _ptr(s["grad_logits"]), _ptr(s["grad_values"]), _ptr(s["loss_partials"]), _ptr(s["policy_partials"]),
+                                _lib.OcPolicyGrads(*[_ptr(t) for t in s["grads"]]), None, None)
+
+        polc, q, ad, u = self._cached(key_head, params, loss, update)
+        stats, info = self._outputs(n, minibatch, dev, u, ad)
+        with torch.cuda.device(dev):
+            rc = getattr(_lib.load(), self._ENTRY)(ctypes.byref(polc), ctypes.byref(q), ctypes.byref(ad), ctypes.byref(u), _stream(dev))
+        _lib.check(rc, self._ENTRY)
+        return stats, info
+
+
+class PPOLearner(_ChainLearner):
+    """The whole update of a PPO minibatch — policy forward, clipped-surrogate loss, backward to the weights, clipped Adam step — as
+    stream-ordered kernels behind ONE C call (oc_ppo_update), for one minibatch (`update`) or a whole pass over a permutation
+    (`epoch`).  The loss's hyperparameters are ppo_loss()'s, the optimiser's are Adam's (`self.adam`, whose state_dict holds the
+    moments).  No autograd: the parameters' `.grad`s are not touched."""
+
+    _plan, _WIDTH, _UPDATE, _ENTRY = staticmethod(plan_update), 6, _lib.OcPpoUpdate, "oc_ppo_update"
+
+    def __init__(self, policy, lr, clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff=0.0, max_grad_norm=None,
+                 betas=(0.9, 0.999), eps=1e-8):
+        import math
+
+        super().__init__(policy, lr, betas, eps, max_grad_norm)
+        self.hyper = tuple(float(x) for x in (clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff))
+        if not all(math.isfinite(x) and x > 0 for x in self.hyper[:2]):
+            raise ValueError("clip_param and vf_clip_param must be finite and positive, not %r and %r" % self.hyper[:2])
+        if not all(x >= 0 for x in self.hyper[2:]):
+            raise ValueError("vf_loss_coeff, entropy_coeff and kl_coeff must be >= 0, not %r, %r and %r" % self.hyper[2:])
+
+    def _check_batch(self, features, batch, index, dev):
+        self._check_features(features, dev)
         if not isinstance(batch, LearnerBatch):
             raise ValueError("batch must be a LearnerBatch (TrajectoryBuffer.learner_batch)")
         if not isinstance(batch.actions, torch.Tensor) or batch.actions.dim() != 1:
@@ -216,55 +302,21 @@ class PPOLearner:
             _checked("batch.moments", batch.moments, torch.float64, (3,), dev, torch)
         if self.hyper[4] > 0 and batch.logits_old is None:
             raise ValueError("kl_coeff > 0 needs the batch's old logits (TrajectoryBuffer(keep_logits=True))")
-        if not isinstance(index, torch.Tensor) or index.dim() != 1:
-            raise ValueError("index must be a contiguous int32 [n] tensor")
-        _checked("index", index, torch.int32, (int(index.shape[0]),), dev, torch)
-        if S >= 2 ** 31 or features.numel() // pol.in_dim >= 2 ** 31:
+        self._check_index(index, dev)
+        if S >= 2 ** 31 or features.numel() // self.policy.in_dim >= 2 ** 31:
             raise ValueError("an index names samples and feature rows below 2^31")
         return S
 
     def _run(self, features, batch, index, minibatch):
         params, dev = self.adam._device_params()
         S = self._check_batch(features, batch, index, dev)
-        n = int(index.shape[0])
         minibatch = int(minibatch)
-        if minibatch < 1:
-            raise ValueError("minibatch must be at least 1, not %d" % minibatch)
+        self._check_minibatch(minibatch)
         self.adam._state(dev)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        key = (n, minibatch, ptr(features), features.numel(), ptr(index), S) + tuple(ptr(t) for t in batch) + tuple(ptr(p) for p in params) \
-            + tuple(ptr(t) for t in self.adam.m) + (ptr(self.adam.clock),)  # (load_state_dict brings new moments and a new clock)
-        call = self._calls.get(key)
-        if call is None:
-            pol = self.policy
-            dims = (pol.in_dim, pol.h1, pol.h2)
-            rows, loss_rows, pol_rows, size = scratch_rows(n, minibatch, *dims)
-            s = self._scratch.get(rows)
-            if s is None or s["logits"].device != dev:
-                f32 = dict(dtype=torch.float32, device=dev)
-                s = dict(logits=torch.empty((max(rows, 1), 6), **f32), values=torch.empty((max(rows, 1),), **f32),
-                         grad_logits=torch.empty((max(rows, 1), 6), **f32), grad_values=torch.empty((max(rows, 1),), **f32),
-                         loss_partials=torch.empty((loss_rows, 6), dtype=torch.float64, device=dev),
-                         policy_partials=torch.empty((pol_rows, size), **f32), grads=[torch.empty(sh, **f32) for sh in shapes(*dims)])
-                self._scratch[rows] = s
-            K = (n + minibatch - 1) // minibatch
-            u = _lib.OcPpoUpdate(ptr(features), features.numel() // pol.in_dim, ptr(index), n, minibatch, ptr(s["logits"]), ptr(s["values"]),
-                                 ptr(s["grad_logits"]), ptr(s["grad_values"]), ptr(s["loss_partials"]), ptr(s["policy_partials"]),
-                                 _lib.OcPolicyGrads(*[ptr(t) for t in s["grads"]]), None, None)
-            q = _lib.OcPpoLoss(ptr(batch.actions), ptr(batch.logp_old), ptr(batch.advantages), ptr(batch.targets), ptr(batch.seat),
-                               ptr(batch.logits_old), ptr(batch.moments), S, None, None, None, 0, 0, None, None, None, None, None, *self.hyper)
-            if len(self._calls) >= 64:
-                self._calls.clear()
-            call = self._calls[key] = (_lib.OcActorCritic(*[ptr(p) for p in params], *dims), q, self.adam._struct(), u, K)
-        polc, q, ad, u, K = call
-        stats = torch.empty((K, 8), dtype=torch.float64, device=dev)
-        info = torch.empty((K, 4), dtype=torch.float64, device=dev)
-        u.d_stats, u.d_info = stats.data_ptr(), info.data_ptr()
-        ad.lr, ad.max_grad_norm = self.adam.lr, self.adam.max_grad_norm if self.adam.max_grad_norm is not None else 0.0
-        with torch.cuda.device(dev):
-            rc = _lib.load().oc_ppo_update(ctypes.byref(polc), ctypes.byref(q), ctypes.byref(ad), ctypes.byref(u), _stream(dev))
-        _lib.check(rc, "oc_ppo_update")
-        return stats, info
+        key = (int(index.shape[0]), minibatch, _ptr(features), features.numel(), _ptr(index), S) + tuple(_ptr(t) for t in batch)
+        loss = lambda: _lib.OcPpoLoss(_ptr(batch.actions), _ptr(batch.logp_old), _ptr(batch.advantages), _ptr(batch.targets), _ptr(batch.seat),  # noqa: E731
+                                      _ptr(batch.logits_old), _ptr(batch.moments), S, None, None, None, 0, 0, None, None, None, None, None, *self.hyper)
+        return self._chain(key, loss, features, features.numel() // self.policy.in_dim, index, minibatch, params, dev)
 
     def update(self, features, batch, index):
         """One minibatch: the rows of `features` (any contiguous float32 [..., in_dim] tensor) and the samples of `batch` (a

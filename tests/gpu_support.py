@@ -1,4 +1,5 @@
-"""What the GPU tests share and torch is needed for: the device fixture, output arrays with guard rows, the packed event counters,
+"""What the GPU tests share and torch is needed for: the device fixture, output arrays with guard rows, arrays at the header's minimum alignment between
+guard bytes (Fenced) and the comparison of bit patterns (bits, same) of the learner tests, the packed event counters,
 the env and oracle constructors of the parity tests, the sentinel-filled, guarded output arrays of a rollout launch, and the runner of
 one oc_rollout_random launch beside the oracle.  Imported like helpers.py; tests/case_support.py holds what needs no torch."""
 import numpy as np
@@ -25,6 +26,44 @@ def guarded(rows, row_shape, dtype, fill, device, before=0):
     guard slices: the rows behind the output and, with before > 0, those before it)."""
     whole = torch.full((before + rows + GUARD,) + tuple(row_shape), fill, dtype=dtype, device=device)
     return whole[before:before + rows], (whole[before + rows:],) + ((whole[:before],) if before else ())
+
+
+GUARD_BYTES, GUARD_BYTE = 64, 0xEE  # the guard bytes on either side of a Fenced array, and what they hold
+_TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32, np.dtype(np.uint8): torch.uint8}
+
+
+class Fenced:
+    """A device copy of numpy array `a` between GUARD_BYTES guard bytes on either side, its first byte `align` bytes behind a multiple
+    of 2 * align: the minimum alignment include/oc_amd.h allows, which a fresh allocation never has."""
+
+    def __init__(self, a, align, dev):
+        a = np.ascontiguousarray(a)
+        self.raw = torch.full((a.nbytes + 2 * GUARD_BYTES + 4 * align,), GUARD_BYTE, dtype=torch.uint8, device=dev)
+        self.off = GUARD_BYTES + (align - (self.raw.data_ptr() + GUARD_BYTES)) % (2 * align)
+        self.nbytes = a.nbytes
+        part = self.raw[self.off:self.off + a.nbytes]
+        part.copy_(torch.from_numpy(a.reshape(-1).view(np.uint8).copy()))  # (a byte copy: NaN payloads arrive as they are)
+        self.t = part.view(_TORCH[a.dtype]).view(a.shape)
+        assert self.t.data_ptr() % (2 * align) == align % (2 * align)
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def host(self):
+        return self.t.cpu().numpy()
+
+    def intact(self):
+        return bool((self.raw[:self.off] == GUARD_BYTE).all()) and bool((self.raw[self.off + self.nbytes:] == GUARD_BYTE).all())
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
+
+
+def same(x, y):
+    return np.array_equal(bits(x), bits(y))
 
 
 def guards_untouched(case, what, guards, fill):

@@ -1,4 +1,4 @@
-"""The cases of oc_adam_step and oc_ppo_update (include/oc_amd.h: OcAdam, OcPpoUpdate; csrc/adam.hpp, csrc/ppo_update.hpp) and two
+"""The cases of oc_adam_step and oc_ppo_update (include/oc_amd.h: OcAdam, OcPpoUpdate; csrc/adam.hpp, csrc/update_chain.hpp) and two
 numpy statements of the step: `adam_f32`, the header's operations one by one — the order of the norm's sum included —, which the
 device must equal as BIT PATTERNS, and `adam_f64`, the reference: the same step in float64 on the same float32 inputs (the
 hyperparameters widened from float32, the norm a plain float64 sum).  numpy only; imported like helpers.py.

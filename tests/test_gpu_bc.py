@@ -24,13 +24,11 @@ import torch
 import bc_cases as BC
 import learner_cases as LC
 import policy_cases as PC
-from gpu_support import GUARD, gpu, guarded, guards_untouched  # noqa: F401
+from gpu_support import _TORCH, GUARD, Fenced, bits, gpu, guarded, guards_untouched, same  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FILL = BC.FILL
-_TORCH = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8,
-          np.dtype(np.int32): torch.int32}
 
 
 def placed(a, align, dev):
@@ -46,15 +44,6 @@ def placed(a, align, dev):
     t = part.view(_TORCH[a.dtype]).view(a.shape)
     assert t.data_ptr() % (2 * align) == align
     return t
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
-
-
-def same(x, y):
-    return np.array_equal(bits(x), bits(y))
 
 
 def run(c, a, dev, grads=True, stats=True, rows=None):
@@ -197,33 +186,7 @@ def test_g2_no_rows_launch_nothing_and_zero_the_stats(gpu):
 
 
 # ------------------------------------------------------------------------------------------ G3, G4: oc_bc_update
-GUARD_BYTES, GUARD_BYTE = 64, 0xEE
 HYPER = LC.Hyper(1e-3, 0.9, 0.999, 1e-8, 0.1)
-
-
-class Fenced:
-    """A device copy of numpy array `a` between GUARD_BYTES guard bytes on either side, its first byte `align` bytes behind a multiple
-    of 2 * align: the minimum alignment include/oc_amd.h allows."""
-
-    def __init__(self, a, align, dev):
-        a = np.ascontiguousarray(a)
-        self.raw = torch.full((a.nbytes + 2 * GUARD_BYTES + 4 * align,), GUARD_BYTE, dtype=torch.uint8, device=dev)
-        self.off = GUARD_BYTES + (align - (self.raw.data_ptr() + GUARD_BYTES)) % (2 * align)
-        self.nbytes = a.nbytes
-        part = self.raw[self.off:self.off + a.nbytes]
-        part.copy_(torch.from_numpy(a.reshape(-1).view(np.uint8).copy()))
-        self.t = part.view(_TORCH[a.dtype]).view(a.shape)
-        assert self.t.data_ptr() % (2 * align) == align % (2 * align)
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def host(self):
-        return self.t.cpu().numpy()
-
-    def intact(self):
-        return bool((self.raw[:self.off] == GUARD_BYTE).all()) and bool((self.raw[self.off + self.nbytes:] == GUARD_BYTE).all())
 
 
 class Update:

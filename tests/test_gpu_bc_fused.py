@@ -20,21 +20,12 @@ import torch
 
 import bc_cases as BC
 import bc_fused_cases as FC
-from gpu_support import guarded, guards_untouched, gpu  # noqa: F401
+from gpu_support import bits, guarded, guards_untouched, gpu, same  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FILL = FC.FILL
 CLOCK0 = np.array([0.0, 1.0, 1.0, 0.0])
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
-
-
-def same(x, y):
-    return np.array_equal(bits(x), bits(y))
 
 
 def same_info(x, y):

@@ -26,47 +26,11 @@ import torch
 import learner_cases as LC
 import policy_cases as PC
 import ppo_loss_cases as PL
-from gpu_support import gpu  # noqa: F401
+from gpu_support import Fenced, bits, gpu, same  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TOL = LC.DEVICE_FACTOR * LC.F32_ERROR
-GUARD, GUARD_BYTE = 64, 0xEE
-_TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32, np.dtype(np.uint8): torch.uint8}
-
-
-class Fenced:
-    """A device copy of numpy array `a` between GUARD guard bytes on either side, its first byte `align` bytes behind a multiple of
-    2 * align: the minimum alignment include/oc_amd.h allows, which a fresh allocation never has."""
-
-    def __init__(self, a, align, dev):
-        a = np.ascontiguousarray(a)
-        self.raw = torch.full((a.nbytes + 2 * GUARD + 4 * align,), GUARD_BYTE, dtype=torch.uint8, device=dev)
-        self.off = GUARD + (align - (self.raw.data_ptr() + GUARD)) % (2 * align)
-        self.nbytes = a.nbytes
-        part = self.raw[self.off:self.off + a.nbytes]
-        part.copy_(torch.from_numpy(a.reshape(-1).view(np.uint8).copy()))  # (a byte copy: NaN payloads arrive as they are)
-        self.t = part.view(_TORCH[a.dtype]).view(a.shape)
-        assert self.t.data_ptr() % (2 * align) == align % (2 * align)
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def host(self):
-        return self.t.cpu().numpy()
-
-    def intact(self):
-        return bool((self.raw[:self.off] == GUARD_BYTE).all()) and bool((self.raw[self.off + self.nbytes:] == GUARD_BYTE).all())
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
-
-
-def same(x, y):
-    return np.array_equal(bits(x), bits(y))
 
 
 class Optimiser:
