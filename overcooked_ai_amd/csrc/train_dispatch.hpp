@@ -401,7 +401,7 @@ int train_sequence(const TrainCall& c, const TrainPlan& p) {
     if (b->n_envs > 0) {
         StartArgs none;
         start_args(nullptr, &none);
-        launch_step(b, p.n_obj, c.d_state, c.d_state, c.d_actions, c.d_rewards, c.d_flags, c.d_ep_returns, c.horizon, 0u, c.stream, none, c.ea);
+        launch_step(StepCall{b, p.n_obj, c.d_state, c.d_state, c.d_actions, c.d_rewards, c.d_flags, c.d_ep_returns, c.horizon, 0u, 1, none, c.ea, c.stream});
         if (int rc = check_launch(c.who)) return rc;
     }
     if (c.d_phi_tables) {

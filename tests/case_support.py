@@ -229,7 +229,7 @@ def check_census(found, instances, unreachable, reached, count, what="kernels"):
         if not ok:
             pytest.fail(message)
 
-    check(len(found) == len(set(found)) == count, "csrc/oc_amd.hip instantiates %d %s, not %d: %s" % (len(found), what, count, sorted(found)))
+    check(len(found) == len(set(found)) == count, "csrc/ instantiates %d %s, not %d: %s" % (len(found), what, count, sorted(found)))
     check(sorted(found) == sorted(instances), "the list's instances are not the sources': %s" % sorted(set(found) ^ set(instances)))
     check(not reached & set(unreachable), "reached after all: %s" % sorted(reached & set(unreachable)))
     check(not set(found) - reached - set(unreachable), "no case reaches %s" % sorted(set(found) - reached - set(unreachable)))

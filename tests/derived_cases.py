@@ -1,7 +1,7 @@
 """One list of oc_potential and oc_featurize calls, each there for ONE kernel instance, the states they start from, and the C
 oracle's answer.
 
-The family launches four kernel instances (csrc/oc_amd.hip: oc_potential, launch_featurize): k_potential2 (every layout of the
+The family launches four kernel instances (csrc/derived_dispatch.hpp: oc_potential, launch_featurize): k_potential2 (every layout of the
 table has one or two pots), k_potential (any other table, and withheld hints), k_featurize<LAY_LDS=true> (a table of at most 32
 layouts) and k_featurize<LAY_LDS=false>.  Every case names the instance it is there for (`expect`: the words of oc_potential_plan /
 oc_featurize_plan up to and including the instance's name); tests/test_host_derived_instances.py holds the list to the planner's

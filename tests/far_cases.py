@@ -118,12 +118,12 @@ SITES = (
     (("step_lut4.hpp", "k_rollout4, terrain"), ("terrain_lds@far", "terrain_l2_one_pot_regen@far")),
     (("step_lut4.hpp", "k_rollout4, arithmetic: pot blocks 3..9 of the start stream"), ("arith_general_seven_pots@far", "ev_small_masks@far")),
     (("step_lut4.hpp", "k_rollout4: epoch + k"), ("joint_pipe@far", "terrain_l2_one_pot_regen@far", "arith_general_seven_pots@far")),
-    (("oc_amd.hip", "the head / bulk / tail split: t0 + off and epoch + off"), ("split_joint_table_layout@far", "split_mix5_event_counters@far")),
+    (("rollout_dispatch.hpp", "the head / bulk / tail split: t0 + off and epoch + off"), ("split_joint_table_layout@far", "split_mix5_event_counters@far")),
     (("step_lut4.hpp", "k_rollout4<REC>: oc_rollout_record_ex"), (RECORD,)),
     (("step_predicate.hpp", "k_rollout: action stream"), ("predicate_interact_standard_start@far",)),
     (("rollout_pair.hpp", "k_rollout_pair: action stream"), ("lane_pair_standard_start@far",)),
     (("rollout_encode.hpp", "k_rollout_encode: action stream and epoch + k"), ("rollout_u8_unit1@far",)),
-    (("oc_amd.hip", "the oc_step_encode sequence"), ("step_encode_drawn_sequence@far",)),
+    (("observation_dispatch.hpp", "the oc_step_encode sequence"), ("step_encode_drawn_sequence@far",)),
     (("step_one.hpp", "k_step1: epoch"), ("step1_table_in_lds_regen@far",)),
     (("step_table.hpp", "k_step3: epoch + k"), ("step3_fast_one_pot_many@far",)),
     (("step_predicate.hpp", "k_step (caller actions, standard starts)"), ("predicate_two_pots@far",)),

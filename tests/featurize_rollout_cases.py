@@ -28,7 +28,7 @@ import train_cases  # noqa: F401 (... and rollout_cases': mix5)
 from case_support import DRAWN, caller_actions, layout_ids, new_oracle, register_grid, seeded_states, table_of
 
 ONE_KERNEL = "k_rollout_featurize<MAXP=2, FAST=3>"
-INSTANCES = (ONE_KERNEL,)  # every kernel instance csrc/oc_amd.hip instantiates for oc_rollout_featurize
+INSTANCES = (ONE_KERNEL,)  # every kernel instance csrc/observation_dispatch.hpp instantiates for oc_rollout_featurize
 SEEDED = 4096              # a larger batch repeats the seeded states of its first 4 096 envs
 N_BAD = 3                  # illegal actions per step of a call with caller actions
 # 8 x 7 = 56 cells: four object planes, two pots, counters inside the room

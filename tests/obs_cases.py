@@ -1,6 +1,6 @@
 """One list of observation calls, each there for ONE kernel instance of the observation path, and the C oracle's run of such a call.
 
-The observation path launches 13 kernel instances (csrc/oc_amd.hip: launch_encode, launch_rollout_encode): k_encode_uniform<u8>,
+The observation path launches 13 kernel instances (csrc/observation_dispatch.hpp: launch_encode, launch_rollout_encode): k_encode_uniform<u8>,
 k_encode<T, LAY_LDS> (4) and k_rollout_encode<MAXP=2, FAST, T, NW> (8).  plan_encode / plan_rollout_encode (csrc/
 observation_plan.hpp) pick one from the table's hints, the batch size, the observation type and the option bits.  Every case below
 names what it is there for (`expect`: the words of oc_observation_plan up to and including `>`, and those of unit=, G=, epb=,
@@ -57,7 +57,7 @@ def step_by_step(entry, encode):
     return "step by step: %s + %s" % (entry, encode)
 
 
-# Every kernel instance csrc/oc_amd.hip instantiates for the observation path
+# Every kernel instance csrc/observation_dispatch.hpp instantiates for the observation path
 INSTANCES = tuple([uniform(0, 0, 0).split(">")[0] + ">"] + [generic(t, ll) for t in ("u8", "f32") for ll in (True, False)]
                   + [single(f, t, w) for f in (3, 0) for t in ("u8", "f32") for w in (8, 4)])
 _NO_U8_NW4 = ("four wavefronts need eight images of fewer than 4 envs (gmax < 4): the largest u8 grid the kernel takes, 48 cells, "

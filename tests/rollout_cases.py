@@ -1,6 +1,6 @@
 """One list of oc_rollout_random calls, each there for ONE kernel instance, and the C oracle's run of such a call.
 
-`oc_rollout_random` is not one kernel: choose_launch (csrc/oc_amd.hip) picks one of k_rollout4's non-recording instances
+`oc_rollout_random` is not one kernel: choose_launch (csrc/rollout_dispatch.hpp) picks one of k_rollout4's non-recording instances
 (R4Instances, csrc/shared.hpp) or one of k_rollout5's 24 from the table's hints, the batch size, the launch shape, the output
 arrays, the event sink and two option bits.  Every case below names the instance it is there for (`expect`: the words of
 oc_rollout_plan up to and including `>`); tests/test_host_rollout_instances.py holds the list to the planner's answers and to

@@ -1,10 +1,10 @@
 """One list of caller-actions calls (oc_step, oc_step_many, oc_step_server_*), each there for ONE kernel instance, and the C oracle's
 run of such a call.
 
-The family launches 29 kernel instances (csrc/oc_amd.hip: launch_step_as, sv_launch): k_step1<UNIFORM, MAXP, LAY_LDS, EVENTS> (12:
+The family launches 29 kernel instances (csrc/step_dispatch.hpp: launch_step_as; csrc/step_server_host.hpp: sv_launch): k_step1<UNIFORM, MAXP, LAY_LDS, EVENTS> (12:
 one step on a grid of at most four object planes), k_step3<UNIFORM, MAXP, LAY_LDS, FAST, EVENTS> (8: oc_step_many, and single steps
 on 65..128 cells), k_step<UNIFORM, MAXP, LAY_LDS, EVENTS> (6: OC_OPT_PREDICATE_INTERACT) and k_step_server<UNIFORM, MAXP, LAY_LDS>
-(3: the resident step).  choose_step (csrc/oc_amd.hip) picks one from the table's hints, the grid, the option bits, the number of
+(3: the resident step).  choose_step (csrc/step_dispatch.hpp) picks one from the table's hints, the grid, the option bits, the number of
 steps and the event sink.  Every case below names the instance it is there for (`expect`: the words of oc_step_plan up to and
 including `>`); tests/test_host_step_instances.py holds the list to the planner's answers and to the instances the sources
 instantiate, without a GPU, and tests/test_gpu_step_instances.py runs every case against the oracle at zero tolerance.
@@ -53,7 +53,7 @@ STEP1_ROWS = ((True, 1, True), (True, 2, True), (True, 8, True), (False, 2, True
 STEP3_ROWS = ((True, 1, True, True), (True, 2, True, True), (False, 2, True, False), (False, 8, False, False))
 PRED_ROWS = ((True, 2, True), (True, 8, True), (False, 8, False))
 SERVER_ROWS = ((True, 2, True), (False, 2, True), (False, 8, False))
-# Every kernel instance csrc/oc_amd.hip instantiates for the caller-actions family
+# Every kernel instance csrc/step_dispatch.hpp lists for the caller-actions family
 INSTANCES = tuple([step1(*r, EVENTS=ev) for r in STEP1_ROWS for ev in (False, True)] + [step3(*r, EVENTS=ev) for r in STEP3_ROWS for ev in (False, True)]
                   + [pred(*r, EVENTS=ev) for r in PRED_ROWS for ev in (False, True)] + [server(*r) for r in SERVER_ROWS])
 # Instances no call reaches without a tuning knob, each with its reason: none — every instance has a case

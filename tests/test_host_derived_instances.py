@@ -1,5 +1,5 @@
 """tests/derived_cases.py kept honest without a GPU: every case is planned (oc_potential_plan / oc_featurize_plan) onto the kernel
-instance it names, the cases cover the four kernel instances csrc/oc_amd.hip launches for oc_potential and oc_featurize, the
+instance it names, the cases cover the four kernel instances csrc/derived_dispatch.hpp launches for oc_potential and oc_featurize, the
 planners' selection boundaries and refusals hold, the states of every case hold the situations the case lists — at least one
 wavefront's worth of envs each, and one in every whole workgroup —, and the set orders those states ask for on the new layouts are
 the running interpreter's.  A change to the planners that moves a case to another kernel fails here, by the case's name, instead of
@@ -23,8 +23,8 @@ def _ledger():
 
 
 def _instantiated():
-    """The kernel instances oc_potential and oc_featurize (csrc/oc_amd.hip) launch, in their planners' words."""
-    with open(os.path.join(CSRC, "oc_amd.hip")) as f:
+    """The kernel instances oc_potential and oc_featurize (csrc/derived_dispatch.hpp) launch, in their planners' words."""
+    with open(os.path.join(CSRC, "derived_dispatch.hpp")) as f:
         src = f.read()
     pot = _function(src, "oc_potential")
     found = re.findall(r"hipLaunchKernelGGL\((k_potential2?),", pot)

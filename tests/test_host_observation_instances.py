@@ -1,5 +1,5 @@
 """tests/obs_cases.py kept honest without a GPU: every case is planned (oc_observation_plan) onto the kernel instance it names, the
-cases and the named exclusions cover the 13 observation kernel instances csrc/oc_amd.hip instantiates, the exclusions hold for every
+cases and the named exclusions cover the 13 observation kernel instances csrc/observation_dispatch.hpp instantiates, the exclusions hold for every
 grid the single kernel takes, and on the oracle alone each case contains what it is there for — urgent and other envs in one
 sub-group, restarts inside the launch, crowded and sparse sub-groups side by side, every kind of object, flagged illegal actions.
 A change to plan_encode / plan_rollout_encode (csrc/observation_plan.hpp) that moves a case to another kernel fails here, by the
@@ -26,9 +26,9 @@ def _ledger():
 
 
 def _instantiated():
-    """The observation kernel instances launch_encode and launch_rollout_encode (csrc/oc_amd.hip) launch, and the ones
+    """The observation kernel instances launch_encode and launch_rollout_encode (csrc/observation_dispatch.hpp) launch, and the ones
     rollout_encode_lds asks the runtime about, in oc_observation_plan's words."""
-    with open(os.path.join(CSRC, "oc_amd.hip")) as f:
+    with open(os.path.join(CSRC, "observation_dispatch.hpp")) as f:
         src = f.read()
     kinds = {"uint8_t": "u8", "float": "f32"}
     enc = _function(src, "launch_encode")

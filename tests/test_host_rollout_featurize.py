@@ -1,6 +1,6 @@
 """oc_rollout_featurize without a GPU: plan_rollout_featurize (csrc/observation_plan.hpp) through oc_rollout_featurize_plan — the
 conditions of the single kernel one at a time, every refusal before any device call, the empty calls, the instances the planner can
-name against the ones csrc/oc_amd.hip instantiates — and tests/featurize_rollout_cases.py kept honest: every case is planned onto
+name against the ones csrc/observation_dispatch.hpp instantiates — and tests/featurize_rollout_cases.py kept honest: every case is planned onto
 the path it names, and on the oracle alone its run contains what it claims."""
 import ctypes
 import os
@@ -112,8 +112,8 @@ def test_empty_calls_plan_and_launch_nothing():
 
 
 def _instantiated():
-    """The instances launch_rollout_featurize (csrc/oc_amd.hip) launches, in oc_rollout_featurize_plan's words."""
-    with open(os.path.join(CSRC, "oc_amd.hip")) as f:
+    """The instances launch_rollout_featurize (csrc/observation_dispatch.hpp) launches, in oc_rollout_featurize_plan's words."""
+    with open(os.path.join(CSRC, "observation_dispatch.hpp")) as f:
         src = f.read()
     body = function_body(src, "launch_rollout_featurize")
     found = ["k_rollout_featurize<MAXP=%s, FAST=%s>" % mf for mf in re.findall(r"hipLaunchKernelGGL\(\(k_rollout_featurize<(\d), (\d)>\)", body)]
@@ -139,8 +139,11 @@ def test_the_instances_the_planner_names_are_the_ones_the_sources_instantiate():
                 big = plan(batch(w, h, 65537, max_pots=pots), num_pots=num_pots)[1]
                 assert big == text.replace("grid=2,", "grid=257,"), big  # (the batch size changes the grid alone)
                 assert lds + 4608 + 64 <= 160 * 1024, text  # (4 608 bytes of static LDS)
-    steps = function_body(open(os.path.join(CSRC, "oc_amd.hip")).read(), "rollout_featurize_step_by_step")
-    assert "hipLaunchKernelGGL" not in steps and re.search(r"\boc_featurize\(", steps) and "oc_step(" in steps and "oc_rollout_random(" in steps
+    # (rollout_featurize_step_by_step: the loop it shares with oc_rollout_encode, with oc_featurize as the observation of a step)
+    src = open(os.path.join(CSRC, "observation_dispatch.hpp")).read()
+    steps, loop = function_body(src, "rollout_featurize_step_by_step"), function_body(src, "rollout_step_by_step")
+    assert "hipLaunchKernelGGL" not in steps and re.search(r"\boc_featurize\(", steps) and "return rollout_step_by_step(c, " in steps
+    assert "hipLaunchKernelGGL" not in loop and "oc_step(" in loop and "oc_rollout_random(" in loop and "observe(k)" in loop
 
 
 @pytest.mark.parametrize("case", FC.CASES + (FC.far_case(),), ids=lambda c: c.id)

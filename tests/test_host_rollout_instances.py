@@ -1,6 +1,6 @@
 """tests/rollout_cases.py kept honest without a GPU: every case is planned (oc_rollout_plan) onto the kernel instance it names,
 the cases reach every instance the sources list, and on the oracle alone each case contains what it is there for — restarts,
-shaped rewards, deliveries, events, re-drawn layouts.  A change to choose_launch (csrc/oc_amd.hip) that moves a case to another
+shaped rewards, deliveries, events, re-drawn layouts.  A change to choose_launch (csrc/rollout_dispatch.hpp) that moves a case to another
 kernel fails here, by the case's name, instead of silently changing what a GPU test runs."""
 import itertools
 import os

@@ -1,8 +1,8 @@
 """tests/step_cases.py kept honest without a GPU: every case is planned (oc_step_plan) onto the kernel instance it names, the cases
-cover the 29 kernel instances csrc/oc_amd.hip instantiates for oc_step, oc_step_many and oc_step_server_*, the coverage the list
+cover the 29 kernel instances csrc/step_dispatch.hpp lists for oc_step, oc_step_many and oc_step_server_*, the coverage the list
 promises holds, the planner's rules and refusals hold over a sweep of synthetic batches, and on the oracle alone each case contains
 what it is there for — restarts at different steps within a wavefront, flagged illegal actions, every event type its table can
-produce, every kind of pot, re-drawn layouts.  A change to choose_step (csrc/oc_amd.hip) that moves a case to another kernel fails
+produce, every kind of pot, re-drawn layouts.  A change to choose_step (csrc/step_dispatch.hpp) that moves a case to another kernel fails
 here, by the case's name, instead of silently changing what a GPU test runs."""
 import ctypes
 import itertools
@@ -23,25 +23,47 @@ def _ledger():
 
 
 def _instantiated():
-    """The kernel instances launch_step_as and sv_launch (csrc/oc_amd.hip) launch, in oc_step_plan's words: the GO1 / GO3 / GO /
-    GOSV lines of their switches, each family once without and once with EVENTS (launch_step_from picks the template)."""
-    with open(os.path.join(CSRC, "oc_amd.hip")) as f:
+    """The kernel instances launch_step_as (csrc/step_dispatch.hpp) and sv_launch (csrc/step_server_host.hpp) launch, in
+    oc_step_plan's words: the StepRow lines of the four row lists of step_dispatch.hpp, each walked (launch_row) with the one lambda
+    that names its kernel with the row's template arguments; k_step1 / k_step3 / k_step once without and once with EVENTS (launch_step_from picks
+    the template)."""
+    with open(os.path.join(CSRC, "step_dispatch.hpp")) as f:
         src = f.read()
+    with open(os.path.join(CSRC, "step_server_host.hpp")) as f:
+        sv = _function(f.read(), "sv_launch")
     tf = {"true": True, "false": False}
+
+    def rows(name, n_args):
+        """the (UNIFORM, MAXP, LAY_LDS[, FAST]) of every row of `using <name> = StepRows<...>;`, one row per line"""
+        text = re.search(r"^using %s = StepRows<[^\n]*\n(.*?>>);\n" % name, src, re.S | re.M).group(1)
+        found = re.findall(r"^\s+StepRow<(true|false), (\d), (true|false)(?:, (true|false))?>[,>]$", text, re.M)
+        assert len(found) == len(text.splitlines()) and all((f != "") == (n_args == 4) for *_, f in found), text  # nothing but rows
+        return [(tf[u], int(mp), tf[ll]) + ((tf[f],) if n_args == 4 else ()) for u, mp, ll, f in found]
+
+    # each kernel is named once, with the row's template arguments, in the lambda that the walk of its row list is given; the
+    # lambdas of launch_step_as launch through its `launch`, sv_launch's launches itself
     body = _function(src, "launch_step_as")
-    assert "hipLaunchKernelGGL((k_step1<U, MP, LL, EVENTS>)" in body and "hipLaunchKernelGGL((k_step3<U, MP, LL, F, EVENTS>)" in body
-    assert "hipLaunchKernelGGL((k_step<U, MP, LL, EVENTS>)" in body
+    assert body.count("hipLaunchKernelGGL(kernel, ") == 1 and sv.count("hipLaunchKernelGGL(kernel, ") == 1
+    for kernel, args, walk, where in (("k_step1", "row.UNIFORM, row.MAXP, row.LAY_LDS, EVENTS", "Step1Rows", body),
+                                      ("k_step3", "row.UNIFORM, row.MAXP, row.LAY_LDS, row.FAST, EVENTS", "Step3Rows", body),
+                                      ("k_step", "row.UNIFORM, row.MAXP, row.LAY_LDS, EVENTS", "PredicateRows", body),
+                                      ("k_step_server", "row.UNIFORM, row.MAXP, row.LAY_LDS", "ServerRows", sv)):
+        assert re.findall(r"\b%s<[^>]*>" % kernel, where) == ["%s<%s>" % (kernel, args)], kernel
+        assert where.count("launch_row(%s(), ch, " % walk) == 1, kernel
+        if where is sv:
+            assert re.search(r"launch_row\(ServerRows\(\), ch, \[&\]\(auto row\) \{\n[^}]*\bk_step_server<[^}]*hipLaunchKernelGGL\(kernel, ", sv), kernel
+        else:
+            (name, _), = [(n, text) for n, text in re.findall(r"const auto (\w+) = \[&\]\(auto row\) \{\n(.*?)\n    \};", body, re.S)
+                          if kernel + "<" in text and re.search(r"\blaunch\(", text)]
+            assert "launch_row(%s(), ch, %s)" % (walk, name) in body, kernel
     go = _function(src, "launch_step_from")
     assert "ch.events ? launch_step_as<true> : launch_step_as<false>" in go
     found = []
     for ev in (False, True):
-        found += [SC.step1(tf[u], int(mp), tf[ll], ev) for u, mp, ll in re.findall(r"^\s+GO1\((true|false), (\d), (true|false)\);", body, re.M)]
-        found += [SC.step3(tf[u], int(mp), tf[ll], tf[f], ev)
-                  for u, mp, ll, f in re.findall(r"^\s+GO3\((true|false), (\d), (true|false), (true|false)\);", body, re.M)]
-        found += [SC.pred(tf[u], int(mp), tf[ll], ev) for u, mp, ll in re.findall(r"^\s+GO\((true|false), (\d), (true|false)\);", body, re.M)]
-    sv = _function(src, "sv_launch")
-    assert "hipLaunchKernelGGL((k_step_server<U, MP, LL>)" in sv
-    found += [SC.server(tf[u], int(mp), tf[ll]) for u, mp, ll in re.findall(r"^\s+GOSV\((true|false), (\d), (true|false)\);", sv, re.M)]
+        found += [SC.step1(*row, ev) for row in rows("Step1Rows", 3)]
+        found += [SC.step3(*row, ev) for row in rows("Step3Rows", 4)]
+        found += [SC.pred(*row, ev) for row in rows("PredicateRows", 3)]
+    found += [SC.server(*row) for row in rows("ServerRows", 3)]
     return found
 
 
