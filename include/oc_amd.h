@@ -1236,9 +1236,9 @@ int oc_policy_backward(const OcActorCritic* policy, const OcPolicyRows* rows, co
  *   "k_policy_backward<F0=0,NF=3,REST> grid=256, 256 lanes (4 wavefronts x 32-row tiles), 128 rows per workgroup per pass, 32 x 32 x 2 f32 MFMA, 12 accumulator tiles per wavefront, index=yes, 147456 B LDS + k_policy_grad_sum grid=43, 256 lanes, 256 partial(s) of 10823 floats"
  *   "nothing to launch (no rows)"
  *   "k_policy_grad_sum grid=43, 256 lanes, 0 partial(s) of 10823 floats (no rows: the gradients are zeroed)"
- * The grid is the number of workgroups, at most 256.  With 116 and 136 inputs a backward workgroup has three wavefronts (its LDS
- * holds no more) and a second k_policy_backward launch ("+ k_policy_backward<F0=3,NF=2> grid=256 (feature rows 96.. of gw1)")
- * accumulates the rows of gw1 that the first one's registers do not hold; the order of summation is the same.  The checks that need no array apply; usable without a GPU, like the other plan calls; refusals carry the name of the entry
+ * The grid is the number of workgroups, at most 256.  With 136 inputs a backward workgroup has three wavefronts (its LDS
+ * holds no more; at 116 inputs four still fit) and with 116 and 136 inputs a second k_policy_backward launch
+ * ("+ k_policy_backward<F0=3,NF=2> grid=256 (feature rows 96.. of gw1)") accumulates the rows of gw1 that the first one's registers do not hold; the order of summation is the same.  The checks that need no array apply; usable without a GPU, like the other plan calls; refusals carry the name of the entry
  * point the plan is for.
  *   out, out_size caller's text buffer (>= 384 bytes holds every answer)
  */

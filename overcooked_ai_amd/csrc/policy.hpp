@@ -74,7 +74,7 @@ __host__ __device__ constexpr size_t pol_forward_lds(int in_dim) {
 __host__ __device__ constexpr size_t pol_backward_lds(int in_dim, int waves) {
     return sizeof(float) * (size_t)(pl_w1_floats(in_dim) + 2 * PL_W2 + POL_WPT + 2 * PL_HID + waves * (pol_image_floats(in_dim) + POL_BUF + POL_D3));
 }
-// wavefronts of a backward workgroup: four where the LDS holds their images, else three (116 and 136 inputs)
+// wavefronts of a backward workgroup: four where the LDS holds their images (up to 116 inputs: 163 008 of 163 840 bytes), else three (136 inputs)
 __host__ __device__ constexpr int pol_backward_waves(int in_dim) { return pol_backward_lds(in_dim, PL_WAVES) <= POL_LDS_MAX ? PL_WAVES : PL_WAVES - 1; }
 
 struct PolicyLayout {  // offsets (floats) of the eight gradient arrays inside a partial

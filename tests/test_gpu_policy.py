@@ -6,14 +6,22 @@ F2  the six logits bit for bit what oc_partner_logits writes for an env seated a
 F3  488 rows = 200 + 288 via first_row; an indexed call = the contiguous call on the gathered rows; out-of-range rows +0.0f by bit
     pattern; act = forward on the [2 N, F] view.
 B1  every gradient tensor of every case: scaled error (tests/policy_cases.py) at most DEVICE_FACTOR * F32_ERROR = 4e-4.  Largest
-    observed on an MI355X: 0.481 of that (1.9e-4, w2 of 96_64_64-32rows-indexed-dense; every other case below 0.1 of it); F1's
-    largest error / bound: 0.0063 (profiles/policy.txt).
+    observed on an MI355X: 0.481 of that (1.9e-4, w2 of 96_64_64-32rows-indexed-dense; every other case below 0.13 of it); F1's
+    largest error / bound: 0.0063 (profiles/policy.txt).  The eight cases at 76 and 116 inputs: F1 at most 0.00059 of the bound
+    (76_40_24-65rows-indexed-dense), B1 at most 0.128 of the tolerance (5.1e-5, w2 of 116_64_64-32rows-indexed-dense).  Every exact
+    case (E1, E2, E3) matched.
 B2  a call repeats bit for bit; sentinel-filled gradient arrays are overwritten; NaN in a feature row that only out-of-range
     entries could name changes nothing; no rows give zero gradients.
 B3  a tiny collected buffer -> policy(buf.features, index) -> ppo_loss -> loss.backward(), held link by link to the float64
     restatement of the chain: the logits and values within F1's bound, ppo_loss's gradients of them within ppo_loss_cases' tolerance
     of loss_f64 on those logits and values, and the parameter gradients within B1's bound of backward_f64 on those gradients.
-B4  after an in-place SGD step the next forward equals the reference on the NEW weights."""
+B4  after an in-place SGD step the next forward equals the reference on the NEW weights.
+E1  the exact cases (tests/policy_cases.py: integer weights, features and upstream gradients, every sum far below 2^24, so every
+    float32 evaluation IS the float64 reference): all seven outputs of every row equal the reference; out-of-range rows +0.0f.
+E2  their eight gradient arrays equal the reference; the float64 sum of the partials equals the gradients; the partial of workgroup
+    p equals the reference gradient of the rows policy.hpp's dealing gives p (the first workgroup and tensor that differ are named).
+E3  a three-pass exact call at 96 and at 116 inputs repeats bit for bit, ignores NaN in feature rows it does not name, and is the
+    sum of the calls on its rows [0, a) and [a, M)."""
 import ctypes
 import types
 
@@ -57,7 +65,7 @@ def _structs(c, a, dev, features=None, index=(), first=None, n_rows=None):
 
     keep = [placed(w, 4, dev) for w in a.weights]
     feats = placed(a.features if features is None else features, 16, dev)
-    index = a.index if index == () else index
+    index = a.index if isinstance(index, tuple) else index  # (() = the case's own)
     ix = placed(index, 4, dev)
     keep += [feats, ix]
     pol = _lib.OcActorCritic(*[t.data_ptr() for t in keep[:8]], c.in_dim, c.h1, c.h2)
@@ -66,39 +74,42 @@ def _structs(c, a, dev, features=None, index=(), first=None, n_rows=None):
     return pol, rows, keep
 
 
-def forward(c, a, dev, **kw):
+def forward(c, a, dev, fill=FILL, **kw):
     """One oc_policy_forward call: float32 [M, 7] (logits and value) as numpy"""
     from overcooked_ai_amd import _lib
 
     pol, rows, keep = _structs(c, a, dev, **kw)
     M = rows.n_rows
-    lg, g_lg = guarded(M, (6,), torch.float32, FILL, dev, before=1)
-    vl, g_vl = guarded(M, (), torch.float32, FILL, dev, before=GUARD)
+    lg, g_lg = guarded(M, (6,), torch.float32, fill, dev, before=1)
+    vl, g_vl = guarded(M, (), torch.float32, fill, dev, before=GUARD)
     assert lg.data_ptr() % 16 == 8 and vl.data_ptr() % 8 == 4
     L = _lib.load()
     rc = L.oc_policy_forward(ctypes.byref(pol), ctypes.byref(rows), lg.data_ptr(), vl.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     assert rc == 0, L.oc_last_error().decode()
     torch.cuda.synchronize(dev)
-    guards_untouched(c.id, "logits", g_lg, FILL)
-    guards_untouched(c.id, "values", g_vl, FILL)
+    guards_untouched(c.id, "logits", g_lg, fill)
+    guards_untouched(c.id, "values", g_vl, fill)
     return np.concatenate([lg.cpu().numpy(), vl.cpu().numpy()[:, None]], 1)
 
 
-def backward(c, a, dev, fill=FILL, features=None, n_rows=None):
-    """One oc_policy_backward call: (the eight gradient arrays, the partials) as numpy"""
+def backward(c, a, dev, fill=FILL, features=None, n_rows=None, lo=0, part_fill=FILL):
+    """One oc_policy_backward call: (the eight gradient arrays, the partials) as numpy.  lo, n_rows: the call is rows
+    [lo, lo + n_rows) of the case's: from first_row on (contiguous), a slice of the index (indexed); part_fill: the partials' sentinel"""
     from overcooked_ai_amd import _lib
     from overcooked_ai_amd.policy import partials_shape, shapes
 
-    pol, rows, keep = _structs(c, a, dev, features=features, n_rows=n_rows)
-    M = rows.n_rows
-    gl, gv = placed(a.grad_logits[:max(M, 1)], 8, dev), placed(a.grad_values[:max(M, 1)], 4, dev)
+    M = c.M - lo if n_rows is None else n_rows
+    index = () if a.index is None or not lo else a.index[lo:lo + max(M, 1)]
+    pol, rows, keep = _structs(c, a, dev, features=features, index=index, first=a.first + lo, n_rows=M)
+    assert rows.n_rows == M
+    gl, gv = placed(a.grad_logits[lo:lo + max(M, 1)], 8, dev), placed(a.grad_values[lo:lo + max(M, 1)], 4, dev)
     count, size = partials_shape(M, c.in_dim, c.h1, c.h2)
     grads, guards = [], []
     for shape in shapes(c.in_dim, c.h1, c.h2):
         t, g = guarded(shape[0], shape[1:], torch.float32, fill, dev, before=GUARD)
         grads.append(t)
         guards.append(g)
-    part, g_part = guarded(max(count, 1), (size,), torch.float32, FILL, dev, before=1)
+    part, g_part = guarded(max(count, 1), (size,), torch.float32, part_fill, dev, before=1)
     g = _lib.OcPolicyGrads(*[t.data_ptr() for t in grads])
     L = _lib.load()
     rc = L.oc_policy_backward(ctypes.byref(pol), ctypes.byref(rows), gl.data_ptr(), gv.data_ptr(), ctypes.byref(g), part.data_ptr(),
@@ -107,7 +118,7 @@ def backward(c, a, dev, fill=FILL, features=None, n_rows=None):
     torch.cuda.synchronize(dev)
     for name, gd in zip(PC.NAMES, guards):
         guards_untouched(c.id, "gradient of " + name, gd, fill)
-    guards_untouched(c.id, "partials", g_part, FILL)
+    guards_untouched(c.id, "partials", g_part, part_fill)
     return [t.cpu().numpy() for t in grads], part[:count].cpu().numpy()
 
 
@@ -129,7 +140,8 @@ def test_f1_every_output_is_within_its_bound_of_the_f64_reference(c, gpu):
 
 
 @pytest.mark.parametrize("tail", ("96_64_64-488rows-contiguous-dense", "96_33_17-257rows-contiguous-dense", "56_64_64-65rows-contiguous-dense",
-                                  "136_33_17-%drows-contiguous-zero_tiles" % PC.BIG_136))
+                                  "136_33_17-%drows-contiguous-zero_tiles" % PC.BIG_136, "76_64_64-257rows-contiguous-dense",
+                                  "116_64_64-65rows-contiguous-dense"))
 def test_f2_the_logits_are_oc_partner_logits_bit_for_bit(tail, gpu):
     from overcooked_ai_amd import _lib
     from overcooked_ai_amd.policy import ActorCritic
@@ -167,7 +179,8 @@ def test_f3_split_gathered_out_of_range_and_act(gpu):
     parts = [forward(c, a, gpu, first=a.first + lo, n_rows=hi - lo) for lo, hi in ((0, 200), (200, 488))]
     assert np.array_equal(bits(whole), bits(np.concatenate(parts)))
     # an indexed call = the contiguous call on the gathered rows; out-of-range rows are +0.0f by bit pattern
-    for tail in ("96_64_64-488rows-indexed-dense", "136_64_64-257rows-indexed-dense", "96_1_1-65rows-indexed-dense"):
+    for tail in ("96_64_64-488rows-indexed-dense", "136_64_64-257rows-indexed-dense", "96_1_1-65rows-indexed-dense", "76_40_24-65rows-indexed-dense",
+                 "116_33_17-257rows-indexed-dense"):
         c = case_named(tail)
         a = PC.arrays_of(c)
         got = forward(c, a, gpu)
@@ -223,6 +236,82 @@ def test_b2_repeatable_overwriting_isolated_and_zero_without_rows(gpu):
             assert np.array_equal(bits(forward(c, a, gpu)), bits(forward(c, a, gpu, features=dirty))), tail
     grads, partials = backward(c, a, gpu, n_rows=0)
     assert all(not bits(g).any() for g in grads) and partials.shape[0] == 0
+
+
+# ------------------------------------------------------------------------------------------ the exact cases
+EXACT = pytest.mark.parametrize("c", PC.EXACT_CASES, ids=lambda c: c.id)
+EXACT_FILL = PC.EXACT_FILL
+
+
+@EXACT
+def test_e1_every_output_of_an_exact_case_is_the_reference_s(c, gpu):
+    a = PC.exact_arrays_of(c)
+    ref, _ = PC.exact_reference_of(c)
+    got = forward(c, a, gpu, fill=EXACT_FILL)
+    assert not (got == EXACT_FILL).any()  # (every row written)
+    assert not bits(got[~a.valid]).any()  # out-of-range rows: +0.0f
+    wrong = np.flatnonzero((got.astype(np.float64) != ref).any(1) & a.valid)
+    assert wrong.size == 0, "%s: %d rows differ, the first %d (tile %d): %s, not %s" % (c.id, wrong.size, wrong[0], wrong[0] // 32, got[wrong[0]], ref[wrong[0]])
+
+
+def first_difference(c, got, ref):
+    """Words for the first element (in the layout's order) at which float32 [size] got differs from float64 [size] ref, or None"""
+    if np.array_equal(got.astype(np.float64), ref):
+        return None
+    for name, where in PC.layout_of(c).items():
+        at = np.flatnonzero(got[where].astype(np.float64) != ref[where])
+        if at.size:
+            return "%s: %d of %d elements differ, the first [%d]: %r, not %r" % (name, at.size, ref[where].size, at[0], float(got[where][at[0]]), float(ref[where][at[0]]))
+
+
+@EXACT
+def test_e2_every_gradient_and_partial_of_an_exact_case_is_the_reference_s(c, gpu):
+    a = PC.exact_arrays_of(c)
+    _, ref = PC.exact_reference_of(c)
+    grads, partials = backward(c, a, gpu, fill=EXACT_FILL, part_fill=EXACT_FILL)
+    grid, waves = PC.backward_plan_of(c)
+    assert partials.shape == (grid, len(PC.flat(ref.grads)))
+    # ---- the partial of workgroup p is the reference gradient of the rows dealt to p: tile = (pass * grid + p) * wavefronts + wavefront
+    want = PC.exact_partials_of(c)
+    for p in range(grid):
+        said = first_difference(c, partials[p], want[p])
+        if said:
+            owner = PC.owner_of_rows(c.M, grid, waves)
+            tiles = np.unique(np.flatnonzero(owner == p) // 32)
+            pytest.fail("%s: the partial of workgroup %d of %d (%d wavefronts; tiles %s) is not its rows' gradient: %s" % (c.id, p, grid, waves, tiles.tolist(), said))
+    # ---- the gradients are the partials' sum (in float64: exact whatever the order) and the reference
+    assert not (partials == EXACT_FILL).any()  # (no result is the sentinel: the comparison above has named an element left unwritten)
+    got = np.concatenate([g.reshape(-1) for g in grads])
+    total = partials.astype(np.float64).sum(0)
+    said = first_difference(c, got, total)
+    if said:
+        lost = [p for p in range(grid) if partials[p].any() and np.array_equal(got + partials[p].astype(np.float64), total)]
+        pytest.fail("%s: the gradients are not the sum of the %d partials (%s): %s" % (c.id, grid, "they are the sum without partial %s" % lost if lost else "no one partial is missing", said))
+    assert not (got == EXACT_FILL).any()
+    for name, g, r in zip(PC.NAMES, grads, ref.grads):
+        assert np.array_equal(g.astype(np.float64).reshape(r.shape), r), (c.id, name)
+
+
+@pytest.mark.parametrize("tail", ("96_64_64-%drows-contiguous-three_pass" % PC.three_passes(96), "116_64_64-%drows-indexed-three_pass" % PC.three_passes(116)))
+def test_e3_exact_three_pass_calls_repeat_ignore_unnamed_rows_and_split(tail, gpu):
+    c = PC.exact_named(tail)
+    a = PC.exact_arrays_of(c)
+    _, ref = PC.exact_reference_of(c)
+    run = lambda **kw: backward(c, a, gpu, fill=EXACT_FILL, part_fill=EXACT_FILL, **kw)  # noqa: E731
+    whole = run()
+    assert same(whole, run()), tail  # a call repeats bit for bit
+    # NaN in the feature rows no row of the call names: the one no in-range entry has (indexed), those around first .. first + M (contiguous)
+    dirty = a.features.copy()
+    unnamed = np.setdiff1d(np.arange(len(dirty)), a.rows[a.valid])
+    assert (a.nan_row in unnamed if a.index is not None else len(unnamed) == a.first + 5)
+    dirty[unnamed] = np.nan
+    assert same(whole, run(features=dirty)), tail
+    # rows [0, cut) + rows [cut, M), the cut inside a tile of the second pass: other tiles, other workgroups, the same sums
+    cut = PC.one_pass(c.in_dim) + 45
+    lower, upper = run(n_rows=cut), run(lo=cut)
+    for name, w, p, q, r in zip(PC.NAMES, whole[0], lower[0], upper[0], ref.grads):
+        assert np.array_equal(p.astype(np.float64) + q, w) and np.array_equal(w.astype(np.float64).reshape(r.shape), r), (tail, name)
+        assert p.any() and q.any(), (tail, name)
 
 
 def _policy_and_reference_weights(policy):

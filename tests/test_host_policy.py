@@ -1,7 +1,8 @@
 """oc_policy_forward / oc_policy_backward without a GPU: the exports and the structs against the header, the plan's words and their
 numbers, every refusal (made before any device call: this host has no device), the references of tests/policy_cases.py against
-each other and against torch autograd in float64, the share of rows a case had to silence, the recorded float32 error, and
-ActorCritic's own refusals."""
+each other and against torch autograd in float64, the share of rows a case had to silence, the recorded float32 error, the
+exact cases (their precondition, their premise in two float32 orders of summation, that they bite, the dealing rule of the partials),
+the backward plan of every feature length, and ActorCritic's own refusals."""
 import ctypes
 import os
 import re
@@ -152,7 +153,7 @@ def test_the_entry_points_refuse_before_any_device_call():
 
 # ------------------------------------------------------------------------------------------ the references
 def test_the_forward_reference_is_the_partners_with_a_value_column():
-    c = PC.CASES[-3]
+    c = next(c for c in PC.CASES if c.id == "136_33_17-%drows-contiguous-zero_tiles" % PC.BIG_136)
     a = PC.arrays_of(c)
     x = a.features
     six = a.weights[:6]
@@ -229,7 +230,12 @@ def test_the_case_list_covers_what_it_must():
     assert sizes >= {1, 31, 32, 33, 64, 65, 257, 488, PC.BIG}
     for M in PC.SIZES:
         assert {c.mode for c in cases if c.M == M and (c.in_dim, c.h1, c.h2) == (96, 64, 64)} >= {"contiguous", "indexed"}
-    assert {(c.h1, c.h2) for c in cases} >= {(64, 64), (1, 1), (33, 17)} and {c.in_dim for c in cases} == {56, 96, 136}
+    assert {(c.h1, c.h2) for c in cases} >= {(64, 64), (1, 1), (33, 17)} and {c.in_dim for c in cases} == {56, 76, 96, 116, 136}
+    for in_dim in (76, 116):
+        assert {c.mode for c in cases if c.in_dim == in_dim} == {"contiguous", "indexed"}, in_dim
+    for c in cases:
+        rc, text = PC.plan(c.M, c.mode == "indexed", c.in_dim, c.h1, c.h2, 1)
+        assert rc == 0 and ("k_policy_backward<F0=3" in text) == (c.in_dim in (116, 136)), (c.id, text)
     assert {c.pattern for c in cases} == {"dense", "zero_tiles", "at_zero"}
     for c in cases:
         a = PC.arrays_of(c)
@@ -253,6 +259,158 @@ def test_the_case_list_covers_what_it_must():
             assert not pre1.any() and not pre2.any() and not a.unstable[zero].any()
             only = PC._backward(xs[zero], a.weights, up[zero], np.float64).grads
             assert not any(g.any() for g in only[:5]) and not only[6].any() and only[5].any() and only[7].any()
+
+
+# ------------------------------------------------------------------------------------------ the exact cases
+EXACT = pytest.mark.parametrize("c", PC.EXACT_CASES, ids=lambda c: c.id)
+
+
+def test_the_exact_case_list_covers_what_it_must():
+    cases = PC.EXACT_CASES
+    small = [c for c in cases if c.kind == "small"]
+    assert {(c.in_dim, c.M) for c in small} == {(d, M) for d in (56, 76, 96, 116, 136) for M in (1, 33, 257)} and len(small) == 15
+    for in_dim in (56, 76, 96, 116, 136):
+        mine = [c for c in small if c.in_dim == in_dim]
+        assert {c.mode for c in mine} == {"contiguous", "indexed"} and any(c.h1 < 64 and c.h2 < 64 for c in mine), in_dim
+    assert {(c.h1, c.h2) for c in small} == set(PC.EXACT_WIDTHS)
+    three = [c for c in cases if c.kind == "three_pass"]
+    assert [(c.in_dim, c.h1, c.h2, c.mode) for c in three] == [(96, 64, 64, "indexed"), (96, 64, 64, "contiguous"), (116, 64, 64, "indexed"),
+                                                             (136, 33, 17, "contiguous"), (76, 40, 24, "indexed")]
+    assert [c.M for c in three] == [65825, 65825, 65825, 49377, 65825]
+    for c in three:
+        # the third pass: two full workgroups, one full tile more, and a tile of ONE row
+        grid, waves = PC.backward_plan_of(c)
+        assert grid == 256 and c.M == 2 * PC.one_pass(c.in_dim) + 2 * 32 * waves + 33
+        owner = PC.owner_of_rows(c.M, grid, waves)
+        third = owner[2 * PC.one_pass(c.in_dim):]
+        assert np.array_equal(np.unique(third), [0, 1, 2]) and (third == 2).sum() == 33 and (np.bincount(owner)[3:] == 2 * 32 * waves).all()
+    for c in cases:
+        a = PC.exact_arrays_of(c)
+        assert not a.unstable.any()
+        if c.mode == "contiguous":
+            assert a.first == PC.FIRST and a.index is None and a.valid.all() and len(a.features) == a.first + c.M + 5
+        else:
+            inside = a.rows[a.valid]
+            assert len(a.features) == PC.EXACT_ROWS and (~a.valid).sum() == c.M // 16 and a.nan_row not in inside and a.valid[-1], c.id
+            assert not PC.upstream(a)[~a.valid].any() and (c.M < 16 or np.concatenate([a.grad_logits, a.grad_values[:, None]], 1)[~a.valid].any())
+
+
+def test_the_owner_of_a_row_is_the_kernels_dealing():
+    """tile = (pass * grid + workgroup) * wavefronts + wavefront, written out as the loops of k_policy_backward"""
+    for M, grid, waves in ((1, 1, 4), (33, 1, 4), (257, 3, 3), (2 * 5 * 3 * 32 + 100, 5, 3), (3 * 7 * 4 * 32 - 31, 7, 4)):
+        want = np.full(M, -1, np.int64)
+        n_tiles = (M + 31) // 32
+        for block in range(grid):
+            for wave in range(waves):
+                for t in range(block * waves + wave, n_tiles, grid * waves):
+                    want[32 * t:32 * (t + 1)] = block
+        assert np.array_equal(PC.owner_of_rows(M, grid, waves), want), (M, grid, waves)
+
+
+@EXACT
+def test_the_precondition_of_exactness(c):
+    """Integer inputs, and no sum of absolute values of the terms of any sum reaches 2^24: a condition on the reference alone"""
+    a = PC.exact_arrays_of(c)
+    for t in a.weights + (a.features, a.grad_logits, a.grad_values):
+        assert t.dtype == np.float32 and np.array_equal(t, np.rint(t)), c.id
+    assert all(np.abs(w).max() <= 1 for w in a.weights) and np.abs(a.features).max() <= 6 and np.abs(a.grad_logits).max() <= 1
+    sums = PC.exact_sums(c)
+    assert set(sums) == {"pre1", "pre2", "out", "delta2", "delta1"} | {"g" + n for n in PC.NAMES}
+    print("%s: largest sum of |terms| %.6g (%s) of 2^24 = %d; %s" % (c.id, max(sums.values()), max(sums, key=sums.get), 2 ** 24,
+                                                                    ", ".join("%s %.6g" % kv for kv in sums.items())))
+    assert max(sums.values()) < 2 ** 24, (c.id, sums)
+
+
+def _f32_other_order(a):
+    """(out [M, 7], the eight gradients) in float32 in ANOTHER order of summation than np.matmul's: every K loop descending (the
+    operands flipped along K), the rows of the call in four interleaved groups added last group first"""
+    f = np.float32
+    w1, b1, w2, b2, w3, b3 = PC.head(a.weights)
+    x, d3 = PC.rows_of(a), PC.upstream(a)
+    dot = lambda p, q: np.matmul(np.ascontiguousarray(p[:, ::-1]), np.ascontiguousarray(q[::-1]))  # noqa: E731
+    pre1 = dot(x, w1) + b1
+    a1 = np.maximum(pre1, f(0))
+    pre2 = dot(a1, w2) + b2
+    a2 = np.maximum(pre2, f(0))
+    out = dot(a2, w3) + b3
+    d2 = np.where(pre2 > 0, dot(d3, w3.T), f(0))
+    d1 = np.where(pre1 > 0, dot(d2, w2.T), f(0))
+    total = None
+    for k in (3, 2, 1, 0):
+        r = slice(k, None, 4)
+        g3 = dot(a2[r].T, d3[r])
+        part = [dot(x[r].T, d1[r]), d1[r][::-1].sum(0), dot(a1[r].T, d2[r]), d2[r][::-1].sum(0), g3[:, :6], d3[r][::-1, :6].sum(0), g3[:, 6], d3[r][::-1, 6:].sum(0)]
+        assert all(p.dtype == f for p in part)
+        total = part if total is None else [t + p for t, p in zip(total, part)]
+    assert out.dtype == f and all(t.dtype == f for t in total)
+    return np.where(a.valid[:, None], out, f(0)), total
+
+
+@EXACT
+def test_the_premise_any_f32_evaluation_of_an_exact_case_is_the_f64_reference(c):
+    a = PC.exact_arrays_of(c)
+    out, ref = PC.exact_reference_of(c)
+    xs = PC.rows_of(a)
+    f32 = PC._backward(xs, a.weights, PC.upstream(a), np.float32)
+    out32 = np.where(a.valid[:, None], PTC.mlp_f32(xs, PC.head(a.weights)), np.float32(0))
+    out_other, grads_other = _f32_other_order(a)
+    assert out32.dtype == np.float32 and np.array_equal(out32, out) and np.array_equal(out_other, out), c.id
+    for name, g64, g32, other in zip(PC.NAMES, ref.grads, f32.grads, grads_other):
+        assert g32.dtype == np.float32 and np.array_equal(g32, g64) and np.array_equal(other.reshape(g64.shape), g64), (c.id, name)
+    # the reference's own pieces agree: the flat layout, the sum of the workgroups' partials
+    flat = PC.flat_grads(PC.exact_terms_of(c))
+    lay = PC.layout_of(c)
+    assert all(np.array_equal(flat[lay[n]], g.reshape(-1)) for n, g in zip(PC.NAMES, ref.grads)) and np.array_equal(flat, PC.flat(ref.grads))
+    partials = PC.exact_partials_of(c)
+    assert partials.shape == (PC.backward_plan_of(c)[0], len(flat)) and np.array_equal(partials.sum(0), flat)
+    # every result is an integer, so none holds the exact cases' sentinel (FILL itself is one: -7 is a logit of these cases)
+    assert np.array_equal(out, np.rint(out)) and np.array_equal(partials, np.rint(partials)) and PC.EXACT_FILL != np.rint(PC.EXACT_FILL)
+
+
+@pytest.mark.parametrize("c", [c for c in PC.EXACT_CASES if c.kind == "small"], ids=lambda c: c.id)
+def test_the_exact_reference_gradients_are_torch_autograd_s(c):
+    a = PC.exact_arrays_of(c)
+    _, ref = PC.exact_reference_of(c)
+    for name, mine, theirs in zip(PC.NAMES, ref.grads, _torch_autograd(a)):
+        assert np.array_equal(mine.reshape(theirs.shape), theirs), (c.id, name)  # (integers in float64: exactly)
+
+
+@EXACT
+def test_the_exact_cases_bite(c):
+    a = PC.exact_arrays_of(c)
+    assert PC.exact_misses(c, a) == [], c.id
+    t = PC.exact_terms_of(c)
+    pre = np.concatenate([t.pre1[a.valid].reshape(-1), t.pre2[a.valid].reshape(-1)])
+    live = a.valid & PC.upstream(a).any(1)
+    at_zero = ((t.pre1 == 0).any(1) | (t.pre2 == 0).any(1)) & live
+    print("%s: %.3f of the hidden pre-activations positive, %.3f exactly 0, %d live rows with one at 0" % (c.id, (pre > 0).mean(), (pre == 0).mean(), at_zero.sum()))
+    assert 0.3 <= (pre > 0).mean() <= 0.7 and at_zero.any()
+    _, ref = PC.exact_reference_of(c)
+    assert all(g.any() for g in ref.grads), c.id
+    if c.kind == "three_pass":
+        lay = PC.layout_of(c)
+        third, last = PC.flat_grads(t, slice(2 * PC.one_pass(c.in_dim), None)), PC.flat_grads(t, slice(c.M - 1, None))
+        assert all(third[lay[n]].any() and last[lay[n]].any() for n in PC.NAMES), c.id
+        # a pass, a workgroup's share of it or the last row left out is another answer
+        owner = PC.owner_of_rows(c.M, *PC.backward_plan_of(c))
+        assert all(PC.flat_grads(t, np.flatnonzero(owner == p)).any() for p in (0, 1, 2, 255))
+
+
+def test_the_backward_plan_of_every_feature_length():
+    """Lanes and LDS bytes as oc_policy_plan states them: four wavefronts wherever their images fit 160 KB, which leaves out 136
+    inputs alone (116 inputs: 832 bytes to spare)."""
+    table = {56: (256, 120320, 2, None), 76: (256, 132416, 3, None), 96: (256, 147456, 3, None), 116: (256, 163008, 3, 1), 136: (192, 151456, 3, 2)}
+    for in_dim, (lanes, lds, nf, more) in table.items():
+        rc, text = PC.plan(2 ** 20, 1, in_dim, 64, 64, 1)
+        n = PC.plan_numbers(text)
+        assert rc == 0 and (n["lanes"], n["lds"], n["grid"]) == (lanes, lds, 256) and lds <= LDS_MAX, (in_dim, text)
+        assert "k_policy_backward<F0=0,NF=%d,REST>" % nf in text and "%d wavefronts x 32-row tiles" % (lanes // 64) in text
+        assert ("k_policy_backward<F0=3,NF=%s>" % more in text) if more else ("F0=3" not in text), text
+        assert PC.one_pass(in_dim) == 256 * 32 * (lanes // 64) and PC.per_pass(in_dim) == 32 * (lanes // 64)
+    with open(os.path.join(ROOT, "overcooked_ai_amd", "csrc", "policy.hpp")) as f:
+        src = f.read()
+    assert "else three (136 inputs)" in src and "else three (116 and 136 inputs)" not in src
+    assert "With 136 inputs a backward workgroup has three wavefronts" in _header()
 
 
 # ------------------------------------------------------------------------------------------ the Python surface
