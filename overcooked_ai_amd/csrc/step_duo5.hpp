@@ -186,6 +186,16 @@ constexpr bool R5_FAST_START = false;
 #else
 constexpr bool R5_FAST_START = true;
 #endif
+#ifdef OC_R5_NORARE  // (timing-only builds: the rare branch and its test compiled out of dstep — WRONG results; what the step costs without them)
+constexpr bool R5_RARE = false;
+#else
+constexpr bool R5_RARE = true;
+#endif
+// The straight line of dstep sets nothing that only the rare body changes (docs/NOTEBOOK.md, "what the rare branch costs the
+// straight line"): the lower half of the reward quad is a loop-carried register pair of zeros that only the branch writes, and the
+// one-slot instances keep cook_u + k8 in eight registers.  A lane that leaves delivery rewards in the pair sets REC5_FORCE in the
+// flag word it hands to the next step, enters that step's branch whatever else happens there, and writes the pair again.
+constexpr uint32_t REC5_FORCE = 1u;  // a bit of f_rec no mover sets and no entry's .z holds (byte 0 of .z = 16 x class)
 template <bool LAY_LDS, bool FT8, bool OLD = false, bool BIG = false, bool EV = false, bool NOOUT = false, int MAXP = 2>
 __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_rollout5(
     const OcLayout* __restrict__ g_layouts, int n_layouts, const uint16_t* layout_id, uint4* st, float4* __restrict__ rewards,
@@ -358,6 +368,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
     // no soup object without ingredients in its pot (exotic) loads the countdown of a start in the straight line and leaves START out
     // of its gate (start_gate 0); every other lane keeps START in its gate and takes the rare branch
     uint32_t cook_u = 0, start_gate = Z5_START_A;
+    uint32_t cook_k[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // FAST: cook_u + k8, in registers — it changes where cook_u does, at a restart on a re-drawn layout
     int32_t F = 0;  // EV: pots that are full (three idle items, cooking or ready), kept by the entries' deltas like N
     static_assert(!EV || !BIG, "the counters' row 0 is the spare cell row in front of them: 4-byte cell words");
     const uint32_t cnt0 = dummy;  // EV: this lane's column of event counters, [row][BLOCK] u32: row 0 = the spare cell word, rows 1.. behind it
@@ -436,6 +447,10 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
         }
         N = 64 * dishes - useful;
         if (FAST) { cook_u = r5_uniform_cook(C); start_gate = r5_start_gate(cook_u, exotic); }
+        if (FAST) {
+#pragma unroll
+            for (int k8 = 0; k8 < 8; ++k8) cook_k[k8] = cook_u + (uint32_t)k8;
+        }
     }
     float4 ep = ep_returns ? ep_returns[e] : make_float4(0.f, 0.f, 0.f, 0.f);
     typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -488,6 +503,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
     c0 = CW::rd(fo0);
     c1 = CW::rd(fo1);
     Pend pend = {0ull, 0ull};
+    uint64_t zpair = 0ull;  // the quad's lower half: zeros, but for a lane whose last entry into the rare branch left its delivery rewards
     // One step.  k8: its index in the block; (next_buf, next_k): the mover's record of the next step.
     auto dstep = [&](int k8, uint32_t next_buf, uint32_t next_k) __attribute__((always_inline)) {
         const uint4 e0 = lds_rd128(entry_at(c0, hz0));
@@ -508,6 +524,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
 #pragma unroll
         for (int k = 0; k < MAXP; ++k) CW::wr_key(ripe[k] ? pa[k] : dummy, pot_type5(k), PC_READY);
         uint32_t nc0 = CW::rd(nrec.x), nc1 = CW::rd(nrec.y);  // the next step's cells: everything this step writes has been issued
+        uint32_t nf = nrec.z;  // the next step's flag word (the rare body may add REC5_FORCE)
         const int32_t N_mid = N + sext_b1(e0.y);
         int32_t N_new = N_mid + sext_b1(e1.y);
         int32_t late_now = 0;  // OLD: pots that arrived idle and full count as useful from the step after their first one on
@@ -518,12 +535,11 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
         const uint32_t gate = ((uint32_t)(N | N_mid) & Z5_TAKE) | Z5_SERVE | (FAST ? start_gate : Z5_START_A) | (MAXP > 1 ? Z5_START_B : 0u) |
                               (EV ? Z5_PLACE : 0u);
         uint32_t c1_seen = c1;  // EV: the cell word player 1's interact saw (player 0's result when it redoes it)
-        const uint32_t rare_bits = ((e0.z | e1.z) & gate) | ((e0.z | REC5_DONE) & f_rec);
-        uint64_t q_lo, q_hi;  // the reward quad as two register pairs: zeros, and the two entries' shaped floats
+        const uint32_t rare_bits = ((e0.z | e1.z) & gate) | ((e0.z | REC5_DONE | REC5_FORCE) & f_rec);
+        uint64_t q_lo = zpair, q_hi;  // the reward quad as two register pairs: zeros (no instruction), and the two entries' shaped floats
         {
             const uint64_t a64 = ((uint64_t)e0.w << 32) | e0.z, b64 = ((uint64_t)e1.w << 32) | e1.z;
             asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,1]" : "=v"(q_hi) : "v"(a64), "v"(b64));
-            asm("v_mov_b64 %0, 0" : "=v"(q_lo));
         }
         uint32_t nh0 = r0, nh1 = r1, nz0 = e0.z, nz1 = e1.z;
         int32_t F_reset = -1;  // EV: the full pots of a new episode's start state
@@ -533,14 +549,15 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
         // (no usable cook_u: every START of theirs enters the branch), a shared-cell replay of player 1's interact (which may add a
         // start or drop a stale one: the entries that finally count decide), a restart (the new episode's countdown stands)
         const uint32_t rem_was = rem[0];
+        const uint32_t cook_at = cook_k[k8];  // FAST: the countdown of a pot that starts in this step (no add here)
         if (FAST) {
             // (written out: the compiler makes an and, a compare, an add and a select of the C form)
             static_assert(Z5_START_A == 1u << 19, "the START flag's bit");
             uint32_t m;
             asm("v_bfe_i32 %1, %2, 19, 1\n\tv_bfi_b32 %0, %1, %3, %4"
-                : "=v"(rem[0]), "=&v"(m) : "v"(e0.z | e1.z), "v"(cook_u + (uint32_t)k8), "v"(rem_was));
+                : "=v"(rem[0]), "=&v"(m) : "v"(e0.z | e1.z), "v"(cook_at), "v"(rem_was));
         }
-        if (__builtin_expect(rare_bits != 0u, 0)) {
+        if (R5_RARE && __builtin_expect(rare_bits != 0u, 0)) {
             bool grid_changed = false;
             const uint32_t hb0 = CW::hand(h0), hb1 = CW::hand(h1), hn0 = CW::hand(r0);
             if (e0.z & f_rec & Z5_CHG) {  // player 1 acts on the cell player 0 has just changed: redo its interact on what is there now (Q2 / Q3)
@@ -553,7 +570,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
                 grid_changed = true;
             }
             const uint32_t fz = e0.z | e1.z;
-            if (FAST) rem[0] = (start_gate == 0u && (fz & Z5_START_A)) ? cook_u + (uint32_t)k8 : rem_was;  // (behind the replay)
+            if (FAST) rem[0] = (start_gate == 0u && (fz & Z5_START_A)) ? cook_at : rem_was;  // (behind the replay)
             // begin_cooking (mdp.py:1515-1522) = load the countdown: tick 0 now, cooked once by this step's env effects (Q4)
 #pragma unroll
             for (int k = 0; k < MAXP; ++k) {
@@ -584,6 +601,8 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
                 if (fz & Z5_SERVE) {  // deliver_soup (mdp.py:1631-1642)
                     r.x = (e0.z & Z5_SERVE) ? L.value(recipe_idx(hb0) & 15u) : 0.f;
                     r.y = (e1.z & Z5_SERVE) ? L.value(recipe_idx(hb1) & 15u) : 0.f;
+                    // (the quad's lower half stays in zpair until this lane's next entry: the next step's, then)
+                    nf |= ((__float_as_uint(r.x) | __float_as_uint(r.y)) != 0u) ? REC5_FORCE : 0u;
                 }
                 ep.x += r.x; ep.y += r.y;
                 rw.x = r.x; rw.y = r.y; rw.z += r.z; rw.w += r.w;
@@ -619,6 +638,10 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
                             C = load_consts<false>(L);
                             pot_addrs();
                             if (FAST) cook_u = r5_uniform_cook(C);
+                            if (FAST) {
+#pragma unroll
+                                for (int j = 0; j < 8; ++j) cook_k[j] = cook_u + (uint32_t)j;
+                            }
                         }
                         d = draw_start(L, g, sa.epoch + step_k, sa.seed_lo, sa.seed_hi, sa.random_start_pos, sa.thresh);
                     }
@@ -656,6 +679,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
             }
             q_lo = ((uint64_t)__float_as_uint(rw.y) << 32) | __float_as_uint(rw.x);
             q_hi = ((uint64_t)__float_as_uint(rw.w) << 32) | __float_as_uint(rw.z);
+            zpair = q_lo;  // (zeros again, unless this step delivers)
             // (wait for the reads in here: left pending, the join behind the branch would wait for them at its first LDS use)
             __builtin_amdgcn_s_waitcnt(0xC07F);
         }
@@ -691,7 +715,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)
         if (k8 < 7) { pend.lo = q_lo; pend.hi = q_hi; }
         else { const Pend now = {q_lo, q_hi}; flush(now, 7); }
         h0 = nh0; h1 = nh1; hz0 = nz0; hz1 = nz1; N = N_new - late_now;
-        fo0 = nrec.x; fo1 = nrec.y; f_rec = nrec.z; c0 = nc0; c1 = nc1;
+        fo0 = nrec.x; fo1 = nrec.y; f_rec = nf; c0 = nc0; c1 = nc1;
         step_k += 1u;
     };
     uint32_t rbuf = 0;  // (wave-uniform) offset of the ring buffer that holds the block being run
