@@ -1514,6 +1514,87 @@ int oc_bc_epoch_fused(const OcActorCritic* policy, const OcBcLoss* loss, const O
  */
 int oc_bc_epoch_fused_plan(int64_t n_index, int64_t minibatch, int in_dim, int h1, int h2, int with_class_weights, char* out, size_t out_size);
 
+/*
+ * The learner's sample index (ABI 6: entry points added beside the others; no existing signature, struct or option changes, so the
+ * version stays) — the d_index of oc_ppo_update and oc_bc_update, made on the device (csrc/sample_index.hpp): first the samples of a
+ * collected batch that the loss uses, then a permutation of them that is a stated function of (seed, epoch), like every other random
+ * stream of the library.  With a behaviour-cloning partner about half of a batch's samples are the partner's: oc_ppo_loss leaves
+ * them out, but a minibatch cut from a permutation of all S samples still carries them through the policy's forward and backward
+ * pass, and its count of learner samples is about half its size.  A minibatch cut from this index holds learner samples only, as the
+ * reference's train batch does, whose sgd_minibatch_size counts learner samples.
+ *
+ * Selection.  Sample s of 0 .. S - 1 (s = (t * n_envs + e) * 2 + p, as for OcPpoLoss) is selected when both hold:
+ *   d_seat == NULL or d_seat[s >> 1] != (s & 1)        (not the partner's sample)
+ *   d_actions == NULL or d_actions[s] <= 5             (not the sampler's invalid row)
+ * — oc_ppo_loss's left-out rules without the one on the index range.  With L the number of selected samples, d_ids[0 .. L) holds
+ * them in ascending order, d_ids[L .. S) holds -1 and *d_count = L.
+ *
+ * Permutation.  d_index[i] = d_ids[pi(i)] for i < min(L, n_out) and -1 for L <= i < n_out, with L = *d_count READ ON THE DEVICE (the
+ * host need not know it) and pi a bijection of 0 .. L - 1, in u32 arithmetic that wraps:
+ *   keys: for j = 0, 1:  k[4j .. 4j+3] = philox4x32_10(counter = {epoch_lo, epoch_hi, j, 0}, key = {seed_lo, seed_hi ^ 0x53485546})
+ *         ("SHUF"): eight round keys, the same for every i
+ *   L <= 1:  pi(0) = 0
+ *   otherwise:  w = max(1, bit length of L - 1),  a = w >> 1,  c = w - a
+ *     mix(v):  v *= 0x9E3779B1;  v ^= v >> 16;  v *= 0x85EBCA6B;  v ^= v >> 13
+ *     top(v, q) = q ? v >> (32 - q) : 0
+ *     x = i;  repeat {  l = x >> c,  r = x & (2^c - 1);
+ *                       for j = 0 .. 7:  even j:  l ^= top(mix(r + k[j]), a),   odd j:  r ^= top(mix(l + k[j]), c);
+ *                       x = (l << c) | r  }  until x < L;   pi(i) = x
+ * Each of the eight rounds changes one half by a function of the other, so together they are a bijection of 0 .. 2^w - 1, and
+ * 2^w < 2 L.  The repeat ("cycle walking") follows that bijection's cycle from a point below L until it is below L again: it ends
+ * by construction (the cycle returns to i), pi is a bijection of 0 .. L - 1, and it evaluates the rounds fewer than 2 times per
+ * element on average.  Every lane walks alone: nothing waits for another lane.  It is a shuffle for SGD, not a cipher: nothing
+ * here is meant to withstand someone who wants to predict it.
+ * No atomics in either call: the same call on the same inputs gives the same bytes.
+ */
+
+/*
+ * oc_sample_select — three launches on the caller's stream, in none of which a workgroup waits for another (no look-back, no spin
+ * flags): k_sample_count writes the number of selected samples of every block of P = 1024 consecutive samples (a wavefront's count
+ * is the popcount of a __ballot), k_sample_scan, one workgroup, turns the counts into exclusive offsets and writes *d_count,
+ * k_sample_write evaluates the rule again, ranks a sample inside its block (ballot prefix, an LDS prefix across wavefronts) and
+ * stores it at the block's offset; position s >= L gets its -1 from the lane of sample s.  n_samples == 0 launches only what sets
+ * *d_count = 0.
+ *   n_samples        S, 0 .. 2^31 - 1; even when d_seat is given
+ *   d_seat           [S / 2] u8: the partner's player of (t, e), else no partner; any address; NULL = no partner anywhere
+ *   d_actions        [S] u8; any address; NULL = every action valid
+ *   d_ids            [S] i32 out; 4-byte aligned; required
+ *   d_count          [1] i64 out; 8-byte aligned; required
+ *   d_block_offsets  [max(1, ceil(S / P))] u32 scratch (oc_sample_index_plan states its bytes); 4-byte aligned; required
+ * OC_EINVAL, before any device call, with this entry point's name in front of the message: a NULL d_ids, d_count or
+ * d_block_offsets; a misaligned one; n_samples < 0 or >= 2^31; an odd n_samples with d_seat.
+ */
+int oc_sample_select(int64_t n_samples, const uint8_t* d_seat, const uint8_t* d_actions, int32_t* d_ids, int64_t* d_count,
+                     uint32_t* d_block_offsets, void* stream);
+
+/*
+ * oc_sample_permute — one launch (k_sample_permute): one lane per output, at most 1024 workgroups, outputs beyond them by grid
+ * stride.  n_out == 0 launches nothing.
+ *   d_ids    [>= *d_count] i32: oc_sample_select's; 4-byte aligned; NULL = the identity (ids[j] = j): a plain permutation of
+ *            0 .. L - 1, for a learner whose every sample counts (oc_bc_update)
+ *   d_count  [1] i64: L, 0 .. 2^31 - 1, read on the device; 8-byte aligned; required
+ *   n_out    how many entries of d_index to write, 0 .. 2^31 - 1: L where the host knows it; S without reading L back, the
+ *            entries from L on are then -1, which oc_ppo_loss and the policy's passes leave out
+ *   seed, epoch   the stream's key and counter, all 64 bits of both
+ *   d_index  [n_out] i32 out; 4-byte aligned; required
+ * OC_EINVAL, before any device call, with this entry point's name in front of the message: a NULL d_count or d_index; a misaligned
+ * d_ids, d_count or d_index; n_out < 0 or >= 2^31.
+ */
+int oc_sample_permute(const int32_t* d_ids, const int64_t* d_count, int64_t n_out, uint64_t seed, uint64_t epoch, int32_t* d_index,
+                      void* stream);
+
+/*
+ * oc_sample_index_plan — what the two calls would launch, as text (with_seat, with_actions, with_ids: the optional array is
+ * given; n_learner: L, for the permutation's w, a and c):
+ *   "select: k_sample_count<SEAT=true, ACT=true> grid=51200, 256 lanes + k_sample_scan grid=1, 256 lanes, 200 pass(es) of 256 blocks, 8 passes in flight + k_sample_write<SEAT=true, ACT=true> grid=51200, 256 lanes; P = 1024 samples per block, scratch 204800 B; permute: k_sample_permute<IDS=true> grid=1024, 256 lanes (one per output, 100 output(s) per lane at most); L = 26214400: w = 25, a = 12, c = 13"
+ *   "select: k_sample_scan grid=1, 256 lanes, 0 pass(es) (no samples: *d_count = 0); P = 1024 samples per block, scratch 4 B; permute: nothing to launch (no output); L = 0: w = 1, a = 0, c = 1"
+ * Usable without a GPU, like the other plan calls.  The checks that need no array apply, under the name of the call they belong
+ * to; n_learner outside 0 .. 2^31 - 1 is refused under this call's name.
+ *   out, out_size caller's text buffer (>= 640 bytes holds every answer)
+ */
+int oc_sample_index_plan(int64_t n_samples, int with_seat, int with_actions, int with_ids, int64_t n_out, int64_t n_learner, char* out,
+                         size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,8 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_sample_actions", "oc_multi_agent_step_sample", "oc_multi_agent_step_sample_plan",
            "oc_partner_logits", "oc_partner_logits_plan", "oc_gae", "oc_gae_plan", "oc_ppo_loss", "oc_ppo_loss_plan",
            "oc_policy_forward", "oc_policy_backward", "oc_policy_plan", "oc_adam_step", "oc_adam_plan", "oc_ppo_update", "oc_ppo_update_plan",
-           "oc_bc_loss", "oc_bc_loss_plan", "oc_bc_update", "oc_bc_update_plan", "oc_bc_epoch_fused", "oc_bc_epoch_fused_plan")
+           "oc_bc_loss", "oc_bc_loss_plan", "oc_bc_update", "oc_bc_update_plan", "oc_bc_epoch_fused", "oc_bc_epoch_fused_plan",
+           "oc_sample_select", "oc_sample_permute", "oc_sample_index_plan")
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
 
 
@@ -306,6 +307,12 @@ def load():
     L.oc_bc_epoch_fused.argtypes = [acp, bcp, adp, ctypes.POINTER(OcBcEpochFused), vp]
     L.oc_bc_epoch_fused_plan.restype = i32
     L.oc_bc_epoch_fused_plan.argtypes = [i64, i64, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.oc_sample_select.restype = i32
+    L.oc_sample_select.argtypes = [i64, vp, vp, vp, vp, vp, vp]
+    L.oc_sample_permute.restype = i32
+    L.oc_sample_permute.argtypes = [vp, vp, i64, u64, u64, vp, vp]
+    L.oc_sample_index_plan.restype = i32
+    L.oc_sample_index_plan.argtypes = [i64, i32, i32, i32, i64, i64, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

@@ -6,7 +6,8 @@
 // The OC_R4_PART == 2 unit, the shortest of the four, also compiles partner.hpp (k_partner_logits and its two entry points) and
 // gae.hpp (k_gae, k_gae_moments and theirs), ppo_loss.hpp (k_ppo_loss, k_ppo_loss_stats and theirs) and policy.hpp (k_policy_forward,
 // k_policy_backward, k_policy_grad_sum and theirs), adam.hpp (k_adam_step and its two), bc_loss.hpp (k_bc_loss, k_bc_loss_stats and theirs),
-// update_chain.hpp (host code only: oc_ppo_update and oc_bc_update) and bc_fused.hpp (k_bc_epoch_fused and its two).
+// update_chain.hpp (host code only: oc_ppo_update and oc_bc_update), bc_fused.hpp (k_bc_epoch_fused and its two) and sample_index.hpp (k_sample_count, k_sample_scan, k_sample_write,
+// k_sample_permute and their three).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -177,4 +178,5 @@ template void describe_rollout<OC_R4_PART>(const Rollout4Call& c, char* out, siz
 #include "bc_loss.hpp"  // k_bc_loss, k_bc_loss_stats, oc_bc_loss, oc_bc_loss_plan
 #include "update_chain.hpp"  // oc_ppo_update, oc_bc_update and their plans (host code: the launches of the files above, minibatch after minibatch)
 #include "bc_fused.hpp"      // k_bc_epoch_fused, oc_bc_epoch_fused, oc_bc_epoch_fused_plan (oc_bc_update's chain for minibatches of one workgroup, in one kernel)
+#include "sample_index.hpp"  // k_sample_count, k_sample_scan, k_sample_write, k_sample_permute, oc_sample_select, oc_sample_permute, oc_sample_index_plan
 #endif

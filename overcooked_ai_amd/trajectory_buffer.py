@@ -14,7 +14,9 @@
 the drawn actions and their log-probabilities there in place of the env's persistent buffers: no copy per step, and the rows are the
 step's own bytes.  `advantages` is `gae.gae` (oc_gae, one launch) over the whole buffer; `learner_batch` hands the buffer to
 `ppo_loss.ppo_loss` as flat [S] views, S = T * N * 2, and `minibatches` cuts a device permutation of the samples into index tensors
-(`permutation` hands it over whole, for `learner.PPOLearner.epoch`).
+(`permutation` hands it over whole, for `learner.PPOLearner.epoch`).  `learner_samples`, `learner_permutation` and
+`learner_minibatches` do the same over the learner's samples alone and on the library's own random stream (`sample_index`): with a
+behaviour-cloning partner a minibatch then holds only samples the loss counts.
 
 Row t of every tensor meets the alignment the step and the sampler ask for whatever N is: rewards rows are 16 N bytes apart (16-byte
 aligned), logp and values rows 8 N (8), actions rows 2 N (2), done and seat rows N (any address) — a fresh allocation starts on a
@@ -138,4 +140,33 @@ class TrajectoryBuffer:
             raise ValueError("TrajectoryBuffer.minibatches: %d samples do not fit an int32 index" % S)
         perm = torch.randperm(S, dtype=torch.int32, device=self.values.device, generator=generator)
         for lo in range(0, S, size):
+            yield perm[lo:lo + size]
+
+    def learner_samples(self):
+        """The samples of the buffer that the PPO loss uses — not the partner's (by `seat`), not an invalid row's (by `actions`) —
+        as a `sample_index.LearnerSamples`, in ascending order on the device: oc_sample_select, three launches, once per iteration.
+        Nothing here waits for the device; reading the result's `.n` does, once."""
+        from .sample_index import select
+
+        S = self.T * self.n_envs * 2
+        if S >= 2 ** 31:
+            raise ValueError("TrajectoryBuffer.learner_samples: %d samples do not fit an int32 index" % S)
+        return select(self.seat.view(S // 2) if self.seat is not None else None, self.actions.view(S), S)
+
+    def learner_permutation(self, samples, epoch, seed=None):
+        """One permutation of the learner's samples (`learner_samples()`'s) as an int32 [samples.n] tensor on the buffer's device,
+        for `learner.PPOLearner.epoch`: every entry is a sample the loss counts, so a minibatch of M rows holds M learner samples.
+        The permutation is include/oc_amd.h's function of (seed, epoch) — seed: the env's seed by default; epoch: any counter that
+        differs from pass to pass, such as iteration * num_sgd_iter + pass — and of nothing else: no torch generator is read."""
+        from .sample_index import permute
+
+        return permute(samples, samples.n, self.tenv.venv.seed if seed is None else seed, epoch)
+
+    def learner_minibatches(self, size, samples, epoch, seed=None):
+        """Index tensors (int32 [size], the last one shorter) that cut `learner_permutation(samples, epoch, seed)`."""
+        size = int(size)
+        if size < 1:
+            raise ValueError("TrajectoryBuffer.learner_minibatches: size must be at least 1, not %d" % size)
+        perm = self.learner_permutation(samples, epoch, seed)
+        for lo in range(0, int(perm.shape[0]), size):
             yield perm[lo:lo + size]
