@@ -1003,6 +1003,62 @@ int oc_partner_logits(const OcBatch* batch, const OcDensePolicy* policy, const O
 int oc_partner_logits_plan(const OcBatch* batch, const OcDensePolicy* policy, int num_pots, char* out, size_t out_size);
 
 /*
+ * The partner pool (ABI 6: entry points added beside the others; no existing signature or struct changes, so the version stays) —
+ * one of up to 16 frozen policies per episode: a league of the learner's past snapshots, BC models of several data splits,
+ * fictitious co-play.  oc_partner_pool_logits is oc_partner_logits with a pool in the policy's place: it seats the partners, draws
+ * each new partner's member, and writes every partner's logits from ITS member's network (csrc/partner_pool.hpp: the seated envs are
+ * bucketed by member on the device, without atomics, and the network runs over the buckets — four launches, the step's kernels
+ * stay as they are).
+ *
+ * Member draw.  The seating block is unchanged — the same counter and the same "SEAT" key — and so are the seats: d_seat is byte-equal
+ * to what oc_partner_logits draws from the same OcPartnerSeats.  A reseated env that gets a partner also draws
+ *   member = #{ m < n_members - 1 : r[2] >= thresholds[m] }
+ * from word 2 of that block, with non-decreasing thresholds (two equal ones give the member between them probability 0).
+ * thresholds == NULL is the uniform pool, thresholds[m] = ceil((m + 1) * 2^32 / n_members) formed in 64-bit integers, which makes
+ * member = (r[2] * n_members) >> 32.  d_member[e] = the draw, and 255 where the reseated env has no partner; an env that is not
+ * reseated keeps both its seat and its member (a kept member that is not below n_members reads as "no partner": no logits).  Word 3
+ * stays reserved.
+ *
+ * Logits.  For every env with a seat p and a member m after the reseat of this same call, d_logits[e][p][0..5] receives the network
+ * of members[m] on d_features[e][p][:], by OcDensePolicy's fmaf chain above: the six floats are bit-equal to what oc_partner_logits
+ * writes for that env with members[m] as the only policy.  Nothing else of d_logits is written.  No atomics, no spin flags, no
+ * look-back: a call repeats byte for byte.
+ *
+ * Scratch.  d_scratch is the caller's, 16-byte aligned, of the size in bytes that oc_partner_pool_plan states ("scratch ... B":
+ * 1092 + 4 * n_members * ceil(n_envs / 256) + 4 * n_envs); its contents after a call are unspecified.
+ */
+#define OC_MAX_POOL 16
+typedef struct OcPartnerPool {
+    const OcDensePolicy* members;  /* HOST array [n_members]; device weight pointers; the same in_dim, h1 / h2 may differ per member */
+    int n_members;                 /* 1..OC_MAX_POOL */
+    const uint32_t* thresholds;    /* HOST array [n_members - 1], non-decreasing, or NULL = uniform */
+    uint8_t* d_member;             /* [n_envs] in/out: the member an env's partner is, 255 = no partner */
+} OcPartnerPool;
+
+/*
+ * oc_partner_pool_logits — the reseat, the member draw and the partners' forward passes; the other arguments as oc_partner_logits'.
+ * OC_EINVAL, before any device call, with this entry point's name in front of the message: a NULL pool, members or d_member, or a
+ * NULL or misaligned d_scratch where there are envs; n_members outside 1..16; a member whose in_dim differs from the call's
+ * feature length, whose h1 or h2 lies outside 1..64, or that has a NULL or misaligned array (from the second member on the message
+ * ends in "(members[m])"); decreasing thresholds; n_envs of 2^31 or more; whatever oc_partner_logits refuses.
+ */
+int oc_partner_pool_logits(const OcBatch* batch, const OcPartnerPool* pool, const OcPartnerSeats* seats, const float* d_features,
+                           int num_pots, float* d_logits, void* d_scratch, void* stream);
+
+/*
+ * oc_partner_pool_plan — what oc_partner_pool_logits would launch, every launch with its grid, and the scratch bytes, as text:
+ *   "k_pool_seat grid=256, 256 lanes + k_sample_scan grid=1, 256 lanes, 5 pass(es) of 256 counts + k_pool_write grid=256, 256 lanes + k_pool_logits grid=260 (256 blocks of envs + 4 members), 256 lanes (128 j rows of one member), 32 x 32 x 2 f32 MFMA, K 96 -> 64 -> 64 -> 32, 101248 B LDS; scratch 267332 B"
+ *   "nothing to launch (no envs)"
+ * (j is 2 unless the seated envs' chunks of 256 rows outnumber the device's CUs; then the kernel takes the least j for which chunks
+ * of 128 j rows fit, from the scanned counts: a workgroup stages its member once and makes j passes.  No row's arithmetic depends
+ * on it.)
+ * The checks that need no device array apply (batch, pool: members' in_dim, h1, h2, n_members, thresholds; num_pots); usable without
+ * a GPU, like the other plan calls; refusals carry oc_partner_pool_logits's name.
+ *   out, out_size caller's text buffer (>= 512 bytes holds every answer)
+ */
+int oc_partner_pool_plan(const OcBatch* batch, const OcPartnerPool* pool, int num_pots, char* out, size_t out_size);
+
+/*
  * Advantages and value targets of a collected batch (ABI 6: entry points added beside the others; no existing signature, struct or
  * option changes, so the version stays) — what PPO makes of the T steps it has collected: per-agent GAE(gamma, lambda) advantages
  * and the value targets A + V, as the reference's PPO computes them (use_gae; gamma 0.99, lambda 0.98; the end of the horizon is a

@@ -32,7 +32,8 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_partner_logits", "oc_partner_logits_plan", "oc_gae", "oc_gae_plan", "oc_ppo_loss", "oc_ppo_loss_plan",
            "oc_policy_forward", "oc_policy_backward", "oc_policy_plan", "oc_adam_step", "oc_adam_plan", "oc_ppo_update", "oc_ppo_update_plan",
            "oc_bc_loss", "oc_bc_loss_plan", "oc_bc_update", "oc_bc_update_plan", "oc_bc_epoch_fused", "oc_bc_epoch_fused_plan",
-           "oc_sample_select", "oc_sample_permute", "oc_sample_index_plan")
+           "oc_sample_select", "oc_sample_permute", "oc_sample_index_plan", "oc_partner_pool_logits", "oc_partner_pool_plan")
+MAX_POOL = 16
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
 
 
@@ -83,6 +84,11 @@ class OcDensePolicy(ctypes.Structure):
 class OcPartnerSeats(ctypes.Structure):
     _fields_ = [("d_seat", ctypes.c_void_p), ("d_done", ctypes.c_void_p), ("bc_factor", ctypes.c_float), ("seed", ctypes.c_uint64),
                 ("env_offset", ctypes.c_int64), ("step", ctypes.c_int64)]
+
+
+class OcPartnerPool(ctypes.Structure):
+    _fields_ = [("members", ctypes.POINTER(OcDensePolicy)), ("n_members", ctypes.c_int), ("thresholds", ctypes.POINTER(ctypes.c_uint32)),
+                ("d_member", ctypes.c_void_p)]
 
 
 class OcGaeBatch(ctypes.Structure):
@@ -313,6 +319,11 @@ def load():
     L.oc_sample_permute.argtypes = [vp, vp, i64, u64, u64, vp, vp]
     L.oc_sample_index_plan.restype = i32
     L.oc_sample_index_plan.argtypes = [i64, i32, i32, i32, i64, i64, ctypes.c_char_p, ctypes.c_size_t]
+    ppp = ctypes.POINTER(OcPartnerPool)
+    L.oc_partner_pool_logits.restype = i32
+    L.oc_partner_pool_logits.argtypes = [bp, ppp, ctypes.POINTER(OcPartnerSeats), vp, i32, vp, vp, vp]
+    L.oc_partner_pool_plan.restype = i32
+    L.oc_partner_pool_plan.argtypes = [bp, ppp, i32, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

@@ -215,38 +215,39 @@ __global__ __launch_bounds__(BLOCK) void k_partner_logits(PartnerArgs a, int64_t
 
 const char* const PARTNER_WHO = "oc_partner_logits";
 
-int pl_refuse(const char* why) {
+// (who: the entry point a refusal names — oc_partner_pool_logits, csrc/partner_pool.hpp, makes the same checks under its own)
+int pl_refuse(const char* why, const char* who = PARTNER_WHO) {
     char msg[sizeof(g_err)];
-    snprintf(msg, sizeof(msg), "%s: %s", PARTNER_WHO, why);
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
     return fail(OC_EINVAL, msg);
 }
 
 // the checks that need no array (oc_partner_logits_plan makes these alone)
-int pl_check_shape(const OcBatch* b, const OcDensePolicy* pol, int num_pots) {
-    if (!b) return pl_refuse("batch is NULL");
-    if (b->n_envs < 0) return pl_refuse("batch.n_envs < 0");
-    if (!pol) return pl_refuse("policy is NULL");
-    if (num_pots < 0 || num_pots > 4) return pl_refuse("num_pots must be in 0..4");
-    if (pol->in_dim != 2 * (num_pots * 10 + 26) + 4) return pl_refuse("policy.in_dim must equal the feature length 2 * (num_pots * 10 + 26) + 4");
-    if (pol->h1 < 1 || pol->h1 > PL_HID || pol->h2 < 1 || pol->h2 > PL_HID) return pl_refuse("policy.h1 and policy.h2 must be in 1..64");
+int pl_check_shape(const OcBatch* b, const OcDensePolicy* pol, int num_pots, const char* who = PARTNER_WHO) {
+    if (!b) return pl_refuse("batch is NULL", who);
+    if (b->n_envs < 0) return pl_refuse("batch.n_envs < 0", who);
+    if (!pol) return pl_refuse("policy is NULL", who);
+    if (num_pots < 0 || num_pots > 4) return pl_refuse("num_pots must be in 0..4", who);
+    if (pol->in_dim != 2 * (num_pots * 10 + 26) + 4) return pl_refuse("policy.in_dim must equal the feature length 2 * (num_pots * 10 + 26) + 4", who);
+    if (pol->h1 < 1 || pol->h1 > PL_HID || pol->h2 < 1 || pol->h2 > PL_HID) return pl_refuse("policy.h1 and policy.h2 must be in 1..64", who);
     return OC_OK;
 }
 
 int pl_check(const OcBatch* b, const OcDensePolicy* pol, const OcPartnerSeats* seats, const float* d_features, int num_pots,
-             const float* d_logits) {
-    if (!b) return pl_refuse("batch is NULL");
-    if (!pol) return pl_refuse("policy is NULL");
-    if (!seats) return pl_refuse("seats is NULL");
-    if (!pol->d_w1 || !pol->d_b1 || !pol->d_w2 || !pol->d_b2 || !pol->d_w3 || !pol->d_b3) return pl_refuse("NULL weight or bias array");
-    if (!seats->d_seat) return pl_refuse("seats.d_seat is NULL");
-    if (!d_features || !d_logits) return pl_refuse("NULL d_features or d_logits");
-    if ((uintptr_t)d_features & 15u) return pl_refuse("d_features must be 16-byte aligned");
-    if ((uintptr_t)d_logits & 7u) return pl_refuse("d_logits must be 8-byte aligned");
+             const float* d_logits, const char* who = PARTNER_WHO) {
+    if (!b) return pl_refuse("batch is NULL", who);
+    if (!pol) return pl_refuse("policy is NULL", who);
+    if (!seats) return pl_refuse("seats is NULL", who);
+    if (!pol->d_w1 || !pol->d_b1 || !pol->d_w2 || !pol->d_b2 || !pol->d_w3 || !pol->d_b3) return pl_refuse("NULL weight or bias array", who);
+    if (!seats->d_seat) return pl_refuse("seats.d_seat is NULL", who);
+    if (!d_features || !d_logits) return pl_refuse("NULL d_features or d_logits", who);
+    if ((uintptr_t)d_features & 15u) return pl_refuse("d_features must be 16-byte aligned", who);
+    if ((uintptr_t)d_logits & 7u) return pl_refuse("d_logits must be 8-byte aligned", who);
     if (((uintptr_t)pol->d_w1 | (uintptr_t)pol->d_b1 | (uintptr_t)pol->d_w2 | (uintptr_t)pol->d_b2 | (uintptr_t)pol->d_w3 |
          (uintptr_t)pol->d_b3) & 3u)
-        return pl_refuse("weight and bias arrays must be 4-byte aligned");
-    if (int rc = pl_check_shape(b, pol, num_pots)) return rc;
-    if (!(seats->bc_factor >= 0.f && seats->bc_factor <= 1.f)) return pl_refuse("seats.bc_factor must be in [0, 1]");
+        return pl_refuse("weight and bias arrays must be 4-byte aligned", who);
+    if (int rc = pl_check_shape(b, pol, num_pots, who)) return rc;
+    if (!(seats->bc_factor >= 0.f && seats->bc_factor <= 1.f)) return pl_refuse("seats.bc_factor must be in [0, 1]", who);
     return OC_OK;
 }
 

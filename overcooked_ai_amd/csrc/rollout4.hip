@@ -179,4 +179,5 @@ template void describe_rollout<OC_R4_PART>(const Rollout4Call& c, char* out, siz
 #include "update_chain.hpp"  // oc_ppo_update, oc_bc_update and their plans (host code: the launches of the files above, minibatch after minibatch)
 #include "bc_fused.hpp"      // k_bc_epoch_fused, oc_bc_epoch_fused, oc_bc_epoch_fused_plan (oc_bc_update's chain for minibatches of one workgroup, in one kernel)
 #include "sample_index.hpp"  // k_sample_count, k_sample_scan, k_sample_write, k_sample_permute, oc_sample_select, oc_sample_permute, oc_sample_index_plan
+#include "partner_pool.hpp"  // k_pool_seat, k_pool_write, k_pool_logits, oc_partner_pool_logits, oc_partner_pool_plan (after partner.hpp and sample_index.hpp)
 #endif

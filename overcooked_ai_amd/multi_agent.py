@@ -8,7 +8,9 @@ With `bc_policy` (a `partner.DensePolicy`: the reference's behaviour-cloning net
 the reference's (rllib.py:262-281): at every episode start a `bc_factor` coin decides whether it has a "bc" partner and which
 player that partner plays — drawn on the library's counter-based stream, not np.random — and `step_sampled` evaluates the
 partners' network into the learner's logits array (`oc_partner_logits`, one launch in front of the step) before the actions are
-drawn.  The partner's observation alone is available through `observations("bc")`.
+drawn.  The partner's observation alone is available through `observations("bc")`.  With a `partner.PartnerPool` as `bc_policy`
+every new partner is also one of the pool's up to 16 members, drawn with its seat (`member`, `infos["member"]`: uint8 [N], 255 = no
+partner), and `partner_logits` evaluates each partner's own member (`oc_partner_pool_logits`); everything else is as with one policy.
 
 With `obs="features"` the same call also returns featurize_state of the states the next step starts from (`obs="both"`: the
 lossless encoding and the features), through `oc_multi_agent_step_featurize` — one kernel for single-layout batches.
@@ -189,9 +191,12 @@ class VecOvercookedMultiAgent:
     def __init__(self, layouts, n_envs, horizon=400, reward_shaping_factor=0.0, reward_shaping_horizon=0, use_phi=True,
                  gamma=0.99, obs="ppo", obs_dtype=None, device="cuda", random_start_pos=False, rnd_obj_prob_thresh=0.0,
                  num_pots=2, counter_goals="none", one_kernel=False, bc_policy=None, bc_schedule=None, **venv_kwargs):
+        import re
+
         import torch
 
         from . import _lib
+        from .partner import PartnerPool
         from .vec_env import VecOvercookedEnv
 
         self._torch, self._lib = torch, _lib
@@ -239,6 +244,14 @@ class VecOvercookedMultiAgent:
         self._reseat_all = True  # construction and reset(): every env is seated anew at the next partner_logits()
         self._feat_current = False  # the feature buffer holds featurize_state of the current states
         self._seats = _lib.OcPartnerSeats()
+        # a partner.PartnerPool: member[e] is the pool member the partner of env e is (255 = no partner), drawn with the seat; the
+        # scratch of oc_partner_pool_logits is allocated once, at the size the plan states
+        self._pool = None
+        if isinstance(bc_policy, PartnerPool):
+            self.member = torch.full((self.n_envs,), 255, dtype=torch.uint8, device=dev)
+            self._pool = bc_policy.struct_for(self.member)
+            nbytes = int(re.search(r"scratch (\d+) B", self.plan_partner()).group(1)) if self.n_envs else 0
+            self.pool_scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
         self.anneal_bc_factor(0)
         if self.use_phi:
             # phi of each layout's STANDARD start state (what a standard reset carries into phi_cur), from a probe batch of
@@ -460,6 +473,8 @@ class VecOvercookedMultiAgent:
         infos["actions"], infos["logp"] = actions, logp
         if self.bc_policy is not None:
             infos["seat"] = self.seat
+            if self._pool is not None:
+                infos["member"] = self.member
         return out, shaped, done, infos
 
     def partner_logits(self, logits):
@@ -467,7 +482,9 @@ class VecOvercookedMultiAgent:
         env at the first call and after reset() — are seated anew from the current `bc_factor` on the seating stream of
         include/oc_amd.h at (the env's seed, its env offset + env, sample_step), and for every env with a partner the network's six
         logits on featurize_state of the CURRENT state of the partner's player overwrite `logits[e, seat[e]]`; nothing else of
-        `logits` is written.  Does not advance `sample_step`.  Returns `seat` (uint8 [n_envs]: 0 / 1 the partner's player, 255 none)."""
+        `logits` is written.  Does not advance `sample_step`.  Returns `seat` (uint8 [n_envs]: 0 / 1 the partner's player, 255 none).
+        With a PartnerPool (oc_partner_pool_logits, four launches) a reseated env with a partner also draws its member into `member`,
+        and the six logits are the network of that member; `pool_scratch` is the call's scratch, allocated once."""
         import ctypes
 
         v, torch = self.venv, self._torch
@@ -482,9 +499,15 @@ class VecOvercookedMultiAgent:
         s = self._seats
         s.d_seat, s.d_done = self.seat.data_ptr(), None if self._reseat_all else self._last_done.data_ptr()
         s.bc_factor, s.seed, s.env_offset, s.step = float(self.bc_factor), v.seed, v.env_offset, self.sample_step
-        rc = v._launch(v.lib.oc_partner_logits, v._bref, self.bc_policy._ref, ctypes.byref(s), self._feat_buffer().data_ptr(),
-                       self.num_pots, logits.data_ptr())
-        self._lib.check(rc, "oc_partner_logits")
+        if self._pool is not None:  # (the stream is _launch's last argument: the scratch goes in front of it)
+            self._pool.d_member = self.member.data_ptr()
+            rc = v._launch(v.lib.oc_partner_pool_logits, v._bref, ctypes.byref(self._pool), ctypes.byref(s), self._feat_buffer().data_ptr(),
+                           self.num_pots, logits.data_ptr(), self.pool_scratch.data_ptr())
+            self._lib.check(rc, "oc_partner_pool_logits")
+        else:
+            rc = v._launch(v.lib.oc_partner_logits, v._bref, self.bc_policy._ref, ctypes.byref(s), self._feat_buffer().data_ptr(),
+                           self.num_pots, logits.data_ptr())
+            self._lib.check(rc, "oc_partner_logits")
         self._reseat_all = False
         return self.seat
 
@@ -494,9 +517,13 @@ class VecOvercookedMultiAgent:
 
         if self.bc_policy is None:
             raise ValueError("plan_partner needs a bc_policy")
-        out = ctypes.create_string_buffer(320)
-        rc = self.venv.lib.oc_partner_logits_plan(self.venv._bref, self.bc_policy._ref, self.num_pots, out, len(out))
-        self._lib.check(rc, "oc_partner_logits_plan")
+        out = ctypes.create_string_buffer(512)
+        if self._pool is not None:
+            rc = self.venv.lib.oc_partner_pool_plan(self.venv._bref, ctypes.byref(self._pool), self.num_pots, out, len(out))
+            self._lib.check(rc, "oc_partner_pool_plan")
+        else:
+            rc = self.venv.lib.oc_partner_logits_plan(self.venv._bref, self.bc_policy._ref, self.num_pots, out, len(out))
+            self._lib.check(rc, "oc_partner_logits_plan")
         return out.value.decode()
 
     def anneal_bc_factor(self, timesteps):

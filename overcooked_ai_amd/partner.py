@@ -4,7 +4,8 @@ The reference's BC model (human_aware_rl/imitation/behavior_cloning_tf2.py) is a
 in_dim -> h1 -> h2 -> 6 logits with ReLU after the two hidden layers (96 -> 64 -> 64 -> 6 by default).  `DensePolicy` takes its six
 arrays in the Keras Dense layout (kernels [in, out], biases [out]; `model.get_weights()` of such a model, in order), validates
 them, uploads them once as contiguous float32 and holds the `OcDensePolicy` the C-ABI takes.  `VecOvercookedMultiAgent(...,
-bc_policy=policy)` seats it."""
+bc_policy=policy)` seats it.  `PartnerPool` is up to 16 of them, one drawn per episode on the device (`oc_partner_pool_logits`):
+`bc_policy=PartnerPool([...])`."""
 import ctypes
 
 import numpy as np
@@ -59,3 +60,66 @@ class DensePolicy:
     def tensors(self):
         """The six device tensors (float32), in the constructor's order."""
         return tuple(self._dev)
+
+
+def thresholds_of(weights):
+    """The OcPartnerPool thresholds of non-negative member weights: thresholds[m] = ceil(2^32 * (w_0 + ... + w_m) / sum(w)) for
+    m < len(weights) - 1, in exact rational arithmetic, capped at 2^32 - 1.  Member m is drawn with probability (thresholds[m] -
+    thresholds[m - 1]) / 2^32 (0 before the first, 2^32 after the last): its share rounded to a multiple of 2^-32, and exactly 0 for
+    a weight of 0, whose two thresholds are equal — except for a LAST member of weight 0, which the cap leaves 2^-32."""
+    from fractions import Fraction
+
+    w = [Fraction(x) for x in weights]
+    if any(x < 0 for x in w) or sum(w) <= 0:
+        raise ValueError("PartnerPool: weights must be non-negative with a positive sum")
+    total, run, out = sum(w), Fraction(0), []
+    for x in w[:-1]:
+        run += x
+        out.append(min(-((-run * 2**32) // total), 2**32 - 1))
+    return [int(t) for t in out]
+
+
+class PartnerPool:
+    """1 to 16 `DensePolicy` on one device with one `in_dim` (h1 and h2 may differ): the members of `oc_partner_pool_logits`.
+    `VecOvercookedMultiAgent(..., bc_policy=pool)` draws one of them for every new partner, uniformly, or by `weights`
+    (non-negative numbers, one per member: see `thresholds_of` for their rounding).  `set_member(i, policy)` swaps a member in place
+    — a league that ages — for every env built on this pool, from its next call on.  `n_members`, `in_dim`, `policies`,
+    `thresholds` (None: uniform)."""
+
+    def __init__(self, policies, weights=None):
+        from . import _lib
+
+        policies = list(policies)
+        if not 1 <= len(policies) <= _lib.MAX_POOL:
+            raise ValueError("PartnerPool: %d members, must be 1..%d" % (len(policies), _lib.MAX_POOL))
+        self.n_members, self.in_dim, self.device = len(policies), policies[0].in_dim, policies[0].device
+        self.policies = [None] * self.n_members
+        self._members = (_lib.OcDensePolicy * self.n_members)()
+        for i, p in enumerate(policies):
+            self.set_member(i, p)
+        self.thresholds = self._thresholds = None
+        if weights is not None:
+            weights = list(weights)
+            if len(weights) != self.n_members:
+                raise ValueError("PartnerPool: %d weights for %d members" % (len(weights), self.n_members))
+            self.thresholds = thresholds_of(weights)
+            self._thresholds = (ctypes.c_uint32 * max(1, self.n_members - 1))(*self.thresholds)
+
+    def set_member(self, i, policy):
+        if not isinstance(policy, DensePolicy):
+            raise ValueError("PartnerPool: member %d is not a DensePolicy" % i)
+        if not 0 <= i < self.n_members:
+            raise ValueError("PartnerPool: no member %d among %d" % (i, self.n_members))
+        if policy.in_dim != self.in_dim or policy.device != self.device:
+            raise ValueError("PartnerPool: member %d has in_dim %d on %s, the pool %d on %s"
+                             % (i, policy.in_dim, policy.device, self.in_dim, self.device))
+        self.policies[i] = policy  # (kept alive: the array below points into its tensors)
+        self._members[i] = policy.struct
+
+    def struct_for(self, member):
+        """The OcPartnerPool of an env whose member array is the uint8 tensor `member` (the pool's arrays are shared)."""
+        from . import _lib
+
+        return _lib.OcPartnerPool(self._members, self.n_members,
+                                  ctypes.cast(self._thresholds, ctypes.POINTER(ctypes.c_uint32)) if self._thresholds is not None else None,
+                                  member.data_ptr())
