@@ -941,7 +941,7 @@ int oc_multi_agent_step_sample_plan(const OcBatch* batch, int horizon, int with_
  * dense network on featurize_state of human_aware_rl/imitation/behavior_cloning_tf2.py (in_dim -> h1 -> h2 -> 6 logits, ReLU).
  * oc_partner_logits seats the partners and writes their logits INTO the learner's logits array, so that the sampler that follows
  * (oc_multi_agent_step_sample, oc_sample_actions) draws the partner's action from its own policy and the learner's from the
- * learner's: one launch (k_partner_logits, csrc/partner.hpp) in front of the step, whose kernels stay as they are.
+ * learner's: one launch (k_partner_logits, csrc/partner.hpp; its MFMA tile: csrc/mlp_tile.hpp) in front of the step, whose kernels stay as they are.
  *
  * Seating stream.  For global env g = env_offset + e and the caller's 64-bit step counter t = step:
  *   r[0..3] = philox4x32_10(counter = {t_lo, g_lo, g_hi, t_hi}, key = {seed_lo, seed_hi ^ 0x53454154 ("SEAT")})
@@ -961,7 +961,7 @@ int oc_multi_agent_step_sample_plan(const OcBatch* batch, int horizon, int with_
  *   a2_j = max(the same chain over a1_0 .. a1_{h1-1} with w2, from b2_j, 0)                                         j < h2
  *   logit_j = the same chain over a2_0 .. a2_{h2-1} with w3, from b3_j                                              j < 6
  * one rounding per step, no wider accumulator.  This is what gfx950's f32-input MFMA computes bit for bit when the K steps are issued
- * in order with the bias as the initial accumulator (v_mfma_f32_32x32x2_f32); the kernel pads the hidden widths to its tile of 32
+ * in order with the bias as the initial accumulator (v_mfma_f32_32x32x2_f32; csrc/mlp_tile.hpp states the scheme); the kernel pads the hidden widths to its tile of 32
  * units with zero weights and zero biases, which add exact zeros to a chain.  (max(., 0) of a NaN is 0, as v_max_f32 gives it; a
  * chain whose value is exactly -0 may come out as +0, since a padded step adds +0 to it.)
  */

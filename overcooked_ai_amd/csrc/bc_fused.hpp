@@ -10,9 +10,10 @@
 // at the tens of microseconds a minibatch takes; docs/NOTEBOOK.md); the host chains the launches of an epoch on the caller's stream.
 // Per minibatch k, from the weights minibatch k - 1 left:
 //   stage     W1, W2, W2 transposed, (Wp|wv) both ways and the biases from global memory into LDS, as k_policy_forward and
-//             k_policy_backward stage them (policy.hpp's pol_stage functions)
+//             k_policy_backward stage them (mlp_tile.hpp: pol_stage_dealt, pol_stage_biases; policy.hpp: pol_stage_w2_back and
+//             pol_stage_head_back, which k_policy_backward holds as its own lambdas, pol_stage_head_forward, pol_stage_head_bias)
 //   forward   wavefront w gathers tile w (rows 32 w .. 32 w + 31) through the index (pol_source, pol_load_rows: a row out of range is a
-//             row of zeros), runs pol_hidden and k_policy_forward's last layer, and leaves the logits in its [row][8] image (zeros
+//             row of zeros), runs pol_hidden (mlp_tile.hpp) and k_policy_forward's last layer, and leaves the logits in its [row][8] image (zeros
 //             for a row without a source, as k_policy_forward stores them)
 //   head      lane r of the workgroup takes row r (row r on lane r % 64 of wavefront r / 64, k_bc_loss's dealing): bc_loss.hpp's
 //             arithmetic, the gradients back into the [row][8] image, the four f64 sums in k_bc_loss's order (the shuffle tree 32 .. 1,
@@ -22,10 +23,14 @@
 //             2 NF + 6 accumulator tiles are added ((w0 + w1) + w2) + w3 through LDS over the weights
 //   adam      k_adam_step's three phases on that sum with grad_scale = stats[7]: lane l owns the flat elements i % 256 == l, the f64
 //             tree 128 .. 1, the same skip rules and clock; the scaled gradients' image lies over the row images, which are dead
+// Shared with the policy kernels: the stager and every staging function named above, pol_hidden, pol_source, pol_load_rows.
 // The bodies of k_policy_backward's tile, of its wavefront sum and of k_bc_loss's row stand here a second time (bcf_tile_back,
 // bcf_sum_waves, bcf_partial_element, bcf_row, bcf_row_grads, bcf_sum_lanes, bcf_stats_of): moved into functions that those kernels
-// call too, they changed the register counts of k_policy_backward and the order of k_bc_loss's loads (docs/NOTEBOOK.md).  Adam's
-// scalars and element update are shared (adam.hpp: adam_step_of, adam_element; k_adam_step compiles to the same instructions).
+// call too, they changed the register counts of k_policy_backward and the order of k_bc_loss's loads (docs/NOTEBOOK.md).  The last
+// forward layer and the LDS carve-up stand here a second time too (mlp_tile.hpp: pol_head, pl_operands): with either, this kernel's
+// ds_ instruction count moved by one or two (read pairs of the bias loads split); as it stands the kernel is the assembly it was
+// before mlp_tile.hpp existed.
+// Adam's scalars and element update are shared (adam.hpp: adam_step_of, adam_element; k_adam_step compiles to the same instructions).
 //
 // Visibility.  Adam's stores to the parameters are plain vector stores by the lanes that own the elements; the staging loads of
 // minibatch k + 1 are plain vector loads by other lanes of the SAME workgroup.  Between them stands the __syncthreads() at the top of
@@ -380,27 +385,11 @@ __global__ __launch_bounds__(BLOCK) void k_bc_epoch_fused(BcFusedArgs a) {
         BCF_STAMP(0);
         pol_stage_dealt(sw1, pa.w1, pa.in_dim, pa.h1, pa.in_dim / 2);
         pol_stage_dealt(sw2, pa.w2, pa.h1, pa.h2, bcf_opaque(PL_STEPS));
-        // W2 for the way back: A[unit i of layer 1, dealt][k = unit j of layer 2]
-        pol_stage(sw2t, bcf_opaque(PL_W2), pa.w1, [=](int i) -> const float* {
-            const int ln = i & 63, tile = (i >> 6) & 1, s = i >> 7;
-            const int u = 32 * tile + pl_unit_of_row(ln & 31), j = 2 * s + (ln >> 5);
-            return u < pa.h1 && j < pa.h2 ? pa.w2 + u * pa.h2 + j : nullptr;
-        });
-        // (Wp|wv) for the way back: A[unit of layer 2, dealt][k = output j], 7 outputs padded to 8
-        pol_stage(swpt, bcf_opaque(POL_WPT), pa.w1, [=](int i) -> const float* {
-            const int ln = i & 63, tile = (i >> 6) & 1, s = i >> 7;
-            const int u = 32 * tile + pl_unit_of_row(ln & 31), j = 2 * s + (ln >> 5);
-            if (u >= pa.h2 || j >= POL_OUT) return nullptr;
-            return j < OC_NUM_ACTIONS ? pa.wp + u * OC_NUM_ACTIONS + j : pa.wv + u;
-        });
-        // the last layer going forward, rows in their natural order: six logits and the value
-        pol_stage(sw3, bcf_opaque(PL_W3), pa.w1, [=](int i) -> const float* {
-            const int ln = i & 63, kk = 2 * (i >> 6) + (ln >> 5), r = ln & 31;
-            if (kk >= pa.h2 || r >= POL_OUT) return nullptr;
-            return r < OC_NUM_ACTIONS ? pa.wp + kk * OC_NUM_ACTIONS + r : pa.wv + kk;
-        });
-        pol_stage_biases(sb1, sb2, pa);
-        if (tid < 32) sb3[tid] = tid < OC_NUM_ACTIONS ? pa.bp[tid] : tid == OC_NUM_ACTIONS ? pa.bv[tid - OC_NUM_ACTIONS] : 0.f;
+        pol_stage_w2_back(sw2t, bcf_opaque(PL_W2), pa);
+        pol_stage_head_back(swpt, bcf_opaque(POL_WPT), pa);
+        pol_stage_head_forward(sw3, bcf_opaque(PL_W3), pa);
+        pol_stage_biases(sb1, sb2, pa.b1, pa.b2, pa.h1, pa.h2);
+        pol_stage_head_bias(sb3, pa);
         __syncthreads();
         BCF_STAMP(1);
 
@@ -417,7 +406,7 @@ __global__ __launch_bounds__(BLOCK) void k_bc_epoch_fused(BcFusedArgs a) {
             __builtin_amdgcn_sched_barrier(0);
             pol_hidden<true>(sw1, sw2, sb1, sb2, sx, pa.in_dim, lane, c0, c1, d0, d1);
             __builtin_amdgcn_sched_barrier(0);
-            pl_f32x16 out;
+            pl_f32x16 out;  // (pol_head of mlp_tile.hpp, word for word: called here it splits two ds_read2_b32 of the bias reads, + 2 ds_)
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) out[reg] = sb3[(reg & 3) + 8 * (reg >> 2) + 4 * h];
 #pragma unroll

@@ -1,7 +1,7 @@
 // partner_pool.hpp — a pool of frozen partner policies, one member per episode: k_pool_seat, k_pool_write, k_pool_logits,
 // oc_partner_pool_logits, oc_partner_pool_plan (include/oc_amd.h: OcPartnerPool)
-// Part of liboc_amd.so: included at file scope by rollout4.hip in its OC_R4_PART == 2 unit, after partner.hpp (the seating stream, the
-// operand staging pl_stage, the wave fence, the LDS shape, the host checks) and sample_index.hpp (k_sample_scan, si_lanes_below).
+// Part of liboc_amd.so: included at file scope by rollout4.hip in its OC_R4_PART == 2 unit, after mlp_tile.hpp (the MFMA tile of
+// the dense network), partner.hpp (the seating stream, the stager pl_stage, the LDS shape, the host checks) and sample_index.hpp (k_sample_scan, si_lanes_below).
 //
 // A 32-env MFMA tile shares one set of weights, and neighbouring envs draw different members: so the seated envs are bucketed by
 // member first — over the whole batch, since a bucket of one workgroup's 256 envs would hold 256 / K rows and every workgroup would
@@ -40,11 +40,8 @@ inline size_t pp_scratch_bytes(int64_t n, int n_members) { return PP_COUNTS_AT +
 __host__ __device__ constexpr size_t pp_lds_bytes(int in_dim) { return pl_lds_bytes(in_dim) + sizeof(int32_t) * BLOCK; }  // + the rows' envs
 
 struct PoolSeatArgs {
-    uint8_t *seat, *member;
-    const uint8_t* done;
-    float bc_factor;
-    uint32_t seed_lo, seed_hi, t_lo, t_hi;
-    int64_t env_offset;
+    SeatStream s;  // (partner.hpp)
+    uint8_t* member;
     int n_members;
     uint32_t thr[OC_MAX_POOL - 1];
     PoolMember members[OC_MAX_POOL];
@@ -59,20 +56,18 @@ __global__ __launch_bounds__(BLOCK) void k_pool_seat(PoolSeatArgs a, int64_t n, 
     const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     uint32_t seat = 255u, member = 255u;
     if (e < n) {
-        if (!a.done || a.done[e]) {
-            const uint64_t g = (uint64_t)(a.env_offset + e);
+        if (!a.s.done || a.s.done[e]) {
             uint32_t r[4];
-            philox4x32_10(a.t_lo, (uint32_t)g, (uint32_t)(g >> 32), a.t_hi, a.seed_lo, a.seed_hi ^ SEAT_KEY_TWEAK, r);
-            seat = (float)(r[0] >> 8) * 0x1p-24f < a.bc_factor ? (r[1] & 1u) : 255u;
+            seat = seat_draw(a.s, e, r);
             if (seat <= 1u) {
                 member = 0u;
 #pragma unroll
                 for (int m = 0; m < OC_MAX_POOL - 1; ++m) member += (m < a.n_members - 1 && r[2] >= a.thr[m]) ? 1u : 0u;
             }
-            a.seat[e] = (uint8_t)seat;
+            a.s.seat[e] = (uint8_t)seat;
             a.member[e] = (uint8_t)member;
         } else {
-            seat = a.seat[e];
+            seat = a.s.seat[e];
             member = a.member[e];
         }
     }
@@ -173,16 +168,11 @@ __global__ __launch_bounds__(BLOCK) void k_pool_logits(PoolArgs a) {
     const PoolMember pm = a.table[__builtin_amdgcn_readfirstlane(member)];
 
     extern __shared__ float pp_lds[];
-    float* const sw1 = pp_lds;
-    float* const sw2 = sw1 + pl_w1_floats(a.in_dim);
-    float* const sw3 = sw2 + PL_W2;
-    float* const sb1 = sw3 + PL_W3;
-    float* const sb2 = sb1 + PL_HID;
-    float* const sb3 = sb2 + PL_HID;
-    uint8_t* const sseat = reinterpret_cast<uint8_t*>(sb3 + 32);
-    int32_t* const senv = reinterpret_cast<int32_t*>(sb3 + 32 + PL_SEATS);
+    const PlOperands w = pl_operands(pp_lds, a.in_dim);
+    uint8_t* const sseat = reinterpret_cast<uint8_t*>(w.end);
+    int32_t* const senv = reinterpret_cast<int32_t*>(w.end + PL_SEATS);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* const sx = sb3 + 32 + PL_SEATS + BLOCK + wave * pl_image_floats(a.in_dim);
+    float* const sx = w.end + PL_SEATS + BLOCK + wave * pl_image_floats(a.in_dim);
 
     // (the rows of the first pass: their loads are in flight beside the staging)
     const int col = lane & 31, h = lane >> 5;
@@ -191,17 +181,13 @@ __global__ __launch_bounds__(BLOCK) void k_pool_logits(PoolArgs a) {
     uint32_t seat = row < last ? a.seat[env] : 255u;
 
     // ---- the member's weights and biases, once per workgroup, in operand order
-    pl_stage<2, true>(sw1, pm.w1, a.in_dim, pm.h1, a.in_dim / 2);
-    pl_stage<2, true>(sw2, pm.w2, pm.h1, pm.h2, PL_STEPS);
-    pl_stage<1, false>(sw3, pm.w3, pm.h2, OC_NUM_ACTIONS, PL_STEPS);
-    if (threadIdx.x < PL_HID) {
-        sb1[threadIdx.x] = (int)threadIdx.x < pm.h1 ? pm.b1[threadIdx.x] : 0.f;
-        sb2[threadIdx.x] = (int)threadIdx.x < pm.h2 ? pm.b2[threadIdx.x] : 0.f;
-        if (threadIdx.x < 32) sb3[threadIdx.x] = threadIdx.x < OC_NUM_ACTIONS ? pm.b3[threadIdx.x] : 0.f;
-    }
+    pl_stage<2, true>(w.sw1, pm.w1, a.in_dim, pm.h1, a.in_dim / 2);
+    pl_stage<2, true>(w.sw2, pm.w2, pm.h1, pm.h2, PL_STEPS);
+    pl_stage<1, false>(w.sw3, pm.w3, pm.h2, OC_NUM_ACTIONS, PL_STEPS);
+    pol_stage_biases(w.sb1, w.sb2, pm.b1, pm.b2, pm.h1, pm.h2);
+    if (threadIdx.x < 32) w.sb3[threadIdx.x] = threadIdx.x < OC_NUM_ACTIONS ? pm.b3[threadIdx.x] : 0.f;
     __syncthreads();
 
-    const int S = a.in_dim + 2, q = a.in_dim / 4, steps1 = a.in_dim / 2;
     const uint8_t* const tseat = sseat + wave * 32;
     const int32_t* const tenv = senv + wave * 32;
     // ---- the passes of 128 rows; from here on a wavefront works alone, on rows [32 wave, 32 wave + 32) of every pass
@@ -216,73 +202,13 @@ __global__ __launch_bounds__(BLOCK) void k_pool_logits(PoolArgs a) {
         seat = row < last ? a.seat[env] : 255u;
         // ---- the tile's rows -> the image (rows beyond the bucket keep what the image held: their columns are never stored)
         pl_wave_fence();  // (and the tile's rows are written)
-        for (int i0 = lane; i0 < 32 * q; i0 += 4 * 64) {  // four 16-byte loads in flight per lane
-            float4 v[4];
-            int at[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int i = i0 + j * 64;
-                const bool in = i < 32 * q;
-                const int r = in ? i / q : 0, c = in ? i - r * q : 0;
-                const uint32_t p = tseat[r];
-                const bool load = in && p <= 1u;
-                v[j] = *reinterpret_cast<const float4*>(load ? a.features + ((int64_t)tenv[r] * 2 + p) * a.in_dim + 4 * c : a.features);
-                at[j] = load ? r * S + 4 * c : -1;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (at[j] >= 0) {
-                    float2* const dst = reinterpret_cast<float2*>(sx + at[j]);
-                    dst[0] = make_float2(v[j].x, v[j].y);
-                    dst[1] = make_float2(v[j].z, v[j].w);
-                }
-        }
+        pl_load_seated(sx, a.features, tseat, a.in_dim, lane, [=](int r) { return tenv[r]; });
         pl_wave_fence();
-        // ---- the three layers, as k_partner_logits issues them
-        pl_f32x16 c0, c1;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            c0[reg] = sb1[2 * reg + h];
-            c1[reg] = sb1[32 + 2 * reg + h];
-        }
-        const float* const xrow = sx + col * S + h;
-#pragma unroll 4
-        for (int s = 0; s < steps1; ++s) {
-            const float b = xrow[2 * s];
-            c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(sw1[(2 * s) * 64 + lane], b, c0, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(sw1[(2 * s + 1) * 64 + lane], b, c1, 0, 0, 0);
-        }
-        pl_f32x16 d0, d1;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            d0[reg] = sb2[2 * reg + h];
-            d1[reg] = sb2[32 + 2 * reg + h];
-        }
-#pragma unroll
-        for (int s = 0; s < PL_STEPS; ++s) {
-            const float b = fmaxf(s < 16 ? c0[s & 15] : c1[s & 15], 0.f);
-            d0 = __builtin_amdgcn_mfma_f32_32x32x2f32(sw2[(2 * s) * 64 + lane], b, d0, 0, 0, 0);
-            d1 = __builtin_amdgcn_mfma_f32_32x32x2f32(sw2[(2 * s + 1) * 64 + lane], b, d1, 0, 0, 0);
-        }
-        pl_f32x16 o;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) o[reg] = sb3[(reg & 3) + 8 * (reg >> 2) + 4 * h];
-#pragma unroll
-        for (int s = 0; s < PL_STEPS; ++s) {
-            const float b = fmaxf(s < 16 ? d0[s & 15] : d1[s & 15], 0.f);
-            o = __builtin_amdgcn_mfma_f32_32x32x2f32(sw3[s * 64 + lane], b, o, 0, 0, 0);
-        }
-        // ---- rows 0..3 sit in registers 0..3 of lane half 0, rows 4..5 in registers 0..1 of half 1
+        pl_f32x16 c0, c1, d0, d1;
+        pol_hidden<false>(w.sw1, w.sw2, w.sb1, w.sb2, sx, a.in_dim, lane, c0, c1, d0, d1);
+        const pl_f32x16 o = pol_head(w.sw3, w.sb3, lane, d0, d1);
         const uint32_t p = tseat[col];
-        if (p <= 1u) {
-            float2* const out = reinterpret_cast<float2*>(a.logits + ((int64_t)tenv[col] * 2 + p) * OC_NUM_ACTIONS);
-            if (h == 0) {
-                out[0] = make_float2(o[0], o[1]);
-                out[1] = make_float2(o[2], o[3]);
-            } else {
-                out[2] = make_float2(o[0], o[1]);
-            }
-        }
+        if (p <= 1u) pl_store_logits(a.logits + ((int64_t)tenv[col] * 2 + p) * OC_NUM_ACTIONS, h, o);
     }
 }
 
@@ -341,10 +267,8 @@ int oc_partner_pool_logits(const OcBatch* b, const OcPartnerPool* pool, const Oc
     uint32_t* const counts = reinterpret_cast<uint32_t*>(scratch + PP_COUNTS_AT);
     int32_t* const order = reinterpret_cast<int32_t*>(counts + pp_counts(n, K));
     PoolSeatArgs s = {};
-    s.seat = seats->d_seat; s.member = pool->d_member; s.done = seats->d_done; s.bc_factor = seats->bc_factor;
-    s.seed_lo = (uint32_t)seats->seed; s.seed_hi = (uint32_t)(seats->seed >> 32);
-    s.t_lo = (uint32_t)(uint64_t)seats->step; s.t_hi = (uint32_t)((uint64_t)seats->step >> 32);
-    s.env_offset = seats->env_offset;
+    s.s = seat_stream_of(seats);
+    s.member = pool->d_member;
     s.n_members = K;
     pp_thresholds(pool, s.thr);
     for (int m = 0; m < K; ++m) {

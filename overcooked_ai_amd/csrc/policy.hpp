@@ -1,17 +1,14 @@
 // policy.hpp — the learner's actor-critic on featurize_state rows, forward and backward to the weights: k_policy_forward,
 // k_policy_backward, k_policy_grad_sum, oc_policy_forward, oc_policy_backward, oc_policy_plan
 // (include/oc_amd.h: OcActorCritic, OcPolicyRows, OcPolicyGrads)
-// Part of liboc_amd.so: included at file scope by rollout4.hip in its OC_R4_PART == 2 unit, behind partner.hpp, whose operand-order
-// scheme, unit dealing (pl_unit_of_row), wavefront fence and tile type it uses; after common.hpp (BLOCK) and host_util.hpp (fail,
-// check_launch, want_lds).  k_partner_logits and partner.hpp's entry points are untouched, and no other kernel knows of this file.
+// Part of liboc_amd.so: included at file scope by rollout4.hip in its OC_R4_PART == 2 unit, behind mlp_tile.hpp (the MFMA tile of the
+// dense network: scheme, stager, pol_hidden, pol_head); after common.hpp (BLOCK) and host_util.hpp (fail, check_launch, want_lds).
 //
 // Both kernels run a persistent grid of at most POL_GRID workgroups.  A wavefront takes 32-row tiles
 //   tile = (pass * gridDim.x + blockIdx.x) * wavefronts + wavefront,   pass = 0, 1, ...
-// and computes them as k_partner_logits does: Dt = Wt * Xt on v_mfma_f32_32x32x2_f32, a tile's 32 columns the rows of the call, the
-// weights staged once per workgroup in operand order with the unit dealing that makes max(acc, 0) the next layer's B operand, the
-// K steps in ascending order from the bias (the header's fmaf chain, bit for bit), the feature rows through the wavefront's LDS image
-// with the in_dim + 2 stride.  Rows may be gathered through an index; a row that is out of range is a row of zeros in the image
-// (nothing is read for it) and its outputs are +0.0f.  The last layer's tile carries the value head as its seventh row.
+// and computes them as mlp_tile.hpp says, a tile's 32 columns the rows of the call.  Rows may be gathered through an index; a row
+// that is out of range is a row of zeros in the image (nothing is read for it) and its outputs are +0.0f.  The last layer's tile
+// carries the value head as its seventh row.
 //
 // k_policy_backward recomputes layers 1 and 2 of a tile (the logits themselves are not needed), then
 //   delta3 = the seven upstream gradients of the row (zeros for a row out of range),
@@ -94,39 +91,41 @@ __host__ __device__ inline PolicyLayout pol_layout(int in_dim, int h1, int h2) {
     return o;
 }
 
-// dst[i] = *at(i), or 0 where at(i) is NULL, for i < total, by the whole workgroup; PL_BATCH loads in flight per lane (partner.hpp)
-template <class F>
-__device__ __forceinline__ void pol_stage(float* dst, int total, const float* inside, F at) {
-    const int nt = blockDim.x;
-    for (int i0 = threadIdx.x; i0 < total; i0 += PL_BATCH * nt) {
-        float v[PL_BATCH];
-#pragma unroll
-        for (int j = 0; j < PL_BATCH; ++j) {
-            const int i = i0 + j * nt;
-            const float* p = i < total ? at(i) : nullptr;
-            v[j] = *(p ? p : inside);  // (an address inside an array in any case)
-            v[j] = p ? v[j] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < PL_BATCH; ++j)
-            if (i0 + j * nt < total) dst[i0 + j * nt] = v[j];
-    }
-}
+// ---- the operands that are the learner's own, each by the whole workgroup (pol_stage, mlp_tile.hpp); total: the floats of dst, which a
+// caller may hide from the optimiser (bc_fused.hpp: bcf_opaque).  The two for the way back serve k_bc_epoch_fused; k_policy_backward
+// keeps them as lambdas of its own (see there).
 
-// the forward operands of layers 1 and 2, as pl_stage<2, true> lays them out: dst[(s * 2 + tile) * 64 + lane] = w[2 s + (lane >> 5)][32 tile + unit of row lane & 31]
-__device__ __forceinline__ void pol_stage_dealt(float* dst, const float* __restrict__ w, int K, int H, int steps) {
-    pol_stage(dst, steps * 2 * 64, w, [=](int i) -> const float* {
-        const int lane = i & 63, tile = (i >> 6) & 1, s = i >> 7;
-        const int k = 2 * s + (lane >> 5), u = 32 * tile + pl_unit_of_row(lane & 31);
-        return k < K && u < H ? w + (size_t)k * H + u : nullptr;
+// W2 for the way back: A[unit i of layer 1, dealt][k = unit j of layer 2]
+__device__ __forceinline__ void pol_stage_w2_back(float* dst, int total, const PolicyArgs& a) {
+    pol_stage(dst, total, a.w1, [=](int i) -> const float* {
+        const int ln = i & 63, tile = (i >> 6) & 1, s = i >> 7;
+        const int u = 32 * tile + pl_unit_of_row(ln & 31), j = 2 * s + (ln >> 5);
+        return u < a.h1 && j < a.h2 ? a.w2 + u * a.h2 + j : nullptr;
     });
 }
 
-__device__ __forceinline__ void pol_stage_biases(float* sb1, float* sb2, const PolicyArgs& a) {
-    if (threadIdx.x < PL_HID) {
-        sb1[threadIdx.x] = (int)threadIdx.x < a.h1 ? a.b1[threadIdx.x] : 0.f;
-        sb2[threadIdx.x] = (int)threadIdx.x < a.h2 ? a.b2[threadIdx.x] : 0.f;
-    }
+// (Wp|wv) for the way back: A[unit of layer 2, dealt][k = output j], 7 outputs padded to 8
+__device__ __forceinline__ void pol_stage_head_back(float* dst, int total, const PolicyArgs& a) {
+    pol_stage(dst, total, a.w1, [=](int i) -> const float* {
+        const int ln = i & 63, tile = (i >> 6) & 1, s = i >> 7;
+        const int u = 32 * tile + pl_unit_of_row(ln & 31), j = 2 * s + (ln >> 5);
+        if (u >= a.h2 || j >= POL_OUT) return nullptr;
+        return j < OC_NUM_ACTIONS ? a.wp + u * OC_NUM_ACTIONS + j : a.wv + u;
+    });
+}
+
+// (Wp|wv) going forward, the last layer, rows in their natural order: six logits and the value
+__device__ __forceinline__ void pol_stage_head_forward(float* dst, int total, const PolicyArgs& a) {
+    pol_stage(dst, total, a.w1, [=](int i) -> const float* {
+        const int ln = i & 63, k = 2 * (i >> 6) + (ln >> 5), r = ln & 31;
+        if (k >= a.h2 || r >= POL_OUT) return nullptr;
+        return r < OC_NUM_ACTIONS ? a.wp + k * OC_NUM_ACTIONS + r : a.wv + k;
+    });
+}
+
+// its bias: bp, bv, zeros
+__device__ __forceinline__ void pol_stage_head_bias(float* sb3, const PolicyArgs& a) {
+    if (threadIdx.x < 32) sb3[threadIdx.x] = threadIdx.x < OC_NUM_ACTIONS ? a.bp[threadIdx.x] : threadIdx.x == OC_NUM_ACTIONS ? a.bv[0] : 0.f;
 }
 
 // which feature row column `col` of tile `row0` reads, relative to `base`: -1 for a row beyond the call or out of range
@@ -167,60 +166,17 @@ __device__ __forceinline__ void pol_load_rows(float* sx, const float* __restrict
     }
 }
 
-// layers 1 and 2 of the tile in the image: the PRE-activations, register reg of lane half h of tile u = unit 32 u + 2 reg + h.
-// TIGHT: the operand reads stay within four K steps of their MFMAs (the backward kernel's registers hold its accumulators; left to
-// itself the scheduler lifts all 64 reads of layer 2 to the top)
-template <bool TIGHT>
-__device__ __forceinline__ void pol_hidden(const float* sw1, const float* sw2, const float* sb1, const float* sb2, const float* sx, int in_dim,
-                                           int lane, pl_f32x16& c0, pl_f32x16& c1, pl_f32x16& d0, pl_f32x16& d1) {
-    const int col = lane & 31, h = lane >> 5, S = in_dim + 2, steps1 = in_dim / 2;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        c0[reg] = sb1[2 * reg + h];
-        c1[reg] = sb1[32 + 2 * reg + h];
-    }
-    const float* const xrow = sx + col * S + h;
-#pragma unroll 4
-    for (int s = 0; s < steps1; ++s) {
-        const float b = xrow[2 * s];
-        c0 = __builtin_amdgcn_mfma_f32_32x32x2f32(sw1[(2 * s) * 64 + lane], b, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(sw1[(2 * s + 1) * 64 + lane], b, c1, 0, 0, 0);
-    }
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        d0[reg] = sb2[2 * reg + h];
-        d1[reg] = sb2[32 + 2 * reg + h];
-    }
-#pragma unroll
-    for (int s = 0; s < PL_STEPS; ++s) {
-        const float b = fmaxf(s < 16 ? c0[s & 15] : c1[s & 15], 0.f);
-        d0 = __builtin_amdgcn_mfma_f32_32x32x2f32(sw2[(2 * s) * 64 + lane], b, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_32x32x2f32(sw2[(2 * s + 1) * 64 + lane], b, d1, 0, 0, 0);
-        if (TIGHT && (s & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
 __global__ __launch_bounds__(BLOCK) void k_policy_forward(PolicyArgs a) {
     extern __shared__ float pol_lds[];
-    float* const sw1 = pol_lds;
-    float* const sw2 = sw1 + pl_w1_floats(a.in_dim);
-    float* const sw3 = sw2 + PL_W2;
-    float* const sb1 = sw3 + PL_W3;
-    float* const sb2 = sb1 + PL_HID;
-    float* const sb3 = sb2 + PL_HID;
+    const PlOperands w = pl_operands(pol_lds, a.in_dim);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* const sx = sb3 + 32 + wave * pl_image_floats(a.in_dim);
+    float* const sx = w.end + wave * pl_image_floats(a.in_dim);
 
-    pol_stage_dealt(sw1, a.w1, a.in_dim, a.h1, a.in_dim / 2);
-    pol_stage_dealt(sw2, a.w2, a.h1, a.h2, PL_STEPS);
-    // the last layer, rows in their natural order: six logits and the value
-    pol_stage(sw3, PL_W3, a.w1, [=](int i) -> const float* {
-        const int ln = i & 63, k = 2 * (i >> 6) + (ln >> 5), r = ln & 31;
-        if (k >= a.h2 || r >= POL_OUT) return nullptr;
-        return r < OC_NUM_ACTIONS ? a.wp + k * OC_NUM_ACTIONS + r : a.wv + k;
-    });
-    pol_stage_biases(sb1, sb2, a);
-    if (threadIdx.x < 32) sb3[threadIdx.x] = threadIdx.x < OC_NUM_ACTIONS ? a.bp[threadIdx.x] : threadIdx.x == OC_NUM_ACTIONS ? a.bv[0] : 0.f;
+    pol_stage_dealt(w.sw1, a.w1, a.in_dim, a.h1, a.in_dim / 2);
+    pol_stage_dealt(w.sw2, a.w2, a.h1, a.h2, PL_STEPS);
+    pol_stage_head_forward(w.sw3, PL_W3, a);
+    pol_stage_biases(w.sb1, w.sb2, a.b1, a.b2, a.h1, a.h2);
+    pol_stage_head_bias(w.sb3, a);
     __syncthreads();
 
     const int col = lane & 31, h = lane >> 5;
@@ -232,15 +188,9 @@ __global__ __launch_bounds__(BLOCK) void k_policy_forward(PolicyArgs a) {
         pl_wave_fence();  // (the reads of the previous tile are done)
         pol_load_rows(sx, a.features, base, rel, a.in_dim, lane);
         pl_wave_fence();
-        pl_f32x16 c0, c1, d0, d1, o;
-        pol_hidden<false>(sw1, sw2, sb1, sb2, sx, a.in_dim, lane, c0, c1, d0, d1);
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) o[reg] = sb3[(reg & 3) + 8 * (reg >> 2) + 4 * h];
-#pragma unroll
-        for (int s = 0; s < PL_STEPS; ++s) {
-            const float b = fmaxf(s < 16 ? d0[s & 15] : d1[s & 15], 0.f);
-            o = __builtin_amdgcn_mfma_f32_32x32x2f32(sw3[s * 64 + lane], b, o, 0, 0, 0);
-        }
+        pl_f32x16 c0, c1, d0, d1;
+        pol_hidden<false>(w.sw1, w.sw2, w.sb1, w.sb2, sx, a.in_dim, lane, c0, c1, d0, d1);
+        const pl_f32x16 o = pol_head(w.sw3, w.sb3, lane, d0, d1);
         // ---- rows 0..3 sit in registers 0..3 of lane half 0, rows 4..6 in registers 0..2 of half 1
         if (row0 + col < a.n) {
             const bool ok = rel >= 0;
@@ -282,6 +232,8 @@ __global__ __launch_bounds__(BLOCK) void k_policy_backward(PolicyArgs a) {
 
     pol_stage_dealt(sw1, a.w1, a.in_dim, a.h1, a.in_dim / 2);
     pol_stage_dealt(sw2, a.w2, a.h1, a.h2, PL_STEPS);
+    // (pol_stage_w2_back and pol_stage_head_back, word for word, as this kernel's own lambdas: through the functions its rows on a
+    // grid of one wave of workgroups were 0.5-0.8 us of 80 slower on the device; docs/NOTEBOOK.md)
     // W2 for the way back: A[unit i of layer 1, dealt][k = unit j of layer 2]
     pol_stage(sw2t, PL_W2, a.w1, [=](int i) -> const float* {
         const int ln = i & 63, tile = (i >> 6) & 1, s = i >> 7;
@@ -295,7 +247,7 @@ __global__ __launch_bounds__(BLOCK) void k_policy_backward(PolicyArgs a) {
         if (u >= a.h2 || j >= POL_OUT) return nullptr;
         return j < OC_NUM_ACTIONS ? a.wp + u * OC_NUM_ACTIONS + j : a.wv + u;
     });
-    pol_stage_biases(sb1, sb2, a);
+    pol_stage_biases(sb1, sb2, a.b1, a.b2, a.h1, a.h2);
     __syncthreads();
 
     const int col = lane & 31, h = lane >> 5, S = a.in_dim + 2;

@@ -3,7 +3,8 @@
 // workgroups and MODE 2, the pose one step ahead in one wavefront) and 2 (MODE 0: arithmetic movement), so that a clean build runs four hipcc processes side by side (overcooked_ai_amd/build.py) instead
 // of one 80-second compile.  oc_amd.hip (choose_rollout) picks the instance; the unit that compiles it launches it
 // (launch_rollout) or, for oc_rollout_plan, names it and its LDS bytes (describe_rollout).
-// The OC_R4_PART == 2 unit, the shortest of the four, also compiles partner.hpp (k_partner_logits and its two entry points) and
+// The OC_R4_PART == 2 unit, the shortest of the four, also compiles mlp_tile.hpp (the MFMA tile of the dense network: device functions
+// for the kernels of partner.hpp, partner_pool.hpp, policy.hpp and bc_fused.hpp), partner.hpp (k_partner_logits and its two entry points) and
 // gae.hpp (k_gae, k_gae_moments and theirs), ppo_loss.hpp (k_ppo_loss, k_ppo_loss_stats and theirs) and policy.hpp (k_policy_forward,
 // k_policy_backward, k_policy_grad_sum and theirs), adam.hpp (k_adam_step and its two), bc_loss.hpp (k_bc_loss, k_bc_loss_stats and theirs),
 // update_chain.hpp (host code only: oc_ppo_update and oc_bc_update), bc_fused.hpp (k_bc_epoch_fused and its two) and sample_index.hpp (k_sample_count, k_sample_scan, k_sample_write,
@@ -170,6 +171,7 @@ template void describe_rollout<OC_R4_PART>(const Rollout4Call& c, char* out, siz
 }  // namespace oc_detail
 
 #if OC_R4_PART == 2
+#include "mlp_tile.hpp" // the MFMA tile of the dense network under the five kernels of partner.hpp, partner_pool.hpp, policy.hpp and bc_fused.hpp
 #include "partner.hpp"  // k_partner_logits, oc_partner_logits, oc_partner_logits_plan
 #include "gae.hpp"      // k_gae, k_gae_moments, oc_gae, oc_gae_plan
 #include "ppo_loss.hpp" // k_ppo_loss, k_ppo_loss_stats, oc_ppo_loss, oc_ppo_loss_plan
