@@ -1651,6 +1651,77 @@ int oc_sample_permute(const int32_t* d_ids, const int64_t* d_count, int64_t n_ou
 int oc_sample_index_plan(int64_t n_samples, int with_seat, int with_actions, int with_ids, int64_t n_out, int64_t n_learner, char* out,
                          size_t out_size);
 
+/*
+ * Episode outcomes of a collected batch by partner member and seat (additive to ABI version 6: two new entry points, the version
+ * stays) — how well anyone played, from the arrays the step calls already write (csrc/outcomes.hpp).  oc_multi_agent_step_sample
+ * copies the episode totals of every env to d_ep_returns_out at every step; they are final where the done mask is set.  Kept per
+ * step, time-major like OcGaeBatch, next to the done mask, the seats and the members of a partner pool, one reduction gives the
+ * table cross-play tables and prioritised partner sampling are built from.
+ *
+ * Episodes.  An episode ends at (t, e) iff d_done[t][e] != 0.  Its row is d_ep_returns[t][e][0..3] = (sparse p0, sparse p1, shaped
+ * p0, shaped p1), and R = (double) sparse p0 + (double) sparse p1.  d_ep_returns is READ ONLY WHERE d_done IS SET: nothing else the
+ * array holds, a NaN included, reaches the result.
+ *
+ * Groups.  G = 1 without d_seat, else 1 + 2 K (K = n_members).  With s = d_seat[t][e] and m = d_member[t][e] (0 without d_member):
+ *   no d_seat, or s == 255      group 0, "no partner" (m is not looked at)
+ *   s <= 1 and m < K            group 1 + 2 m + s, "member m plays seat s"
+ *   anything else               no group: the episode adds 1 to d_table[G][0], "unattributed", and nothing else anywhere in d_table
+ *
+ * d_table, f64 [G + 1][8].  Row g < G, over the episodes of group g:
+ *   [0] episodes   [1] sum R   [2] sum R * R   [3] min R (+inf: no episode)   [4] max R (-inf: no episode)
+ *   [5] sum shaped p0   [6] sum shaped p1   [7] sum sparse p0
+ * Row G holds the unattributed count in [0] and 0, 0, +inf, -inf, 0, 0, 0 behind it.
+ * d_env_table, f64 [n_envs][4], optional: episodes, sum R, sum R * R, sum ((double) shaped p0 + (double) shaped p1) of env e over
+ * ALL its episodes, attributed or not, added in ascending t.  A caller groups it by anything constant per env (the layout of a mixed
+ * batch) with one index_add.
+ *
+ * Order of summation — a function of (n_steps, n_envs, the block of envs B = 256 the plan names) and of nothing else.  Every sum
+ * starts at +0.0, every min at +inf, every max at -inf; a product R * R is rounded to f64 before it is added; min and max are fmin
+ * and fmax.  "Adding" a table to another adds columns 0, 1, 2, 5, 6, 7, takes the min of column 3 and the max of column 4, entry by
+ * entry, the running table on the left.
+ *   1. Wavefront q of block b holds the envs b * B + 64 q .. b * B + 64 q + 63 (those below n_envs).  Its table starts empty and
+ *      takes its episodes one at a time, in ascending t and, within a step, in ascending e.
+ *   2. The partial of block b (d_scratch[b]) is the empty table plus the tables of its wavefronts q = 0, 1, 2, 3, in that order.
+ *   3. d_table is the empty table plus the partials b = 0, 1, ..., ceil(n_envs / B) - 1, in that order.
+ * No atomics on floating-point data, no look-back, no spin flags: the same call on the same inputs gives the same bytes.  Counts, min
+ * and max are exact whatever the order, and so is every sum of the env's own returns (multiples of 20, sums of 3s and 5s).
+ * Cost: the done lanes of a wavefront take turns.  64 envs of a wavefront finishing on one step (equal horizons) are 64 short turns
+ * on that step, once per horizon; a batch that is done on every step takes a turn per env and step: slow, and correct.
+ */
+typedef struct OcOutcomeBatch {
+    const uint8_t* d_done;        /* [n_steps][n_envs] u8; any address */
+    const float* d_ep_returns;    /* [n_steps][n_envs][4] f32; 16-byte aligned; read only where d_done is set */
+    const uint8_t* d_seat;        /* [n_steps][n_envs] u8 or NULL (no partner anywhere: G = 1); any address */
+    const uint8_t* d_member;      /* [n_steps][n_envs] u8 or NULL (one partner policy: n_members == 1); any address; needs d_seat */
+    double* d_table;              /* [G + 1][8] f64 out; 8-byte aligned; required */
+    double* d_env_table;          /* [n_envs][4] f64 out or NULL; 8-byte aligned */
+    double* d_scratch;            /* the bytes oc_outcome_plan states (ceil(n_envs / 256) * (G + 1) * 64); 8-byte aligned; what it held does not matter */
+    int64_t n_envs;               /* N >= 0; 0 writes the empty table */
+    int64_t n_steps;              /* T >= 1; T * N < 2^31 */
+    int n_members;                /* K, 1..16; 1 when d_member is NULL */
+} OcOutcomeBatch;
+
+/*
+ * oc_outcome_table — two launches on the caller's stream: k_outcomes, a lane per env walking t upwards with the bytes of the next 16
+ * steps in flight, writes one partial per block of 256 envs (and d_env_table); k_outcome_sum, one wavefront, adds the partials.
+ * n_envs == 0 launches k_outcome_sum alone, which writes the empty table.
+ * OC_EINVAL, before any device call, with this entry point's name in front of the message: a NULL batch or d_table; a NULL d_done,
+ * d_ep_returns or d_scratch where n_envs > 0; a d_ep_returns that is not 16-byte aligned; a d_table, d_env_table or d_scratch that is
+ * not 8-byte aligned; d_member without d_seat; n_members outside 1..16, or not 1 without d_member; n_steps < 1; n_envs < 0;
+ * n_steps * n_envs >= 2^31.
+ */
+int oc_outcome_table(const OcOutcomeBatch* q, void* stream);
+
+/*
+ * oc_outcome_plan — what a call would launch, as text (with_seat, with_member, with_env_table: the optional array is given):
+ *   "k_outcomes<SEAT=true, MEMBER=true, ENV=false> grid=256, 256 lanes (one per env; one partial per block of 256 envs), 16 steps per prefetch block, 25 block(s) + k_outcome_sum grid=1, 64 lanes; G = 7 group(s), table 512 B, scratch 131072 B"
+ *   "k_outcome_sum grid=1, 64 lanes (no envs: the empty table); G = 1 group(s), table 128 B, scratch 0 B"
+ * Usable without a GPU, like the other plan calls.  The checks that need no array apply, under oc_outcome_table's name.
+ *   out, out_size caller's text buffer (>= 384 bytes holds every answer)
+ */
+int oc_outcome_plan(int64_t n_envs, int64_t n_steps, int with_seat, int with_member, int n_members, int with_env_table, char* out,
+                    size_t out_size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,7 +32,8 @@ EXPORTS = ("oc_abi_version", "oc_layout_size", "oc_last_error", "oc_state_planes
            "oc_partner_logits", "oc_partner_logits_plan", "oc_gae", "oc_gae_plan", "oc_ppo_loss", "oc_ppo_loss_plan",
            "oc_policy_forward", "oc_policy_backward", "oc_policy_plan", "oc_adam_step", "oc_adam_plan", "oc_ppo_update", "oc_ppo_update_plan",
            "oc_bc_loss", "oc_bc_loss_plan", "oc_bc_update", "oc_bc_update_plan", "oc_bc_epoch_fused", "oc_bc_epoch_fused_plan",
-           "oc_sample_select", "oc_sample_permute", "oc_sample_index_plan", "oc_partner_pool_logits", "oc_partner_pool_plan")
+           "oc_sample_select", "oc_sample_permute", "oc_sample_index_plan", "oc_partner_pool_logits", "oc_partner_pool_plan",
+           "oc_outcome_table", "oc_outcome_plan")
 MAX_POOL = 16
 MB_STATE_IN, MB_ACTIONS, MB_STATE_OUT, MB_REWARDS, MB_FLAGS, MB_EVENTS, MB_BYTES = 256, 336, 512, 592, 608, 616, 4096
 
@@ -95,6 +96,12 @@ class OcGaeBatch(ctypes.Structure):
     _fields_ = [("d_rewards", ctypes.c_void_p), ("d_values", ctypes.c_void_p), ("d_last_values", ctypes.c_void_p), ("d_done", ctypes.c_void_p),
                 ("d_seat", ctypes.c_void_p), ("d_advantages", ctypes.c_void_p), ("d_targets", ctypes.c_void_p), ("d_partials", ctypes.c_void_p),
                 ("d_moments", ctypes.c_void_p), ("n_steps", ctypes.c_int64), ("gamma", ctypes.c_float), ("lam", ctypes.c_float)]
+
+
+class OcOutcomeBatch(ctypes.Structure):
+    _fields_ = [("d_done", ctypes.c_void_p), ("d_ep_returns", ctypes.c_void_p), ("d_seat", ctypes.c_void_p), ("d_member", ctypes.c_void_p),
+                ("d_table", ctypes.c_void_p), ("d_env_table", ctypes.c_void_p), ("d_scratch", ctypes.c_void_p), ("n_envs", ctypes.c_int64),
+                ("n_steps", ctypes.c_int64), ("n_members", ctypes.c_int)]
 
 
 class OcPpoLoss(ctypes.Structure):
@@ -324,6 +331,10 @@ def load():
     L.oc_partner_pool_logits.argtypes = [bp, ppp, ctypes.POINTER(OcPartnerSeats), vp, i32, vp, vp, vp]
     L.oc_partner_pool_plan.restype = i32
     L.oc_partner_pool_plan.argtypes = [bp, ppp, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.oc_outcome_table.restype = i32
+    L.oc_outcome_table.argtypes = [ctypes.POINTER(OcOutcomeBatch), vp]
+    L.oc_outcome_plan.restype = i32
+    L.oc_outcome_plan.argtypes = [i64, i64, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
     if L.oc_abi_version() != ABI_VERSION:
         raise OcAmdError("liboc_amd.so ABI version %d != expected %d; rebuild" % (L.oc_abi_version(), ABI_VERSION))
     if L.oc_layout_size() != 256:

@@ -8,7 +8,7 @@
 // gae.hpp (k_gae, k_gae_moments and theirs), ppo_loss.hpp (k_ppo_loss, k_ppo_loss_stats and theirs) and policy.hpp (k_policy_forward,
 // k_policy_backward, k_policy_grad_sum and theirs), adam.hpp (k_adam_step and its two), bc_loss.hpp (k_bc_loss, k_bc_loss_stats and theirs),
 // update_chain.hpp (host code only: oc_ppo_update and oc_bc_update), bc_fused.hpp (k_bc_epoch_fused and its two) and sample_index.hpp (k_sample_count, k_sample_scan, k_sample_write,
-// k_sample_permute and their three).
+// k_sample_permute and their three), and outcomes.hpp (k_outcomes, k_outcome_sum and their two).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -174,6 +174,7 @@ template void describe_rollout<OC_R4_PART>(const Rollout4Call& c, char* out, siz
 #include "mlp_tile.hpp" // the MFMA tile of the dense network under the five kernels of partner.hpp, partner_pool.hpp, policy.hpp and bc_fused.hpp
 #include "partner.hpp"  // k_partner_logits, oc_partner_logits, oc_partner_logits_plan
 #include "gae.hpp"      // k_gae, k_gae_moments, oc_gae, oc_gae_plan
+#include "outcomes.hpp" // k_outcomes, k_outcome_sum, oc_outcome_table, oc_outcome_plan
 #include "ppo_loss.hpp" // k_ppo_loss, k_ppo_loss_stats, oc_ppo_loss, oc_ppo_loss_plan
 #include "policy.hpp"   // k_policy_forward, k_policy_backward, k_policy_grad_sum, oc_policy_forward, oc_policy_backward, oc_policy_plan
 #include "adam.hpp"     // k_adam_step, oc_adam_step, oc_adam_plan

@@ -351,12 +351,14 @@ class VecOvercookedMultiAgent:
             raise ValueError("actions must be a contiguous uint8 [n_envs, 2] tensor on %s" % v.device)
         return self._step(actions.data_ptr(), None)
 
-    def _step(self, actions_ptr, sampler, shaped=None, done=None):
-        """step() with the caller's actions (sampler None), or step_sampled() with an OcActionSampler in their place.  shaped, done:
-        the tensors that receive the training rewards and the done mask in place of the persistent buffers (step_sampled's `into`)."""
+    def _step(self, actions_ptr, sampler, shaped=None, done=None, ep_returns=None):
+        """step() with the caller's actions (sampler None), or step_sampled() with an OcActionSampler in their place.  shaped, done,
+        ep_returns: the tensors that receive the training rewards, the done mask and the copy of the episode returns in place of the
+        persistent buffers (step_sampled's `into`)."""
         v = self.venv
         shaped = self.shaped if shaped is None else shaped
         done = self.done if done is None else done
+        ep_returns = self.ep_returns if ep_returns is None else ep_returns
         obs, code, start, sink = self._call_args()
         if self.use_phi:
             if self._phi_args is None:
@@ -366,7 +368,7 @@ class VecOvercookedMultiAgent:
             plan, off, tables = self._phi_args
         else:
             plan = off = tables = None
-        args = (v._bref, v._state_ptr, actions_ptr if sampler is None else sampler, v._rewards_ptr, v._flags_ptr, v._ep_ptr, self.ep_returns.data_ptr(), plan, off,
+        args = (v._bref, v._state_ptr, actions_ptr if sampler is None else sampler, v._rewards_ptr, v._flags_ptr, v._ep_ptr, ep_returns.data_ptr(), plan, off,
                 tables, self.phi_next.data_ptr(), self.phi_cur.data_ptr(), self.phi_start.data_ptr(), float(self.reward_shaping_factor),
                 shaped.data_ptr(), done.data_ptr(), obs.data_ptr() if obs is not None else None, code, self.horizon)
         feat = None
@@ -391,7 +393,7 @@ class VecOvercookedMultiAgent:
         self._last_done = done
         self._feat_current = feat is not None
         infos = {"sparse_r_by_agent": v.rewards[:, 0:2], "shaped_r_by_agent": v.rewards[:, 2:4], "flags": v.flags,
-                 "ep_returns": self.ep_returns}  # episode totals so far; final where done (the reset cleared the live ones)
+                 "ep_returns": ep_returns}  # episode totals so far; final where done (the reset cleared the live ones)
         if self.use_phi:
             infos["phi_s_prime"] = self.phi_next
         if feat is not None:
@@ -431,16 +433,25 @@ class VecOvercookedMultiAgent:
         return actions, logp
 
     def _checked_row(self, into):
-        """step_sampled's `into`: a TrajectoryBuffer row of this env's batch size, on its device."""
+        """step_sampled's `into`: a TrajectoryBuffer row of this env's batch size, on its device.  ep_returns and, with a PartnerPool,
+        member are optional (a buffer with keep_returns has them)."""
         torch, dev = self._torch, self.venv.state.device
         n = self.n_envs
-        for name, dtype, shape in (("rewards", torch.float64, (n, 2)), ("done", torch.uint8, (n,)), ("actions", torch.uint8, (n, 2)),
-                                   ("logp", torch.float32, (n, 2))) + ((("seat", torch.uint8, (n,)),) if self.bc_policy is not None else ()):
+        wanted = (("rewards", torch.float64, (n, 2)), ("done", torch.uint8, (n,)), ("actions", torch.uint8, (n, 2)), ("logp", torch.float32, (n, 2)))
+        if self.bc_policy is not None:
+            wanted += (("seat", torch.uint8, (n,)),)
+        if getattr(into, "ep_returns", None) is not None:
+            wanted += (("ep_returns", torch.float32, (n, 4)),)
+        if self._pool is not None and getattr(into, "member", None) is not None:
+            wanted += (("member", torch.uint8, (n,)),)
+        for name, dtype, shape in wanted:
             t = getattr(into, name, None)
             if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
                 raise ValueError("into.%s must be a contiguous %s %s tensor on %s" % (name, str(dtype).replace("torch.", ""), list(shape), dev))
         if into.rewards.data_ptr() % 16 or into.logp.data_ptr() % 8 or into.actions.data_ptr() % 2:
             raise ValueError("into: rewards must be 16-byte, logp 8-byte and actions 2-byte aligned")
+        if getattr(into, "ep_returns", None) is not None and into.ep_returns.data_ptr() % 16:
+            raise ValueError("into: ep_returns must be 16-byte aligned")
         return into
 
     def step_sampled(self, logits, greedy=False, into=None):
@@ -457,7 +468,9 @@ class VecOvercookedMultiAgent:
         into: a row of a trajectory_buffer.TrajectoryBuffer (`buf.row(t, values)`).  The same C call then writes the training
         rewards, the done mask, the drawn actions and their log-probabilities into that row in place of the persistent buffers —
         which this call leaves untouched — and returns the row's views; with a bc_policy the seats of this step are copied into
-        the row's seat (one copy).  The next call, with or without `into`, reseats by the done mask this call wrote.  Observations
+        the row's seat (one copy), and with a PartnerPool their members into the row's member where it has one.  A row with
+        ep_returns (a buffer with keep_returns) also receives the call's copy of the episode returns — infos["ep_returns"] is then
+        the row's view — for `TrajectoryBuffer.outcomes()`.  The next call, with or without `into`, reseats by the done mask this call wrote.  Observations
         stay in their persistent buffers: the policy's next forward pass reads them there."""
         if into is not None:
             self._checked_row(into)
@@ -465,11 +478,13 @@ class VecOvercookedMultiAgent:
             self.partner_logits(logits)
             if into is not None:
                 into.seat.copy_(self.seat)
+                if self._pool is not None and getattr(into, "member", None) is not None:
+                    into.member.copy_(self.member)
         actions, logp, s = self._sampler(logits, greedy, into)
         if into is None:
             out, shaped, done, infos = self._step(None, s)
         else:
-            out, shaped, done, infos = self._step(None, s, into.rewards, into.done)
+            out, shaped, done, infos = self._step(None, s, into.rewards, into.done, getattr(into, "ep_returns", None))
         infos["actions"], infos["logp"] = actions, logp
         if self.bc_policy is not None:
             infos["seat"] = self.seat
@@ -501,6 +516,7 @@ class VecOvercookedMultiAgent:
         s.bc_factor, s.seed, s.env_offset, s.step = float(self.bc_factor), v.seed, v.env_offset, self.sample_step
         if self._pool is not None:  # (the stream is _launch's last argument: the scratch goes in front of it)
             self._pool.d_member = self.member.data_ptr()
+            self._pool.thresholds = self.bc_policy.thresholds_ref()  # (the pool's current ones: PartnerPool.set_weights)
             rc = v._launch(v.lib.oc_partner_pool_logits, v._bref, ctypes.byref(self._pool), ctypes.byref(s), self._feat_buffer().data_ptr(),
                            self.num_pots, logits.data_ptr(), self.pool_scratch.data_ptr())
             self._lib.check(rc, "oc_partner_pool_logits")

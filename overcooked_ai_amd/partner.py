@@ -83,8 +83,9 @@ class PartnerPool:
     """1 to 16 `DensePolicy` on one device with one `in_dim` (h1 and h2 may differ): the members of `oc_partner_pool_logits`.
     `VecOvercookedMultiAgent(..., bc_policy=pool)` draws one of them for every new partner, uniformly, or by `weights`
     (non-negative numbers, one per member: see `thresholds_of` for their rounding).  `set_member(i, policy)` swaps a member in place
-    — a league that ages — for every env built on this pool, from its next call on.  `n_members`, `in_dim`, `policies`,
-    `thresholds` (None: uniform)."""
+    — a league that ages — for every env built on this pool, from its next call on; `set_weights(weights)` changes the draw the
+    same way (`rank_weights`: towards the members the learner does worst with).  `n_members`, `in_dim`, `policies`, `thresholds`
+    (None: uniform)."""
 
     def __init__(self, policies, weights=None):
         from . import _lib
@@ -98,12 +99,26 @@ class PartnerPool:
         for i, p in enumerate(policies):
             self.set_member(i, p)
         self.thresholds = self._thresholds = None
-        if weights is not None:
-            weights = list(weights)
-            if len(weights) != self.n_members:
-                raise ValueError("PartnerPool: %d weights for %d members" % (len(weights), self.n_members))
-            self.thresholds = thresholds_of(weights)
-            self._thresholds = (ctypes.c_uint32 * max(1, self.n_members - 1))(*self.thresholds)
+        self._threshold_store = (ctypes.c_uint32 * max(1, self.n_members - 1))()  # (one array for the pool's life: set_weights rewrites it)
+        self.set_weights(weights)
+
+    def set_weights(self, weights):
+        """New draw weights (non-negative numbers, one per member; None: uniform again) for every env built on this pool, from its
+        next call on, as `set_member` does for a member: envs already seated keep their partner until their episode ends.  Works on
+        a pool built uniform as well.  `thresholds` follows (`thresholds_of`)."""
+        if weights is None:
+            self.thresholds = self._thresholds = None
+            return
+        weights = list(weights)
+        if len(weights) != self.n_members:
+            raise ValueError("PartnerPool: %d weights for %d members" % (len(weights), self.n_members))
+        thresholds = thresholds_of(weights)
+        self._threshold_store[:len(thresholds)] = thresholds
+        self.thresholds, self._thresholds = thresholds, self._threshold_store
+
+    def thresholds_ref(self):
+        """The OcPartnerPool.thresholds pointer of the current weights (None: uniform)."""
+        return ctypes.cast(self._thresholds, ctypes.POINTER(ctypes.c_uint32)) if self._thresholds is not None else None
 
     def set_member(self, i, policy):
         if not isinstance(policy, DensePolicy):
@@ -120,6 +135,26 @@ class PartnerPool:
         """The OcPartnerPool of an env whose member array is the uint8 tensor `member` (the pool's arrays are shared)."""
         from . import _lib
 
-        return _lib.OcPartnerPool(self._members, self.n_members,
-                                  ctypes.cast(self._thresholds, ctypes.POINTER(ctypes.c_uint32)) if self._thresholds is not None else None,
-                                  member.data_ptr())
+        return _lib.OcPartnerPool(self._members, self.n_members, self.thresholds_ref(), member.data_ptr())
+
+
+def rank_weights(mean_returns, beta=1.0):
+    """Prioritised partner sampling (the rank-based prioritisation of the maximum-entropy-population work): weights proportional to
+    rank^beta, where the member with the WORST mean return has the highest rank K' (the number of distinct means, a member without
+    an episode counting as worse than any) and the best has rank 1; members with equal means share a rank.  mean_returns: K
+    numbers, NaN or None for a member without an episode (`Outcomes.by_member()["mean"]` of one seat, or averaged over both).
+    Returns K floats summing to 1, for `PartnerPool.set_weights`.  Plain Python on K numbers; beta = 0 is uniform."""
+    import math
+
+    means = [None if m is None or math.isnan(float(m)) else float(m) for m in mean_returns]
+    if not means:
+        raise ValueError("rank_weights: no members")
+    beta = float(beta)
+    if beta < 0:
+        raise ValueError("rank_weights: beta must not be negative, not %r" % beta)
+    levels = sorted({m for m in means if m is not None}, reverse=True)  # best first: rank 1
+    rank = {m: i + 1 for i, m in enumerate(levels)}
+    worst = len(levels) + (1 if any(m is None for m in means) else 0)
+    raw = [float((worst if m is None else rank[m]) ** beta) for m in means]
+    total = sum(raw)
+    return [x / total for x in raw]

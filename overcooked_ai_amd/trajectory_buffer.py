@@ -20,18 +20,70 @@ behaviour-cloning partner a minibatch then holds only samples the loss counts.
 
 Row t of every tensor meets the alignment the step and the sampler ask for whatever N is: rewards rows are 16 N bytes apart (16-byte
 aligned), logp and values rows 8 N (8), actions rows 2 N (2), done and seat rows N (any address) — a fresh allocation starts on a
-multiple of 256."""
+multiple of 256.  With keep_returns, ep_returns rows are 16 N bytes apart (16-byte aligned) and member rows N (any address);
+`outcomes()` is `outcomes.outcome_table` (oc_outcome_table) over done, ep_returns, seat and member: the finished episodes by partner
+member and seat.  `ReturnsBuffer` keeps those four alone (`outcomes.evaluate`)."""
 import collections
 
-TrajectoryRow = collections.namedtuple("TrajectoryRow", "rewards done actions logp seat")
+# (ep_returns and member: trailing and defaulted, so that a five-field construction keeps working)
+TrajectoryRow = collections.namedtuple("TrajectoryRow", "rewards done actions logp seat ep_returns member", defaults=(None, None))
 
 ROW_BYTES = {"rewards": 16, "done": 1, "actions": 2, "logp": 8, "values": 8, "seat": 1}  # bytes per env of a row
 ROW_ALIGN = {"rewards": 16, "done": 1, "actions": 2, "logp": 8, "values": 8, "seat": 1}  # what the C-ABI asks of a row's address
 
 
+# the rows a buffer with keep_returns adds (tables of their own: tests/test_host_gae.py holds the two above to exactly their six rows)
+RETURNS_ROW_BYTES = {"ep_returns": 16, "member": 1}
+RETURNS_ROW_ALIGN = {"ep_returns": 16, "member": 1}
+
+
 def row_offsets(name, T, n_envs):
     """Byte offsets of rows 0..T-1 of tensor `name` from its base."""
-    return [t * n_envs * ROW_BYTES[name] for t in range(T)]
+    nbytes = ROW_BYTES[name] if name in ROW_BYTES else RETURNS_ROW_BYTES[name]
+    return [t * n_envs * nbytes for t in range(T)]
+
+
+def _outcomes_of(buf, per_env):
+    from .outcomes import outcome_table
+
+    if buf.ep_returns is None:
+        raise ValueError("outcomes() needs a buffer with keep_returns")
+    pool = getattr(buf.tenv, "_pool", None)
+    return outcome_table(buf.done, buf.ep_returns, seat=buf.seat, member=buf.member,
+                         n_members=buf.tenv.bc_policy.n_members if pool is not None else None, per_env=per_env)
+
+
+class ReturnsBuffer:
+    """What `outcomes.evaluate` collects through: done uint8 [T, N], ep_returns float32 [T, N, 4] and, with a bc_policy, seat (and with
+    a `PartnerPool` member) uint8 [T, N], time-major, and nothing else.  `row(t)` is a `TrajectoryRow` for `step_sampled(into=...)`
+    whose rewards, actions and logp are ONE [N, 2] row shared by every t: the step call has to write them somewhere, and an
+    evaluation does not read them."""
+
+    def __init__(self, tenv, T):
+        import torch
+
+        T = int(T)
+        if T < 1:
+            raise ValueError("ReturnsBuffer: T must be at least 1, not %d" % T)
+        self.tenv, self.T, self.n_envs = tenv, T, tenv.n_envs
+        N, dev = tenv.n_envs, tenv.venv.device
+        self.done = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+        self.ep_returns = torch.zeros((T, N, 4), dtype=torch.float32, device=dev)
+        self.seat = torch.full((T, N), 255, dtype=torch.uint8, device=dev) if tenv.bc_policy is not None else None
+        self.member = torch.full((T, N), 255, dtype=torch.uint8, device=dev) if getattr(tenv, "_pool", None) is not None else None
+        self._shared = (torch.zeros((N, 2), dtype=torch.float64, device=dev), torch.zeros((N, 2), dtype=torch.uint8, device=dev),
+                        torch.zeros((N, 2), dtype=torch.float32, device=dev))
+
+    def row(self, t):
+        if not 0 <= t < self.T:
+            raise ValueError("ReturnsBuffer.row: t = %d outside 0..%d" % (t, self.T - 1))
+        rewards, actions, logp = self._shared
+        return TrajectoryRow(rewards, self.done[t], actions, logp, self.seat[t] if self.seat is not None else None, self.ep_returns[t],
+                             self.member[t] if self.member is not None else None)
+
+    def outcomes(self, per_env=False):
+        """outcomes.outcome_table over the whole buffer, as `TrajectoryBuffer.outcomes`."""
+        return _outcomes_of(self, per_env)
 
 
 class TrajectoryBuffer:
@@ -40,9 +92,11 @@ class TrajectoryBuffer:
     None).  keep_obs: also obs [T, N, 2, W, H, 26] (the env's obs_dtype) and / or features float32 [T, N, 2, F], whichever the
     env's observation kind has, copied by row() from the env's persistent observation buffers — the observation step t starts
     from, which the policy has just read there.  keep_logits: also logits float32 [T, N, 2, 6], the learner's logits that row()
-    is given (the exact KL of the loss needs them)."""
+    is given (the exact KL of the loss needs them).  keep_returns: also ep_returns float32 [T, N, 4] — the episode totals the step
+    call copies out (sparse p0, sparse p1, shaped p0, shaped p1), final where done is set — and, for an env with a
+    `partner.PartnerPool`, member uint8 [T, N]: what `outcomes()` reduces."""
 
-    def __init__(self, tenv, T, keep_obs=False, keep_logits=False):
+    def __init__(self, tenv, T, keep_obs=False, keep_logits=False, keep_returns=False):
         import torch
 
         T = int(T)
@@ -66,8 +120,15 @@ class TrajectoryBuffer:
                 self.obs = torch.zeros((T,) + tuple(tenv._obs_buffer().shape), dtype=tenv.obs_dtype, device=dev)
             if tenv.obs_kind in ("features", "both"):
                 self.features = torch.zeros((T,) + tuple(tenv._feat_buffer().shape), dtype=torch.float32, device=dev)
+        self.ep_returns = self.member = None
+        if keep_returns:
+            self.ep_returns = torch.zeros((T, N, 4), dtype=torch.float32, device=dev)
+            if getattr(tenv, "_pool", None) is not None:
+                self.member = torch.full((T, N), 255, dtype=torch.uint8, device=dev)
         self._rows = [TrajectoryRow(self.rewards[t], self.done[t], self.actions[t], self.logp[t],
-                                    self.seat[t] if self.seat is not None else None) for t in range(T)]
+                                    self.seat[t] if self.seat is not None else None,
+                                    self.ep_returns[t] if self.ep_returns is not None else None,
+                                    self.member[t] if self.member is not None else None) for t in range(T)]
 
     def row(self, t, values, logits=None):
         """The destinations of step t, for `step_sampled(into=...)`; `values` (float32 [N, 2], the policy's value estimates of the
@@ -100,6 +161,11 @@ class TrajectoryBuffer:
 
         return gae(self.rewards, self.values, self.done, gamma, lam, last_values=self.last_values, seat=self.seat, moments=moments,
                    out=out)
+
+    def outcomes(self, per_env=False):
+        """outcomes.outcome_table over the whole buffer (oc_outcome_table, two launches): the finished episodes by partner member and
+        seat, as an `outcomes.Outcomes`; per_env: also its env table.  Needs keep_returns.  Nothing here waits for the device."""
+        return _outcomes_of(self, per_env)
 
     def learner_batch(self, advantages, targets, moments=None):
         """The buffer as `ppo_loss.ppo_loss` reads it: flat [S] views (S = T * N * 2, sample (t * N + e) * 2 + p) of the actions, logp
